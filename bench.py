@@ -1,8 +1,16 @@
 #!/usr/bin/env python
 """bench.py -- VGICP linearise throughput on MI355X (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: set-up, the untimed device wake-up and W warm-up steps, the K timed steps, the outputs (--dump-outputs) and
+the result line.  --full adds everything else this file measures or checks, as described below: the cold-protocol figure (ms_per_step_cold), the
+back-to-back and rocprofv3 roofline figures, the CPU baseline and the parity against the CPU checker, the optional legs (configs, big source, c4), the
+other N > 1 exchange forms with their verification, and bench_detail.json.
+--dump-outputs DIR: after the timed steps, the records the timed path delivered in its last step -- one per rank, decoded as a caller receives them
+(H_target, H_source, H_target_source [R x 6 x 6], b_target, b_source [R x 6], error, num_inliers [R]) -- as DIR/<name>.npy in float64.  The inputs
+are seeded: the same arguments give the same inputs from run to run.
 
 Workload (config.workload): BASELINE.json configs[1] -- ONE VGICP factor per GPU, 1 M synthetic source points vs a 2 M-point GaussianVoxelMap at 0.5 m
 (gtsam_points_amd.synthetic.make_c2_workload; rank r uses seed 42 + r).  A "step" is one linearize() pass as the optimizer sees it.
@@ -14,9 +22,9 @@ Workload (config.workload): BASELINE.json configs[1] -- ONE VGICP factor per GPU
          computed (exchange_verified), and rank 0 holds its own row to the CPU oracle.
 Inputs (source cloud, voxel map) are resident in HBM before the timed region.  value = N * 1e6 * K / elapsed.  Weak scaling.
 
-Output: the LAST stdout line is ONE compact JSON object (< 4 KB, numbers and short names only: compact_result()).  Everything else -- the notes, BASELINE configs[0], [2],
-[3], [4], the LM loops, the map build, the 8 M-point source -- goes to bench_detail.json next to this file (bench_detail.py holds those legs); the line carries one
-number per leg under `legs`.  The optional legs run while --budget-seconds lasts (default 45 s of wall for the whole run; --detail = no limit).
+Output: the LAST stdout line is ONE compact JSON object (< 4 KB, numbers and short names only: compact_result()).  With --full, everything else -- the notes,
+BASELINE configs[0], [2], [3], [4], the LM loops, the map build, the 8 M-point source -- goes to bench_detail.json next to this file (bench_detail.py holds those legs);
+the line carries one number per leg under `legs`.  The optional legs run while --budget-seconds lasts (default 45 s of wall for the whole run; --detail = no limit).
 
   roofline     -- dominant kernel (vgicp_stream_kernel): algorithmic bytes (48 N_src + 16 N_buckets + 52 N_voxels + 560) / its mean duration.
                   frac / kernel_ms: the WHOLE fused kernel as the K timed steps ran it, by its own 100 MHz stamps; frac_streaming: its streaming slice;
@@ -125,6 +133,7 @@ def compact_result(full):
     out["legs"] = legs
     out["legs_skipped"] = full.get("legs_skipped") or []
     out["run_seconds"] = full.get("run_seconds")
+    out["full"] = full.get("full")
     out["detail_file"] = full.get("detail_file", DETAIL_FILE)
 
     def short(x):  # (names, not notes: whatever a leg wrote into a string field, the line keeps its first 96 characters)
@@ -143,6 +152,21 @@ def compact_line(full):
     if len(line.encode()) >= MAX_LINE_BYTES or "\n" in line:
         raise RuntimeError(f"bench.py: the result line is {len(line.encode())} bytes (limit {MAX_LINE_BYTES})")
     return line
+
+
+OUTPUT_FIELDS = ["H_target", "H_source", "H_target_source", "b_target", "b_source", "error", "num_inliers"]
+
+
+def dump_outputs(directory, records):
+    """--dump-outputs: the [R x 122] f64 records of the last timed step, decoded per field as a caller receives them (LinearizedSystem6), stacked over the R ranks,
+    written as <directory>/<field>.npy in float64"""
+    from gtsam_points_amd import _capi
+    from gtsam_points_amd.factors import LinearizedSystem6
+
+    systems = [LinearizedSystem6.from_doubles(r) for r in np.asarray(records, dtype=np.float64).reshape(-1, _capi.LINEARIZED6_DOUBLES)]
+    os.makedirs(directory, exist_ok=True)
+    for name in OUTPUT_FIELDS:
+        np.save(os.path.join(directory, name + ".npy"), np.stack([np.asarray(getattr(s, name), dtype=np.float64) for s in systems]))
 
 
 def _effective_kernel(lib, batch):
@@ -249,7 +273,10 @@ def main():
     ap.add_argument("--target-points", type=int, default=2_000_000)
     ap.add_argument("--resolution", type=float, default=0.5)
     ap.add_argument("--budget-seconds", type=float, default=45.0, help="wall-clock budget of the whole run: an optional leg starts only while its estimate still fits")
-    ap.add_argument("--detail", action="store_true", help="run every optional leg whatever it costs (no budget; the LM legs with the full CPU loop and all three solvers)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: cold protocol, roofline loops and rocprofv3 passes, CPU baseline and parity, optional legs, "
+                                                           "N > 1 exchange forms and their verification, bench_detail.json (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the records of the last timed step as DIR/<name>.npy (float64)")
+    ap.add_argument("--detail", action="store_true", help="run every optional leg whatever it costs (implies --full; no budget; the LM legs with the full CPU loop and all three solvers)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=4.0, help="CPU baseline: seconds of repeated linearize() passes (bounded sample)")
     ap.add_argument("--kernel-iters", type=int, default=50)
@@ -279,7 +306,7 @@ def main():
     ap.add_argument("--detail-file", default=os.path.join(ROOT, DETAIL_FILE))
     args = ap.parse_args()
     if args.detail:
-        args.budget_seconds, args.lm_full_cpu = 1e9, True
+        args.budget_seconds, args.lm_full_cpu, args.full = 1e9, True, True
 
     import torch
     import torch.distributed as dist
@@ -479,7 +506,7 @@ def main():
 
     # ms_per_step_cold: the same W + K protocol with NOTHING in front -- the device as seconds of host-side set-up left it (rounds 1-3's protocol)
     cold = None
-    if not args.no_cold:
+    if args.full and not args.no_cold:
         el_c, n_c, su_c, ku_c = timed_steps("timed steps (cold)")
         cold = dict(ms_per_step=round(el_c / args.steps * 1e3, 5), stream_us=round(su_c.value, 3) if n_c.value >= args.steps else None,
                     fused_kernel_us=round(ku_c.value, 3) if n_c.value >= args.steps else None)
@@ -487,6 +514,7 @@ def main():
     elapsed, dev_steps, dev_stream_us, dev_kernel_us = timed_steps("timed steps")
     ms_per_step = elapsed / args.steps * 1e3
     value = world * args.source_points * args.steps / elapsed
+    last_records = out_np.copy()  # what the last timed step delivered: one record per rank (--dump-outputs)
 
     # ---- N > 1: the other exchange forms in the same job, and the bit-for-bit check of every form's exchanged stack ----
     exchange_ms, exchange_verified, verify_detail, exchange_notes = None, None, None, None
@@ -501,9 +529,11 @@ def main():
             roofline=dict(bound="hbm", kernel="vgicp_stream_kernel", peak=HBM_PEAK_GBS, unit="GB/s"), cpu_baseline=None, parity_vs_oracle=None, backend=dist.get_backend(), rccl_world=dist.get_world_size(),
             exchange_ms={args.exchange: round(ms_per_step, 5)}, legs_skipped=["everything behind the headline"], run_seconds=round(time.time() - t_run, 1))))
     if dist_on:
+        exchange_ms = {args.exchange: round(ms_per_step, 5)}
+    if dist_on and args.full:
         from gtsam_points_amd.distributed import verify_exchanged_stack
 
-        exchange_ms, exchange_notes = {args.exchange: round(ms_per_step, 5)}, {}
+        exchange_notes = {}
         forms = [args.exchange] if args.no_exchange_forms else [args.exchange] + [f for f in ("all_reduce", "all_gather", "peer") if f != args.exchange]
         def all_agree(ok):  # (one tiny collective: every rank takes the same branch behind a failure)
             flag = torch.tensor([1 if ok else 0], dtype=torch.int32, device=device)
@@ -559,36 +589,39 @@ def main():
     # ---- dominant-kernel roofline ----
     # (1) as the timed steps ran it: the fused kernel stamps its own start / last row in / sums out on the device's 100 MHz clock (gp_vgicp_batch_device_times)
     # (2) back to back: HIP events on the launch stream over a loop of stream-kernel launches (two-kernel form: the streaming part alone)
+    # (2) runs launches of its own: --full only
     ms_total, ms_main, ms_fin = C.c_float(), C.c_float(), C.c_float()
-    _capi.check(lib.gp_vgicp_batch_time_linearize(batch, pose.ctypes.data, args.kernel_iters, C.byref(ms_total), C.byref(ms_main), C.byref(ms_fin)), "time_linearize")
+    if args.full:
+        _capi.check(lib.gp_vgicp_batch_time_linearize(batch, pose.ctypes.data, args.kernel_iters, C.byref(ms_total), C.byref(ms_main), C.byref(ms_fin)), "time_linearize")
     alg_bytes = int(lib.gp_vgicp_batch_algorithmic_bytes(batch))
     actual_bytes = int(lib.gp_vgicp_batch_actual_bytes(batch))
     mirrored = C.c_int(-1)
     lib.gp_vgicp_batch_get_tuning(batch, _capi.GP_TUNE_EFFECTIVE_MIRROR, C.byref(mirrored))
     in_step = dev_steps.value >= args.steps and dev_stream_us.value > 0 and dev_kernel_us.value > 0
     streaming_ms = dev_stream_us.value * 1e-3 if in_step else ms_main.value
-    kernel_ms = dev_kernel_us.value * 1e-3 if in_step else ms_main.value
+    kernel_ms = dev_kernel_us.value * 1e-3 if in_step else (ms_main.value or None)  # (None: a plain run without the kernel's own stamps)
 
     def _frac(ms):
         return round(alg_bytes / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if ms else None
 
-    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9
+    achieved = alg_bytes / (kernel_ms * 1e-3) / 1e9 if kernel_ms else None
     roofline = dict(
-        bound="hbm", kernel=KERNEL_NAMES.get(_effective_kernel(lib, batch), "?"), achieved=round(achieved, 2), peak=HBM_PEAK_GBS, unit="GB/s", frac=round(achieved / HBM_PEAK_GBS, 5),
+        bound="hbm", kernel=KERNEL_NAMES.get(_effective_kernel(lib, batch), "?"), achieved=round(achieved, 2) if achieved else None, peak=HBM_PEAK_GBS, unit="GB/s", frac=_frac(kernel_ms),
         frac_note=("frac = algorithmic bytes / the WHOLE fused kernel as the timed steps ran it (first workgroup started .. last part's sums handed to the host; the kernel's own "
                    "100 MHz stamps, mean over the K steps); frac_streaming = its streaming slice; frac_rocprof = algorithmic bytes / rocprofv3's average duration of the kernel")
-        if in_step else "no fused steps in this configuration: frac is the stream kernel back to back under HIP events",
+        if in_step else "no fused steps in this configuration: frac is the stream kernel back to back under HIP events (--full)",
         frac_streaming=_frac(streaming_ms) if in_step else None, streaming_ms=round(streaming_ms, 5) if in_step else None,
         frac_rocprof=None, rocprof_avg_ms=None, rocprof_calls=None, traffic=None, traffic_source=None,
         algorithmic_bytes=alg_bytes,
         algorithmic_bytes_note="SURVEY.md 8(d), reference-layout accounting (48 B per source point + the reference's bucket table and voxel arrays): internal repacking does not change it",
         source_stream=("packed private mirror: 36 B per point (12 B point + the 6 floats of the symmetric covariance)" if mirrored.value == 1 else "the caller's arrays: 12 + 36 B per point"),
-        actual_bytes=actual_bytes, frac_actual=round(actual_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5),
-        kernel_ms=round(kernel_ms, 5),
+        actual_bytes=actual_bytes, frac_actual=round(actual_bytes / (kernel_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 5) if kernel_ms else None,
+        kernel_ms=round(kernel_ms, 5) if kernel_ms else None,
         kernel_ms_source=(f"measured in THIS run inside the {args.steps} timed steps: the whole fused kernel on the device's 100 MHz constant clock, stamped by the kernel itself "
                           "(gp_vgicp_batch_device_times); mean over the steps") if in_step else "measured in THIS run: HIP events over back-to-back stream-kernel launches on the launch stream",
-        kernel_ms_back_to_back=round(ms_main.value, 5), frac_back_to_back=_frac(ms_main.value),
-        step_finalize=args.finalize if not dist_on else "device-resident records (two kernels)", finalize_kernel_ms=round(ms_fin.value, 5), device_pass_ms=round(ms_total.value, 5), cold=cold)
+        kernel_ms_back_to_back=round(ms_main.value, 5) if args.full else None, frac_back_to_back=_frac(ms_main.value),
+        step_finalize=args.finalize if not dist_on else "device-resident records (two kernels)", finalize_kernel_ms=round(ms_fin.value, 5) if args.full else None,
+        device_pass_ms=round(ms_total.value, 5) if args.full else None, cold=cold)
 
     rec = gpa.LinearizedSystem6.from_doubles(host_out[rank].numpy().copy())
 
@@ -607,7 +640,7 @@ def main():
 
     # ---- rank 0: parity of its own row against the checker, and (N = 1) the CPU baseline ----
     cpu_baseline, parity = None, None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         import oracle  # checker / baseline only -- never on the product path
         from oracle import refcapi
 
@@ -643,7 +676,7 @@ def main():
         del fo, om
 
     # ---- optional legs, most valuable first, while the budget lasts ----
-    single = rank == 0 and world == 1 and not dist_on
+    single = rank == 0 and world == 1 and not dist_on and args.full
     traffic_detail = rocprof_detail = None
     if single and not args.no_rocprof and want("rocprof", 5.0):
         rocprof_detail = measure_rocprof(args)
@@ -666,7 +699,7 @@ def main():
             big_source = bench_detail.run_big_source(args, lib, gpa, _capi, synthetic, torch, device, stream)
         except Exception as exc:  # (memory on a shared box)
             big_source = dict(error=f"{type(exc).__name__}: {exc}")
-    if not args.no_c4 and want("c4", 14.0):
+    if args.full and not args.no_c4 and want("c4", 14.0):
         c4 = bench_detail.run_c4(args, lib, gpa, _capi, synthetic, torch, dist, rank, world, device, stream, dist_on)
 
     result = None
@@ -690,8 +723,8 @@ def main():
             roofline=roofline, cpu_baseline=cpu_baseline, parity_vs_oracle=parity,
             backend=(dist.get_backend() if dist_on else None), rccl_world=(dist.get_world_size() if dist_on else None),
             exchange_ms=exchange_ms, exchange_verified=exchange_verified, exchange_verify_detail=verify_detail, exchange_notes=exchange_notes,
-            c4=c4, configs=configs, big_source=big_source, legs_skipped=skipped, budget_seconds=args.budget_seconds,
-            setup=dict(generate_s=round(t_gen, 2), voxelmap_build_s=round(t_map, 4)), detail_file=os.path.basename(args.detail_file))
+            c4=c4, configs=configs, big_source=big_source, legs_skipped=skipped, budget_seconds=args.budget_seconds, full=args.full,
+            setup=dict(generate_s=round(t_gen, 2), voxelmap_build_s=round(t_map, 4)), detail_file=os.path.basename(args.detail_file) if args.full else None)
     lib.gp_vgicp_batch_destroy(batch)
     if dist_on:
         with PhaseGuard(args.phase_seconds, "process group teardown"):
@@ -714,12 +747,15 @@ def main():
                 result["c4"]["inlib"] = dict(error="the in-library multi-device leg did not finish within 240 s and was stopped")
             except Exception as exc:
                 result["c4"]["inlib"] = dict(error=f"{type(exc).__name__}: {exc}")
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_records)
         result["run_seconds"] = round(time.time() - t_run, 1)
-        try:
-            with open(args.detail_file, "w") as f:
-                json.dump(_clean(result), f, indent=1, allow_nan=False)
-        except OSError as exc:  # (a read-only tree: the line still goes out)
-            sys.stderr.write(f"bench.py: could not write {args.detail_file}: {exc}\n")
+        if args.full:
+            try:
+                with open(args.detail_file, "w") as f:
+                    json.dump(_clean(result), f, indent=1, allow_nan=False)
+            except OSError as exc:  # (a read-only tree: the line still goes out)
+                sys.stderr.write(f"bench.py: could not write {args.detail_file}: {exc}\n")
         # the record is the LAST stdout line: whatever a C library still holds in its stdio buffer (RCCL prints a version banner through printf, which would otherwise be
         # flushed at process exit, BEHIND this line) goes out first
         try:

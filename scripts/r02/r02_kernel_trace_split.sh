@@ -5,7 +5,7 @@ set -u
 export TMPDIR=/tmp
 O=$GRAFT_REPO_ROOT/gpurun_out; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-c4 --kernel-iters 100 > /tmp/kt.log 2>&1
+rm -rf /tmp/kt && timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/kt -o kt -- python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-c4 --kernel-iters 100 > /tmp/kt.log 2>&1
 f=$(find /tmp/kt -name "*kernel_trace.csv" | head -1)
 python - "$f" <<'PY' | tee $O/r02_kernel_trace_split.txt
 import csv, sys

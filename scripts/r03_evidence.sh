@@ -8,22 +8,22 @@ cd $GRAFT_REPO_ROOT
 rocminfo 2>/dev/null | grep -E "Marketing Name|gfx" | head -4 > $O/device.txt; nproc >> $O/device.txt
 # 1. per-kernel times of the bench command (driver's form: --steps 20 --warmup 5; the step runs the fused finalize), with the per-dispatch trace for the
 #    launch-pattern split; the same with --finalize two-kernel (the tile kernel alone inside a step)
-rm -rf /tmp/prof && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-c4 --no-configs > $O/rocprof_bench.log 2>&1
+rm -rf /tmp/prof && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-c4 --no-configs > $O/rocprof_bench.log 2>&1
 f=$(find /tmp/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv && head -5 $f | cut -c1-200
 tf=$(find /tmp/prof -name "*kernel_trace.csv" | head -1)
-rm -rf /tmp/prof2 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o bench -- python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-c4 --no-configs --finalize two-kernel > $O/rocprof_bench_two_kernel.log 2>&1
+rm -rf /tmp/prof2 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o bench -- python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-c4 --no-configs --finalize two-kernel > $O/rocprof_bench_two_kernel.log 2>&1
 f=$(find /tmp/prof2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats_two_kernel.csv && head -5 $f | cut -c1-200
 t=$(find /tmp/prof2 -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python scripts/kernel_trace_split.py "$t" $O/kernel_trace_split.json "$tf" | tee $O/kernel_trace_split.txt
 # 2. HBM traffic of the tile kernel: FETCH_SIZE / WRITE_SIZE in separate passes, read side calibrated on a known stream
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$ctr
-  GP_BENCH_CALIBRATE=1 timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_$ctr -o pmc -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-c4 --no-configs --kernel-iters 5 > $O/pmc_$ctr.log 2>&1
+  GP_BENCH_CALIBRATE=1 timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_$ctr -o pmc -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-c4 --no-configs --kernel-iters 5 > $O/pmc_$ctr.log 2>&1
 done
 ff=$(find /tmp/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1); fw=$(find /tmp/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 [ -n "$ff" ] && [ -n "$fw" ] && python scripts/pmc_summary.py "$ff" "$fw" 1000000 $O/hbm_traffic.json > $O/pmc_summary.txt; tail -1 $O/pmc_summary.txt | cut -c1-300
 # 3. SQ counters of the tile kernel
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
-  rm -rf /tmp/pc && timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pc -o p -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-c4 --no-configs --kernel-iters 5 > /tmp/pc.log 2>&1
+  rm -rf /tmp/pc && timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pc -o p -- python bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-c4 --no-configs --kernel-iters 5 > /tmp/pc.log 2>&1
   f=$(find /tmp/pc -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python - "$f" >> $O/pmc_tile_sq.txt <<'PY'
 import csv, sys
@@ -63,7 +63,7 @@ for wl in c4 c3; do
   f=$(find /tmp/pb -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && grep -E "vgicp_stream_kernel|finalize" $f | cut -c1-60,170-260 | tee -a $O/sync_kernels_$wl.txt
 done
 # 5. the whole default bench (driver's clock) and the GPU test-suite, smoke
-timeout 900 python bench.py > $O/bench.log 2>&1; grep "^{" $O/bench.log > $O/bench_n1.json; cut -c1-400 $O/bench_n1.json
+timeout 900 python bench.py --full > $O/bench.log 2>&1; grep "^{" $O/bench.log > $O/bench_n1.json; cut -c1-400 $O/bench_n1.json
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke exit $?" >> $O/smoke.txt; tail -2 $O/smoke.txt
 timeout 1800 python -m pytest -m gpu -q > $O/pytest_gpu.txt 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.txt; tail -3 $O/pytest_gpu.txt
 ls -la $O

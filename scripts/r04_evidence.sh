@@ -9,27 +9,27 @@ rocminfo 2>/dev/null | grep -E "Marketing Name|gfx" | head -4 > $O/device.txt; n
 B="--no-cpu-baseline --no-c4 --no-configs"
 # 1. per-kernel times of the bench command (driver's form: --steps 20 --warmup 5; the step runs the fused finalize on the packed mirror), with the per-dispatch trace for the
 #    launch-pattern split; the same with --finalize two-kernel (the tile kernel alone inside a step) and with --no-mirror (the caller's 48 B per point)
-rm -rf /tmp/prof && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python bench.py --steps 20 --warmup 5 $B > $O/rocprof_bench.log 2>&1
+rm -rf /tmp/prof && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof -o bench -- python bench.py --full --steps 20 --warmup 5 $B > $O/rocprof_bench.log 2>&1
 f=$(find /tmp/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats.csv && head -4 $f | cut -c1-200
 tf=$(find /tmp/prof -name "*kernel_trace.csv" | head -1)
-rm -rf /tmp/prof2 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o bench -- python bench.py --steps 20 --warmup 5 $B --finalize two-kernel > $O/rocprof_bench_two_kernel.log 2>&1
+rm -rf /tmp/prof2 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof2 -o bench -- python bench.py --full --steps 20 --warmup 5 $B --finalize two-kernel > $O/rocprof_bench_two_kernel.log 2>&1
 f=$(find /tmp/prof2 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats_two_kernel.csv && head -3 $f | cut -c1-200
 t=$(find /tmp/prof2 -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python scripts/kernel_trace_split.py "$t" $O/kernel_trace_split.json "$tf" | tee $O/kernel_trace_split.txt
-rm -rf /tmp/prof3 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof3 -o bench -- python bench.py --steps 20 --warmup 5 $B --no-mirror > $O/rocprof_bench_no_mirror.log 2>&1
+rm -rf /tmp/prof3 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof3 -o bench -- python bench.py --full --steps 20 --warmup 5 $B --no-mirror > $O/rocprof_bench_no_mirror.log 2>&1
 f=$(find /tmp/prof3 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats_no_mirror.csv && head -3 $f | cut -c1-200
 # (the mix of round 3's file: 25 fused steps + the back-to-back launches, without the untimed device wake-up's ~10^4 fused steps)
-rm -rf /tmp/prof4 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof4 -o bench -- python bench.py --steps 20 --warmup 5 $B --device-warmup-ms 0 > $O/rocprof_bench_no_warmup.log 2>&1
+rm -rf /tmp/prof4 && timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof4 -o bench -- python bench.py --full --steps 20 --warmup 5 $B --device-warmup-ms 0 > $O/rocprof_bench_no_warmup.log 2>&1
 f=$(find /tmp/prof4 -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/bench_kernel_stats_no_warmup.csv && head -3 $f | cut -c1-200
 # 2. HBM traffic of the tile kernel: FETCH_SIZE / WRITE_SIZE in separate passes, read side calibrated on a known stream (48 B per point, the API layout's pattern)
 for ctr in FETCH_SIZE WRITE_SIZE; do
   rm -rf /tmp/pmc_$ctr
-  GP_BENCH_CALIBRATE=1 timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_$ctr -o pmc -- python bench.py --steps 5 --warmup 2 $B --kernel-iters 5 --device-warmup-ms 0 > $O/pmc_$ctr.log 2>&1
+  GP_BENCH_CALIBRATE=1 timeout 600 rocprofv3 --pmc $ctr --kernel-trace --output-format csv -d /tmp/pmc_$ctr -o pmc -- python bench.py --full --steps 5 --warmup 2 $B --kernel-iters 5 --device-warmup-ms 0 > $O/pmc_$ctr.log 2>&1
 done
 ff=$(find /tmp/pmc_FETCH_SIZE -name "*counter_collection.csv" | head -1); fw=$(find /tmp/pmc_WRITE_SIZE -name "*counter_collection.csv" | head -1)
 [ -n "$ff" ] && [ -n "$fw" ] && python scripts/pmc_summary.py "$ff" "$fw" 1000000 $O/hbm_traffic.json > $O/pmc_summary.txt; tail -1 $O/pmc_summary.txt | cut -c1-300
 # 3. SQ / TCC counters of the tile kernel
 for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD" "TCP_TOTAL_CACHE_ACCESSES_sum TCP_TCC_READ_REQ_sum TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum"; do
-  rm -rf /tmp/pc && timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pc -o p -- python bench.py --steps 5 --warmup 2 $B --kernel-iters 5 --device-warmup-ms 0 > /tmp/pc.log 2>&1
+  rm -rf /tmp/pc && timeout 300 rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pc -o p -- python bench.py --full --steps 5 --warmup 2 $B --kernel-iters 5 --device-warmup-ms 0 > /tmp/pc.log 2>&1
   f=$(find /tmp/pc -name "*counter_collection.csv" | head -1)
   [ -n "$f" ] && python - "$f" >> $O/pmc_tile_sq.txt <<'PY'
 import csv, sys
@@ -59,7 +59,7 @@ t=$(find /tmp/pm -name "*kernel_trace.csv" | head -1); [ -n "$t" ] && python scr
 timeout 60 ./scripts/probe/sort_probe > $O/sort_probe.txt 2>&1; timeout 60 ./scripts/probe/bins_probe > $O/bins_probe.txt 2>&1; tail -2 $O/sort_probe.txt | cut -c1-200
 timeout 100 python scripts/r04_map_build.py 2>/dev/null | grep "^{" > $O/map_build.json; cat $O/map_build.json
 # 6. the whole default bench (driver's clock), smoke and the GPU test-suite
-timeout 900 python bench.py > $O/bench.log 2>&1; grep "^{" $O/bench.log > $O/bench_n1.json; cut -c1-300 $O/bench_n1.json
+timeout 900 python bench.py --full > $O/bench.log 2>&1; grep "^{" $O/bench.log > $O/bench_n1.json; cut -c1-300 $O/bench_n1.json
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke exit $?" >> $O/smoke.txt; tail -2 $O/smoke.txt
 timeout 1800 python -m pytest -m gpu -q > $O/pytest_gpu.txt 2>&1; echo "pytest exit $?" >> $O/pytest_gpu.txt; tail -3 $O/pytest_gpu.txt
 ls -la $O

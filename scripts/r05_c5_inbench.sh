@@ -7,7 +7,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r05j; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 timeout 900 python -m pytest tests/test_solver_gpu.py tests/test_lm_gpu.py tests/test_knn_gicp_gpu.py -x -q -m gpu > $O/pytest_part.txt 2>&1; echo "pytest rc $?" >> $O/pytest_part.txt
 T="--steps 5 --warmup 2 --no-cold --no-big-source --no-traffic"
-timeout 400 python bench.py $T > $O/bench_c4_lm.log 2>&1
+timeout 400 python bench.py --full $T > $O/bench_c4_lm.log 2>&1
 python - <<'PY' | tee $O/after.txt
 import json
 for l in open("gpurun_out/r05j/bench_c4_lm.log"):
@@ -19,6 +19,6 @@ for l in open("gpurun_out/r05j/bench_c4_lm.log"):
             o = b["configs"][k]
             print(k, {n: (o[n]["ms_per_iteration"], o[n]["ms_per_iteration_by_phase"]) for n in ("gpu_device_solve", "gpu_device_solve_three_calls", "gpu_host_solve") if n in o}, o.get("error"))
 PY
-rm -rf /tmp/pi; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/pi -o b -- python bench.py $T --no-lm > $O/rocprof_c4.log 2>&1
+rm -rf /tmp/pi; timeout 600 rocprofv3 --kernel-trace --output-format csv -d /tmp/pi -o b -- python bench.py --full $T --no-lm > $O/rocprof_c4.log 2>&1
 python scripts/r05_trace_tail.py /tmp/pi $O/with_c4_probe 30
 tail -5 $O/pytest_part.txt

@@ -6,9 +6,9 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 O=$GRAFT_REPO_ROOT/gpurun_out/r05x; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 F="--steps 200 --warmup 20 --no-configs --no-c4 --no-traffic --no-big-source --cpu-seconds 1"
-timeout 300 python bench.py $F > $O/plain.log 2>&1
+timeout 300 python bench.py --full $F > $O/plain.log 2>&1
 for ex in peer all_gather all_reduce; do
-  GP_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29700 + RANDOM % 200)) timeout 300 python bench.py $F --exchange $ex > $O/$ex.log 2>&1
+  GP_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=$((29700 + RANDOM % 200)) timeout 300 python bench.py --full $F --exchange $ex > $O/$ex.log 2>&1
 done
 python - <<'PY' | tee $O/summary.txt
 import json

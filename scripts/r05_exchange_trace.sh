@@ -4,7 +4,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 O=$GRAFT_REPO_ROOT/gpurun_out/r05x; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 F="--steps 50 --warmup 5 --no-configs --no-c4 --no-traffic --no-big-source --no-cpu-baseline --no-cold --device-warmup-ms 20"
-rm -rf /tmp/px; GP_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29791 timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/px -o t -- python bench.py $F --exchange peer > $O/trace.log 2>&1
+rm -rf /tmp/px; GP_BENCH_FORCE_DIST=1 RANK=0 LOCAL_RANK=0 WORLD_SIZE=1 MASTER_ADDR=127.0.0.1 MASTER_PORT=29791 timeout 300 rocprofv3 --kernel-trace --output-format csv -d /tmp/px -o t -- python bench.py --full $F --exchange peer > $O/trace.log 2>&1
 python - <<'PY' | tee $O/trace_summary.txt
 import csv, glob
 f = sorted(glob.glob("/tmp/px/**/*kernel_trace.csv", recursive=True))[-1]

@@ -6,7 +6,7 @@ export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0 GP_BENCH_BACKEND=gloo
 O=gpurun_out/r05_rehearsal; mkdir -p $O
 for N in ${1:-2 4 8}; do
   P=$((29600 + N))
-  ( time timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $P bench.py --gpus $N --steps 20 --warmup 5 ) > $O/n$N.log 2> $O/n$N.err
+  ( time timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $P bench.py --full --gpus $N --steps 20 --warmup 5 ) > $O/n$N.log 2> $O/n$N.err
   echo "exit $?" >> $O/n$N.log
   python - $O/n$N.log $N <<'PY'
 import json, sys

@@ -2,7 +2,7 @@ set -u
 export TMPDIR=/tmp HSA_ENABLE_IPC_MODE_LEGACY=0
 O=$GRAFT_REPO_ROOT/gpurun_out/r05; mkdir -p $O
 cd $GRAFT_REPO_ROOT
-for i in 1 2 3; do ( time timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 ) > $O/bench_run$i.log 2>&1; grep "^{" $O/bench_run$i.log > $O/bench_run$i.json; done
+for i in 1 2 3; do ( time timeout 900 python bench.py --full --gpus 1 --steps 20 --warmup 5 ) > $O/bench_run$i.log 2>&1; grep "^{" $O/bench_run$i.log > $O/bench_run$i.json; done
 cp $O/bench_run1.json $O/bench_n1.json; grep -h "^real" $O/bench_run*.log
 python - <<'PY'
 import json

@@ -6,7 +6,7 @@ O=$GRAFT_REPO_ROOT/gpurun_out/r05w; mkdir -p $O
 cd $GRAFT_REPO_ROOT
 F="--gpus 1 --steps 20 --warmup 5 --no-configs --no-c4 --no-traffic --no-big-source --no-cpu-baseline"
 for rep in 1 2 3 4; do for ms in 300 0 30 100; do
-  timeout 120 python bench.py $F --device-warmup-ms $ms 2>/dev/null | grep '^{' | python -c "
+  timeout 120 python bench.py --full $F --device-warmup-ms $ms 2>/dev/null | grep '^{' | python -c "
 import json,sys
 b=json.loads(sys.stdin.read()); r=b['roofline']
 print(json.dumps(dict(wakeup_ms=$ms, rep=$rep, ms_per_step=b['ms_per_step'], kernel_us=round(r['kernel_ms']*1e3,2), cold_ms_per_step=b['ms_per_step_cold'], cold_kernel_us=(r.get('cold') or {}).get('fused_kernel_us'))))" >> $O/sweep.jsonl

@@ -7,7 +7,7 @@ O=gpurun_out/r06; mkdir -p $O
 rocminfo 2>/dev/null | grep -E "Marketing Name|gfx" | head -4 > $O/device.txt; nproc >> $O/device.txt
 for i in ${RUNS:-1 2}; do
   S=$(date +%s.%N)
-  timeout 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_run$i.out 2> $O/bench_run$i.err; rc=$?
+  timeout 600 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/bench_run$i.out 2> $O/bench_run$i.err; rc=$?
   E=$(date +%s.%N)
   tail -n 1 $O/bench_run$i.out > $O/bench_run$i.json
   cp bench_detail.json $O/bench_detail_run$i.json 2>/dev/null
@@ -22,7 +22,7 @@ PY
 done
 if [ -z "${NO_REHEARSAL:-}" ]; then
   for N in ${REHEARSE:-2}; do
-    ( time GP_BENCH_BACKEND=gloo timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --gpus $N --steps 20 --warmup 5 ) > $O/rehearsal_n$N.out 2> $O/rehearsal_n$N.err
+    ( time GP_BENCH_BACKEND=gloo timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $N --master-addr 127.0.0.1 --master-port $((29600 + N)) bench.py --full --gpus $N --steps 20 --warmup 5 ) > $O/rehearsal_n$N.out 2> $O/rehearsal_n$N.err
     echo "exit $?"; tail -n 1 $O/rehearsal_n$N.out | cut -c1-1500; cp bench_detail.json $O/bench_detail_rehearsal_n$N.json 2>/dev/null
   done
   timeout 900 python3 -m pytest tests/test_multi_gpu.py tests/test_peer_exchange_gpu.py -q -m gpu -x 2>&1 | tail -5

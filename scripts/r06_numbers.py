@@ -121,7 +121,7 @@ def results():
     fb = jf("r06_bench_detail_full_budget.json") if os.path.exists(os.path.join(ROOT, "profiles", "r06_bench_detail_full_budget.json")) else None
     if fb and fb.get("c4"):
         c4 = fb["c4"]
-        out.append(f"| C4: {c4['factors']} factors over 512 submaps of 32,768 pts, 1.0 m, ONE batched call on ONE GPU (the leg the 45 s default budget skips: `bench.py --budget-seconds 120`, `profiles/r06_bench_full_budget.json`, whole run {fb.get('run_seconds', 0):.0f} s) | "
+        out.append(f"| C4: {c4['factors']} factors over 512 submaps of 32,768 pts, 1.0 m, ONE batched call on ONE GPU (the leg the 45 s default budget skips: `bench.py --full --budget-seconds 120`, `profiles/r06_bench_full_budget.json`, whole run {fb.get('run_seconds', 0):.0f} s) | "
                    f"{c4['points_per_linearize'] / 1e6:.1f} M | {c4['ms_per_linearize']:.4f} | {c4['value']:.3g} corr/s | tile kernel {c4['tile_kernel_ms_slowest_rank'] * 1e3:.0f} µs; {c4['algorithmic_frac_per_gpu']:.2f} algorithmic (every source cloud serves 8 factors: not an HBM fraction) | = the C3 kernel | — |")
     reh = jl("r06_bench_rehearsal_n2.json")
     if reh:

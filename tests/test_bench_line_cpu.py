@@ -6,6 +6,7 @@ import json
 import os
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -88,6 +89,23 @@ def test_compact_line_of_a_bare_result_still_carries_every_key():
     for key in bench.REQUIRED_KEYS:
         assert key in b, key
     assert b["cpu_baseline"] is None and b["parity_max"] is None and b["legs"] == {} and set(bench.REQUIRED_ROOFLINE) <= set(b["roofline"])
+
+
+def test_dump_outputs_writes_each_field_of_every_record_in_float64(tmp_path):
+    """--dump-outputs: the [R x 122] records decoded as the caller's LinearizedSystem6, one float64 .npy per field, stacked over the R ranks"""
+    from gtsam_points_amd import _capi
+    from gtsam_points_amd.factors import LinearizedSystem6
+
+    records = np.random.default_rng(5).standard_normal((2, _capi.LINEARIZED6_DOUBLES))
+    records[:, 0] = [1234.0, 987.0]  # num_inliers
+    bench.dump_outputs(str(tmp_path / "out"), records)
+    for r, rec in enumerate(records):
+        want = LinearizedSystem6.from_doubles(rec)
+        for name in bench.OUTPUT_FIELDS:
+            got = np.load(tmp_path / "out" / (name + ".npy"))
+            assert got.dtype == np.float64 and got.shape[0] == 2, name
+            assert np.array_equal(got[r], np.asarray(getattr(want, name), dtype=np.float64)), name
+    assert np.load(tmp_path / "out" / "H_target.npy").shape == (2, 6, 6) and np.load(tmp_path / "out" / "num_inliers.npy").tolist() == [1234.0, 987.0]
 
 
 def test_a_line_that_would_not_fit_is_refused():

@@ -161,7 +161,7 @@ def test_bench_step_through_rccl_with_one_rank(gpu):
     import tempfile
 
     detail = os.path.join(tempfile.mkdtemp(prefix="gp_bench_"), "bench_detail.json")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2", "--source-points", "200000", "--target-points", "400000",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2", "--source-points", "200000", "--target-points", "400000",
            "--cpu-seconds", "1", "--c4-steps", "2", "--no-configs", "--kernel-iters", "5", "--budget-seconds", "600", "--detail-file", detail]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]

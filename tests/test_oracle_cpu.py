@@ -9,7 +9,7 @@ import oracle
 from oracle import vgicp_oracle_np as onp
 from helpers import BLOCKS, assert_linearized_close, expmap, lm_optimize, pose_error, rel_err
 
-REF_DATA = "/root/reference/data"
+KITTI00 = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "kitti_00")  # the two full scans of the reference's data/kitti_00
 
 
 def _factor(d, res, threads=1):
@@ -177,11 +177,10 @@ def test_alignment_gate_oracle(kitti07):
         assert ang < 0.015 and trans < 0.15, (k, ang, trans)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_DATA), reason="reference data not mounted (GPU box)")
 def test_oracle_on_full_c1_anchor(golden):
     """full kitti_00 pair, 10,970 voxels @0.5 m, overlap 0.773 at identity"""
-    tgt = np.fromfile(f"{REF_DATA}/kitti_00/000000.bin", dtype=np.float32).reshape(-1, 3)
-    src = np.fromfile(f"{REF_DATA}/kitti_00/000001.bin", dtype=np.float32).reshape(-1, 3)
+    tgt = np.fromfile(os.path.join(KITTI00, "000000.bin"), dtype=np.float32).reshape(-1, 3)
+    src = np.fromfile(os.path.join(KITTI00, "000001.bin"), dtype=np.float32).reshape(-1, 3)
     ct, _ = oracle.estimate_covariances(tgt, 10, 8)
     cs, _ = oracle.estimate_covariances(src, 10, 8)
     sym = lambda c: np.ascontiguousarray(0.5 * (c.astype(np.float32) + c.astype(np.float32).transpose(0, 2, 1)))
