@@ -211,6 +211,7 @@ _SIGNATURES = {
     "gp_debug_side_stream_probe": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
     "gp_debug_inject_sort_fault": (C.c_int, [C.c_int]),
     "gp_debug_sort_fallbacks": (C.c_int, []),
+    "gp_debug_drop_error_words": (C.c_int, [C.c_void_p, C.c_int]),
     "gp_trim_device_cache": (C.c_int, []),
     "gp_vgicp_batch_issue_linearize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "gp_vgicp_batch_issue_compute_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -43,7 +43,7 @@ constexpr int REC_HT = 2, REC_HS = 38, REC_HTS = 74, REC_BT = 110, REC_BS = 116;
 
 // A (n x n, column-major, lower triangle + diagonal) and, for diagonal destinations, b: one 64-thread workgroup per block
 __global__ void __launch_bounds__(64) assemble_kernel(const BlockDest* __restrict__ dests, const Contribution* __restrict__ contribs, const double* __restrict__ records,
-                                                      int n, double* __restrict__ A, double* __restrict__ b) {
+                                                      int n, double* __restrict__ A, double* __restrict__ b, double* __restrict__ diag0) {
   const BlockDest d = dests[blockIdx.x];
   const int t = threadIdx.x;
   if (t < 36) {
@@ -65,6 +65,7 @@ __global__ void __launch_bounds__(64) assemble_kernel(const BlockDest* __restric
       s += v;
     }
     A[(size_t)(6 * d.col + c) * n + 6 * d.row + r] = s;
+    if (d.row == d.col && r == c) diag0[6 * d.row + r] = s;
   } else if (t < 42 && d.row == d.col) {
     // b = sum of g = -b_target / -b_source (HessianFactor(.., -b_t, .., -b_s, ..), integrated_matching_cost_factor.cpp:49)
     const int r = t - 36;
@@ -91,15 +92,17 @@ __global__ void __launch_bounds__(256) sum_errors_kernel(const double* __restric
   if (threadIdx.x == 0) *c_out = part[0];
 }
 
-// buildDampedSystem: diag += lambda (identity damping) or lambda * clamp(diag, min, max) (diagonalDamping), + optional prior
+// buildDampedSystem: diag += lambda (identity damping) or lambda * clamp(diag, min, max) (diagonalDamping), + optional prior; diag0 keeps the damped diagonal (the
+// factorisation overwrites A's, and a pivot is held against it: chol6)
 __global__ void __launch_bounds__(256) damp_kernel(double* __restrict__ A, int n, double lambda, int diagonal, double min_diag, double max_diag,
-                                                   const double* __restrict__ prior_diag) {
+                                                   const double* __restrict__ prior_diag, double* __restrict__ diag0) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const double d = A[(size_t)i * n + i];
   double add = diagonal ? lambda * fmin(fmax(d, min_diag), max_diag) : lambda;
   if (prior_diag) add += prior_diag[i];
   A[(size_t)i * n + i] = d + add;
+  diag0[i] = A[(size_t)i * n + i];
 }
 
 // ---- blocked Cholesky, block size 6 -------------------------------------------------------------------------------
@@ -107,12 +110,16 @@ __global__ void __launch_bounds__(256) damp_kernel(double* __restrict__ A, int n
 // workgroup i - k (block row i > k) factors A_kk once more for itself (6x6: ~100 flops, cheaper than a kernel boundary) and
 // turns A_ik into L_ik = A_ik L_kk^-T in place.  A_kk itself is left untouched, so the redundant factorisations all read the
 // same data; the substitution kernel takes the diagonal blocks from Ldiag.
-__device__ __forceinline__ bool chol6(double (*a)[6]) {  // in place, lower triangle; false when a pivot is not positive
+// A pivot must exceed kPivotTolerance x the damped assembled diagonal entry of its column (scale6), the rule of the sparse kernels (gp_sparse.hip: chol6_wave), so that
+// the dense and the sparse step call the same systems indeterminate (include/gtsam_points_hip.h, GP_ERROR_INDETERMINATE).  Before, the dense step asked for piv > 0 and
+// solved a singular system into a huge step whenever rounding left a pivot of ~1e-16 A_pp positive.
+constexpr double kPivotTolerance = 1e-11;
+__device__ __forceinline__ bool chol6(double (*a)[6], const double* scale6) {  // in place, lower triangle; false when a pivot is not above the tolerance
   bool ok = true;
   for (int j = 0; j < 6; j++) {
     double d = a[j][j];
     for (int p = 0; p < j; p++) d -= a[j][p] * a[j][p];
-    if (!(d > 0.0)) {
+    if (!(d > kPivotTolerance * scale6[j])) {
       ok = false;
       d = 1.0;
     }
@@ -127,14 +134,15 @@ __device__ __forceinline__ bool chol6(double (*a)[6]) {  // in place, lower tria
   return ok;
 }
 
-__global__ void __launch_bounds__(64) chol_panel_kernel(double* __restrict__ A, int n, int k, double* __restrict__ Ldiag, int* __restrict__ status) {
+__global__ void __launch_bounds__(64) chol_panel_kernel(double* __restrict__ A, int n, int k, const double* __restrict__ diag0, double* __restrict__ Ldiag,
+                                                        int* __restrict__ status) {
   __shared__ double l[6][6];
   const int t = threadIdx.x;
   const double* diag = A + (size_t)(6 * k) * n + 6 * k;
   if (t < 36) l[t % 6][t / 6] = diag[(size_t)(t / 6) * n + t % 6];
   __syncthreads();
   if (t == 0) {
-    if (!chol6(l) && blockIdx.x == 0) atomicExch(status, k + 1);  // not positive definite at this pose block
+    if (!chol6(l, diag0 + 6 * k) && blockIdx.x == 0) atomicExch(status, k + 1);  // not positive definite at this pose block
   }
   __syncthreads();
   if (blockIdx.x == 0) {
@@ -263,7 +271,7 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
                                                                  double* __restrict__ b, double* __restrict__ c_out, double* __restrict__ x, double* __restrict__ Ldiag,
                                                                  int* __restrict__ status, double* __restrict__ out_host, const LmPoseView epi, const int has_epi) {
   __shared__ double part[256];
-  __shared__ double l[6][6], a0[6][6], bb[6], xx[6];
+  __shared__ double l[6][6], a0[6][6], bb[6], xx[6], sc[6];
   __shared__ int st;
   const int t = threadIdx.x;
   const BlockDest d = dests[0];
@@ -314,10 +322,13 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
     A[(size_t)(t / 6) * 6 + t % 6] = a0[t % 6][t / 6];  // column-major 6 x 6 (the upper triangle holds what the assembly left: the same sums, mirrored)
     l[t % 6][t / 6] = a0[t % 6][t / 6];
   }
-  if (t < 6) b[t] = bb[t];
+  if (t < 6) {
+    b[t] = bb[t];
+    sc[t] = a0[t][t];  // the damped diagonal (damp_kernel's diag0)
+  }
   __syncthreads();
   if (t == 0) {
-    st = chol6(l) ? 0 : 1;  // chol_panel_kernel: status = k + 1
+    st = chol6(l, sc) ? 0 : 1;  // chol_panel_kernel: status = k + 1
     // chol_solve_kernel, P = 1: L y = b (the sum over earlier columns is empty: y - 0), then L^T x = y
     double v[6];
     for (int r = 0; r < 6; r++) {
@@ -362,7 +373,7 @@ struct gp_dense_system {
   hipStream_t stream = nullptr;
   std::vector<gp::BlockDest> dests;
   std::vector<gp::Contribution> contribs;
-  gp::DeviceArray d_dests, d_contribs, A, b, c, x, status, prior, Ldiag;
+  gp::DeviceArray d_dests, d_contribs, A, b, c, x, status, prior, Ldiag, diag0;  // diag0 [n]: the damped assembled diagonal (the pivots' scale)
   gp::PinnedArray pinned;  // gp_dense_system_step: x [n] | b [n] | c | status, written by the step's last kernel
   bool built = false;
   bool step_in_flight = false;  // gp_dense_system_issue_step went out, gp_dense_system_finish_step has not collected it
@@ -411,7 +422,8 @@ int gp_dense_system_create(int num_slots, const int* factor_slots, int num_facto
   int rc = GP_OK;
   if ((rc = s->d_dests.alloc(sizeof(gp::BlockDest) * s->dests.size())) || (rc = s->d_contribs.alloc(sizeof(gp::Contribution) * std::max<size_t>(s->contribs.size(), 1))) ||
       (rc = s->A.alloc(sizeof(double) * n * n)) || (rc = s->b.alloc(sizeof(double) * n)) || (rc = s->x.alloc(sizeof(double) * n)) || (rc = s->c.alloc(sizeof(double))) ||
-      (rc = s->status.alloc(sizeof(int))) || (rc = s->prior.alloc(sizeof(double) * n)) || (rc = s->Ldiag.alloc(sizeof(double) * 36 * (size_t)num_slots))) {
+      (rc = s->status.alloc(sizeof(int))) || (rc = s->prior.alloc(sizeof(double) * n)) || (rc = s->Ldiag.alloc(sizeof(double) * 36 * (size_t)num_slots)) ||
+      (rc = s->diag0.alloc(sizeof(double) * n))) {
     delete s;
     return rc;
   }
@@ -442,7 +454,7 @@ int gp_dense_system_build(gp_dense_system_t* s, const gp_linearized6* records_de
   GP_HIP(hipMemsetAsync(s->A.ptr, 0, sizeof(double) * n * n, s->stream));
   GP_HIP(hipMemsetAsync(s->b.ptr, 0, sizeof(double) * n, s->stream));
   hipLaunchKernelGGL(gp::assemble_kernel, dim3((unsigned)s->dests.size()), dim3(64), 0, s->stream, s->d_dests.as<gp::BlockDest>(), s->d_contribs.as<gp::Contribution>(),
-                     reinterpret_cast<const double*>(records_dev), s->n, s->A.as<double>(), s->b.as<double>());
+                     reinterpret_cast<const double*>(records_dev), s->n, s->A.as<double>(), s->b.as<double>(), s->diag0.as<double>());
   hipLaunchKernelGGL(gp::sum_errors_kernel, dim3(1), dim3(256), 0, s->stream, reinterpret_cast<const double*>(records_dev), s->num_factors, s->c.as<double>());
   const double* prior = nullptr;
   if (prior_diag_host) {
@@ -451,7 +463,7 @@ int gp_dense_system_build(gp_dense_system_t* s, const gp_linearized6* records_de
   }
   if (lambda > 0.0 || prior) {
     hipLaunchKernelGGL(gp::damp_kernel, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, s->A.as<double>(), s->n, lambda, diagonal_damping, min_diagonal, max_diagonal,
-                       prior);
+                       prior, s->diag0.as<double>());
   }
   GP_HIP(hipGetLastError());
   if (prior_diag_host) GP_HIP(hipStreamSynchronize(s->stream));  // the caller's pageable array may go away
@@ -480,7 +492,8 @@ static int launch_dense_solve(gp_dense_system_t* s) {
   GP_HIP(hipMemsetAsync(s->status.ptr, 0, sizeof(int), s->stream));
   for (int k = 0; k < P; k++) {
     const int m = P - k - 1;
-    hipLaunchKernelGGL(gp::chol_panel_kernel, dim3(m + 1), dim3(64), 0, s->stream, A, n, k, s->Ldiag.as<double>(), s->status.as<int>());
+    hipLaunchKernelGGL(gp::chol_panel_kernel, dim3(m + 1), dim3(64), 0, s->stream, A, n, k, (const double*)s->diag0.as<double>(), s->Ldiag.as<double>(),
+                       s->status.as<int>());
     if (m >= 128) {
       const int tiles = (m + 7) / 8;
       hipLaunchKernelGGL(gp::chol_update_kernel<8>, dim3((unsigned)((size_t)tiles * (tiles + 1) / 2)), dim3(256), 0, s->stream, A, n, k, m);
@@ -519,6 +532,8 @@ static int issue_step_impl(gp_dense_system_t* s, const gp_linearized6* records_d
                            const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) {
   if (fused) *fused = false;
   if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: null system");
+  // a step in flight owns the pinned x | b | c | status block and the device buffers until finish_step / collect_step: a second issue is refused, not queued over it
+  if (s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_issue_step: a step is in flight (finish it first)");
   const size_t n = (size_t)s->n;
   GP_TRY(s->pinned.ensure(sizeof(double) * (2 * n + 2)));
   if (s->num_slots == 1 && !prior_diag_host && s->one_launch) {

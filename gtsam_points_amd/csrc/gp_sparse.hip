@@ -2178,6 +2178,9 @@ int gp_sparse_system_solve(gp_sparse_system_t* s, double* x_host, double* x_dev_
 static int issue_step_impl(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
                            const double* prior_diag_host, const gp::LmPoseView* epi) {
   if (!s || (!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_step: bad arguments");
+  // a step in flight owns the pinned x | b | c | status block, prior_staged (the source of its pending H2D copy) and the device buffers until finish_step /
+  // collect_step: a second issue is refused, not queued over it
+  if (s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_issue_step: a step is in flight (finish it first)");
   const gp::SparseSymbolic& S = s->sym;
   const size_t n = (size_t)s->n;
   GP_TRY(s->pinned.ensure(sizeof(double) * (2 * n + 2)));
@@ -2185,7 +2188,7 @@ static int issue_step_impl(gp_sparse_system_t* s, const gp_linearized6* records_
   gp::SparseStepExtras ex{};
   ex.lambda = lambda, ex.min_diag = min_diagonal, ex.max_diag = max_diagonal, ex.diagonal = diagonal_damping;
   if (prior_diag_host) {
-    s->prior_staged.resize(n);  // (outlives the copy: the next issue waits for the step in flight first -- gp_sparse_system_finish_step)
+    s->prior_staged.resize(n);  // (outlives the copy: no second issue is taken while this step is in flight)
     for (int k = 0; k < S.P; k++)
       for (int r = 0; r < 6; r++) s->prior_staged[6 * (size_t)k + r] = prior_diag_host[6 * (size_t)S.perm[k] + r];
     GP_HIP(hipMemcpyAsync(s->prior.ptr, s->prior_staged.data(), sizeof(double) * n, hipMemcpyHostToDevice, s->stream));

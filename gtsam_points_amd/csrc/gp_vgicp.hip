@@ -521,6 +521,9 @@ struct gp_vgicp_batch {
   gp::PinnedArray h_done;  // one completion word per factor, written by the finalize kernel behind its record (synchronous calls poll it)
   void* h_done_dev = nullptr;
   bool dev_error_fused = false;  // gp_vgicp_batch_issue_compute_error_dev_begin went out in the by-factor fused form
+  const double* dev_error_lin = nullptr;   // ... at these device pose tables: what _end runs the pass again with when the completion words are missing
+  const double* dev_error_eval = nullptr;
+  int drop_error_words = 0;      // test hook (gp_debug_drop_error_words): the next so many fused error evaluations take the "words did not arrive" branch
   unsigned long long seq = 0;
   bool table_dirty = true;
   std::vector<uint64_t> seen;  // per factor: its generation + its target map's generation when the table was built
@@ -1419,6 +1422,12 @@ int gp_vgicp_batch_issue_compute_error(gp_vgicp_batch_t* b, const double* poses_
 
 static int clean_factor_arrivals(gp_vgicp_batch_t* b);
 static bool words_arrived(const gp_vgicp_batch_t* b, int count, unsigned long long seq);
+// gp_debug_drop_error_words: this fused error evaluation is to read as if its completion words had not arrived (host side only: the kernels run as always)
+static bool take_dropped_error_words(gp_vgicp_batch_t* b) {
+  if (b->drop_error_words <= 0) return false;
+  b->drop_error_words--;
+  return true;
+}
 
 // the same two passes with the poses ALREADY in device memory (double[F][16] per table, column-major -- what a device-side retract produces, gp_lm.hip): no staging,
 // no H2D copy, nothing for the host to wait on before the next call.  rigid: the caller vouches that every 3x3 block is orthonormal to 1e-9 (what the host-pose entry
@@ -1495,6 +1504,7 @@ int gp_vgicp_batch_issue_compute_error_dev_begin(gp_vgicp_batch_t* b, const doub
         static_cast<volatile unsigned long long*>(b->h_done.ptr)[i] = done.seq;
       }
     b->dev_error_fused = true;
+    b->dev_error_lin = poses_lin_dev, b->dev_error_eval = poses_eval_dev;
     return GP_OK;
   }
   return launch_error(b, ps, static_cast<double*>(b->h_out_dev), done);
@@ -1506,21 +1516,31 @@ int gp_vgicp_batch_compute_error_dev_end(gp_vgicp_batch_t* b, double* out_host) 
   if (F == 0) return GP_OK;
   GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), F, b->seq, b->stream, spin_budget_us(b) + 400));  // (+ the damped step queued in front of it)
   if (b->dev_error_fused) {
-    if (!words_arrived(b, (int)F, b->seq)) {  // (as gp_vgicp_batch_compute_error: a counter left dirty by a launch that did not run to its end -- the finalize kernel does the sums)
-      double* partials = nullptr;
-      GP_TRY(partials_ptr(b, &partials));
+    const bool dropped = take_dropped_error_words(b);
+    if (dropped || !words_arrived(b, (int)F, b->seq)) {  // (as gp_vgicp_batch_compute_error: a counter left dirty by a launch that did not run to its end)
+      // Unlike the synchronous call, the rows of the pass cannot be summed again here: work queued behind _begin on the batch's stream -- gp_lm.hip's speculative
+      // linearise -- writes the same partials buffer.  So the pass runs again in its two-kernel form (tile kernel + vgicp_finalize_error_kernel, the order of sums
+      // the fused form keeps) at the poses _begin was given, behind everything queued so far.
       GP_HIP(hipStreamSynchronize(b->stream));
       GP_HIP(hipMemset(b->d_factor_arrive.ptr, 0, sizeof(unsigned long long) * gp::kFactorArriveStride * F));
+      PoseSource ps;
+      ps.d_lin = b->dev_error_lin;
+      ps.d_eval = b->dev_error_eval;
+      ps.inl.use = 0;
       const gp::DoneFlags again{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq};
-      hipLaunchKernelGGL(gp::vgicp_finalize_error_kernel, dim3((int)F), dim3(gp::kBlockThreads), 0, b->stream, b->d_factors.as<gp::FactorDesc>(), (const double*)partials,
-                         static_cast<double*>(b->h_out_dev), -1, again);
-      GP_HIP(hipGetLastError());
+      GP_TRY(launch_error(b, ps, static_cast<double*>(b->h_out_dev), again));
       GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), F, again.seq, b->stream, spin_budget_us(b)));
     }
     b->factor_arrive_dirty = false;
     b->dev_error_fused = false;
   }
   memcpy(out_host, b->h_out.ptr, sizeof(double) * F);
+  return GP_OK;
+}
+
+int gp_debug_drop_error_words(gp_vgicp_batch_t* b, int count) {
+  if (!b || count < 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_debug_drop_error_words: a batch and count >= 0");
+  b->drop_error_words = count;
   return GP_OK;
 }
 
@@ -1820,7 +1840,8 @@ int gp_vgicp_batch_compute_error(gp_vgicp_batch_t* b, const double* poses_lin_ho
       GP_TRY(launch_tiles<gp::MODE_ERR>(b, ps, partials));
       fused_launched(b, ps, parts);
       GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), (size_t)parts, done.seq, b->stream, spin_budget_us(b)));
-      if (!words_arrived(b, parts, done.seq)) {  // (see batch_linearize_sync)
+      const bool dropped = take_dropped_error_words(b);
+      if (dropped || !words_arrived(b, parts, done.seq)) {  // (see batch_linearize_sync)
         GP_TRY(reset_arrival(b));
         fused = false;
       }
@@ -1866,7 +1887,8 @@ int gp_vgicp_batch_compute_error(gp_vgicp_batch_t* b, const double* poses_lin_ho
         static_cast<volatile unsigned long long*>(b->h_done.ptr)[i] = done.seq;
       }
     GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), F, done.seq, b->stream, spin_budget_us(b)));
-    if (!words_arrived(b, (int)F, done.seq)) {  // a counter left dirty by a launch that did not run to its end: clean them, the finalize kernel does this call's sums
+    const bool dropped = take_dropped_error_words(b);
+    if (dropped || !words_arrived(b, (int)F, done.seq)) {  // a counter left dirty by a launch that did not run to its end: clean them, the finalize kernel does this call's sums
       GP_HIP(hipMemset(b->d_factor_arrive.ptr, 0, sizeof(unsigned long long) * gp::kFactorArriveStride * F));
       const gp::DoneFlags again{done.flags, ++b->seq};
       hipLaunchKernelGGL(gp::vgicp_finalize_error_kernel, dim3((int)F), dim3(gp::kBlockThreads), 0, b->stream, b->d_factors.as<gp::FactorDesc>(), (const double*)partials,

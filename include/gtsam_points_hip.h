@@ -49,6 +49,9 @@ extern "C" {
 #define GP_ERROR_NOT_LOADED 3 /* voxel map / cloud offloaded from the GPU */
 #define GP_ERROR_IO 4
 #define GP_ERROR_INDETERMINATE 5 /* normal equations not positive definite (IndeterminantLinearSystemException upstream) */
+/* The rule of every damped step (dense and sparse, one launch or several): the Cholesky factorisation calls the system indeterminate when a pivot p is not above
+ * 1e-11 x the damped assembled diagonal entry of its column (A_pp + the damping + the prior, before any elimination).  A pivot is the entry after the elimination of
+ * the columns in front of it, so the rule reads: min_p pivot_p / A~_pp <= 1e-11 -> GP_ERROR_INDETERMINATE. */
 
 typedef void* gp_stream_t; /* hipStream_t */
 
@@ -448,6 +451,7 @@ int gp_dense_system_step(gp_dense_system_t* sys, const gp_linearized6* records_d
 int gp_dense_system_issue_step(gp_dense_system_t* sys, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
                                const double* prior_diag_host);
 int gp_dense_system_finish_step(gp_dense_system_t* sys, double* x_host, double* b_host, double* c_host);
+/* (one step in flight per system: an issue before the last one was finished or collected fails with GP_ERROR_INVALID_ARGUMENT and leaves that step untouched) */
 int gp_dense_system_device_solution(gp_dense_system_t* sys, const double** x_dev, const int** status_dev);
 /* a system of ONE pose (a scan registered onto a map) runs its step -- assembly, error sum, damping, 6 x 6 Cholesky, both substitutions, hand-over -- as ONE launch of one
  * 64-thread workgroup, the multi-launch path's arithmetic operation for operation (bit-identical); 0 selects the multi-launch path (tests, A/B); returns what the next
@@ -508,7 +512,9 @@ int gp_debug_sparse_step_trace(gp_sparse_system_t* sys, unsigned long long* dev_
  * pose_pairs[2 i + 1] (source) and is evaluated at target^-1 source (integrated_matching_cost_factor.cpp:28-31); pose_fixed[i] != 0 holds pose i (NULL = none held:
  * the gauge is then the caller's problem, the step reports GP_ERROR_INDETERMINATE); the free poses take the variable slots 0, 1, ... in pose order.  The graph builds
  * its own damped system on the batch's stream (one free pose: the dense 6 x 6 step; else block-sparse in `ordering`, gp_sparse_system_create) and does NOT own the batch.
- *   set_values   values_host = double[N][16], column-major 4x4 (all orthonormal to 1e-9: the rigid kernels serve the graph from then on; else the general ones);  get_values: the current values (after accept: the accepted trial's, as the device computed them)
+ *   set_values   values_host = double[N][16], column-major 4x4 (all orthonormal to 1e-9: the rigid kernels serve the graph from then on; else the general ones).  Whatever
+ *                the values, the relative pose of a factor is inverse(T_target) T_source with inverse(R, t) = (R^T, -R^T t): non-orthonormal values are inverted by
+ *                transpose, as gtsam::Pose3::inverse;  get_values: the current values (after accept: the accepted trial's, as the device computed them)
  *   linearize    asynchronous: the batch's linearise at the current values' relative poses -> records in HBM
  *   try_lambda   damped step + retract (Pose3::retract: T Expmap(xi), xi = (omega, v) = the step's six entries of the pose's slot) + the batch's error evaluation on the
  *                linearisation's correspondences at the trial values: queued back to back, ONE wait (a poll of the evaluation's completion words).  x_host [6 slots], b_host [6 slots], c_host (the cost at the
@@ -662,6 +668,9 @@ int gp_debug_side_stream_probe(gp_stream_t caller, float delays_us[4], int* chos
  * gp_debug_sort_fallbacks = how many builds of this thread did so far. */
 int gp_debug_inject_sort_fault(int count);
 int gp_debug_sort_fallbacks(void);
+/* test hook: the next `count` fused error evaluations of this batch (gp_vgicp_batch_compute_error, gp_vgicp_batch_compute_error_dev_end) read as if their
+ * completion words had not arrived and take the recovery path.  Host side only: the kernels run as always.  0 disarms. */
+int gp_debug_drop_error_words(gp_vgicp_batch_t* batch, int count);
 /* timeline hook (measurement): per-workgroup phase timestamps (s_memtime) of THIS batch's single-factor linearise into dev_buffer
  * ([2048][16] uint64: slots 0-7 phases, 8 HW_ID, 9 XCC_ID, 10 / 11 start / end on the device-wide clock; row 2047: the finalize kernel of the
  * synchronous call); NULL disables */

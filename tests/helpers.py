@@ -83,3 +83,49 @@ def lm_optimize(linearize_all, error_all, values, keys, fixed=(), max_iter=30, r
         if rel < rel_tol:
             break
     return values
+
+
+def host_system(records, slots, n_slots):
+    """DenseLinearSystemBuilder (linear_system_builder.cpp:39-48) on the host: scatter the Hessian blocks by key"""
+    A, b, c = np.zeros((6 * n_slots, 6 * n_slots)), np.zeros(6 * n_slots), 0.0
+    for rec, (st, ss) in zip(records, slots):
+        Ht, Hs, Hts = rec[2:38].reshape(6, 6).T, rec[38:74].reshape(6, 6).T, rec[74:110].reshape(6, 6).T
+        bt, bs = rec[110:116], rec[116:122]
+        c += rec[1]
+        if st >= 0:
+            A[6 * st : 6 * st + 6, 6 * st : 6 * st + 6] += Ht
+            b[6 * st : 6 * st + 6] -= bt
+        if ss >= 0:
+            A[6 * ss : 6 * ss + 6, 6 * ss : 6 * ss + 6] += Hs
+            b[6 * ss : 6 * ss + 6] -= bs
+        if st >= 0 and ss >= 0:
+            A[6 * st : 6 * st + 6, 6 * ss : 6 * ss + 6] += Hts
+            A[6 * ss : 6 * ss + 6, 6 * st : 6 * st + 6] += Hts.T
+    return A, b, c
+
+
+def kitti_graph(gpu, kitti07, n=5, pairs=None):
+    """the kitti07 graph of the LM tests: one voxel map (1 m) per cloud, factors over every pair (or `pairs`), truth and a perturbed start (pose 0 = truth)"""
+    import bench_lm
+
+    clouds = [gpu.PointCloudGPU(kitti07[f"points_{i}"], kitti07[f"covs_{i}"]) for i in range(n)]
+    maps = []
+    for c in clouds:
+        vm = gpu.GaussianVoxelMapGPU(1.0, target_points_drop_rate=0.0)
+        vm.insert(c)
+        maps.append(vm)
+    pairs = pairs or [(i, j) for i in range(n) for j in range(i + 1, n)]
+    factors = [gpu.IntegratedVGICPFactorGPU(i, j, maps[i], clouds[j]) for i, j in pairs]
+    truth = np.stack([np.asarray(T, dtype=np.float64) for T in kitti07["poses"][:n]])
+    v0 = truth @ bench_lm.expmap_many(np.random.default_rng(8191).uniform(-0.1, 0.1, (n, 6)))
+    v0[0] = truth[0]
+    return factors, pairs, truth, v0, (clouds, maps)
+
+
+def rigid(values):
+    """nearest rotations (the fixture's poses come from 6-digit text: orthonormal to 1e-6, which sends the host-pose entry points to the general kernels)"""
+    out = np.array(values, dtype=np.float64)
+    for T in out:
+        u, _, vt = np.linalg.svd(T[:3, :3])
+        T[:3, :3] = u @ vt
+    return out

@@ -273,3 +273,4 @@ def test_lm_params_default_and_argument_checks_without_a_device():
         assert fn(*args) == 1
     assert lib.gp_vgicp_batch_issue_linearize_dev(None, None, 1, None) == 1 and lib.gp_vgicp_batch_compute_error_dev(None, None, None, None) == 1
     assert lib.gp_sparse_system_finish_step(None, None, None, None) == 1 and lib.gp_dense_system_collect_step(None, None, None, None) == 1
+    assert lib.gp_debug_drop_error_words(None, 1) == 1  # the error-evaluation test hook refuses a null batch

@@ -13,6 +13,7 @@ sys.path.insert(0, ROOT)
 
 import bench_lm  # noqa: E402
 import oracle  # noqa: E402
+from helpers import kitti_graph as _kitti_graph, rigid as _rigid  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -58,30 +59,6 @@ def test_gpu_lm_reaches_the_gate_and_the_cpu_result(gpu, kitti07):
     for k in range(n):
         ang, tr = bench_lm.pose_error(results["device"]["values"][k], results["host"]["values"][k])
         assert ang < 1e-7 and tr < 1e-6
-
-
-def _kitti_graph(gpu, kitti07, n=5, pairs=None):
-    clouds = [gpu.PointCloudGPU(kitti07[f"points_{i}"], kitti07[f"covs_{i}"]) for i in range(n)]
-    maps = []
-    for c in clouds:
-        vm = gpu.GaussianVoxelMapGPU(1.0, target_points_drop_rate=0.0)
-        vm.insert(c)
-        maps.append(vm)
-    pairs = pairs or [(i, j) for i in range(n) for j in range(i + 1, n)]
-    factors = [gpu.IntegratedVGICPFactorGPU(i, j, maps[i], clouds[j]) for i, j in pairs]
-    truth = np.stack([np.asarray(T, dtype=np.float64) for T in kitti07["poses"][:n]])
-    v0 = truth @ bench_lm.expmap_many(np.random.default_rng(8191).uniform(-0.1, 0.1, (n, 6)))
-    v0[0] = truth[0]
-    return factors, pairs, truth, v0, (clouds, maps)
-
-
-def _rigid(values):
-    """nearest rotations (the fixture's poses come from 6-digit text: orthonormal to 1e-6, which sends the host-pose entry points to the general kernels)"""
-    out = np.array(values, dtype=np.float64)
-    for T in out:
-        u, _, vt = np.linalg.svd(T[:3, :3])
-        T[:3, :3] = u @ vt
-    return out
 
 
 @pytest.mark.parametrize("single,rigid", [(False, True), (True, True), (False, False), (True, False)])

@@ -3,7 +3,7 @@ DenseLinearSolver::solve restated with numpy on the host as the checker (the ref
 import numpy as np
 import pytest
 
-from helpers import expmap, pose_error
+from helpers import expmap, host_system as _host_system, pose_error
 
 pytestmark = pytest.mark.gpu
 
@@ -21,25 +21,6 @@ def _graph(gpu, kitti07, res=1.0):
     rng = np.random.default_rng(8191)
     values = {i: np.asarray(kitti07["poses"][i], dtype=np.float64) @ expmap(rng.uniform(-0.02, 0.02, 6)) for i in range(n)}
     return clouds, maps, pairs, factors, values
-
-
-def _host_system(records, slots, n_slots):
-    """DenseLinearSystemBuilder (linear_system_builder.cpp:39-48) on the host: scatter the Hessian blocks by key"""
-    A, b, c = np.zeros((6 * n_slots, 6 * n_slots)), np.zeros(6 * n_slots), 0.0
-    for rec, (st, ss) in zip(records, slots):
-        Ht, Hs, Hts = rec[2:38].reshape(6, 6).T, rec[38:74].reshape(6, 6).T, rec[74:110].reshape(6, 6).T
-        bt, bs = rec[110:116], rec[116:122]
-        c += rec[1]
-        if st >= 0:
-            A[6 * st : 6 * st + 6, 6 * st : 6 * st + 6] += Ht
-            b[6 * st : 6 * st + 6] -= bt
-        if ss >= 0:
-            A[6 * ss : 6 * ss + 6, 6 * ss : 6 * ss + 6] += Hs
-            b[6 * ss : 6 * ss + 6] -= bs
-        if st >= 0 and ss >= 0:
-            A[6 * st : 6 * st + 6, 6 * ss : 6 * ss + 6] += Hts
-            A[6 * ss : 6 * ss + 6, 6 * st : 6 * st + 6] += Hts.T
-    return A, b, c
 
 
 def test_build_damp_solve_match_host(gpu, kitti07):
