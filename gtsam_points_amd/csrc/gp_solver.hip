@@ -16,30 +16,20 @@
 // forward / backward substitution in one workgroup.  Dense O(n^3): meant for the hundreds of poses of a submap graph, not
 // tuned (the block-sparse factorisation is the obvious next step).
 #include <algorithm>
-#include <cstring>
-#include <map>
+#include <numeric>
+#include <utility>
 #include <vector>
 
+#include "gp_damped_step.hpp"
 #include "gp_host.hpp"
 #include "gp_lm_poses.hpp"
 
 namespace gp {
 
-// which 6x6 of a record a contribution takes: H_target, H_source, H_target_source (as is: row = target, col = source) or
-// its transpose (row = source, col = target)
-enum : int { TAKE_HT = 0, TAKE_HS = 1, TAKE_HTS = 2, TAKE_HTS_T = 3 };
-
 struct BlockDest {
   int row, col;      // block coordinates (row >= col: lower triangle)
   int begin, count;  // range in the contribution list
 };
-
-struct Contribution {
-  int factor;
-  int take;
-};
-
-constexpr int REC_HT = 2, REC_HS = 38, REC_HTS = 74, REC_BT = 110, REC_BS = 116;  // offsets (doubles) inside gp_linearized6
 
 // A (n x n, column-major, lower triangle + diagonal) and, for diagonal destinations, b: one 64-thread workgroup per block
 __global__ void __launch_bounds__(64) assemble_kernel(const BlockDest* __restrict__ dests, const Contribution* __restrict__ contribs, const double* __restrict__ records,
@@ -48,60 +38,21 @@ __global__ void __launch_bounds__(64) assemble_kernel(const BlockDest* __restric
   const int t = threadIdx.x;
   if (t < 36) {
     const int r = t % 6, c = t / 6;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const Contribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      double v;
-      if (q.take == TAKE_HT) {
-        v = rec[REC_HT + c * 6 + r];
-      } else if (q.take == TAKE_HS) {
-        v = rec[REC_HS + c * 6 + r];
-      } else if (q.take == TAKE_HTS) {
-        v = rec[REC_HTS + c * 6 + r];
-      } else {
-        v = rec[REC_HTS + r * 6 + c];
-      }
-      s += v;
-    }
+    const double s = gather_h(contribs, d.begin, d.count, records, r, c);
     A[(size_t)(6 * d.col + c) * n + 6 * d.row + r] = s;
     if (d.row == d.col && r == c) diag0[6 * d.row + r] = s;
   } else if (t < 42 && d.row == d.col) {
-    // b = sum of g = -b_target / -b_source (HessianFactor(.., -b_t, .., -b_s, ..), integrated_matching_cost_factor.cpp:49)
     const int r = t - 36;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const Contribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      s -= q.take == TAKE_HT ? rec[REC_BT + r] : rec[REC_BS + r];
-    }
-    b[6 * d.row + r] = s;
+    b[6 * d.row + r] = gather_g(contribs, d.begin, d.count, records, r);
   }
 }
 
-__global__ void __launch_bounds__(256) sum_errors_kernel(const double* __restrict__ records, int num_factors, double* __restrict__ c_out) {
-  __shared__ double part[256];
-  double s = 0.0;
-  for (int f = threadIdx.x; f < num_factors; f += 256) s += records[122 * (size_t)f + 1];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *c_out = part[0];
-}
-
-// buildDampedSystem: diag += lambda (identity damping) or lambda * clamp(diag, min, max) (diagonalDamping), + optional prior; diag0 keeps the damped diagonal (the
-// factorisation overwrites A's, and a pivot is held against it: chol6)
+// buildDampedSystem (damped_diagonal); diag0 keeps the damped diagonal (the factorisation overwrites A's, and a pivot is held against it: chol6)
 __global__ void __launch_bounds__(256) damp_kernel(double* __restrict__ A, int n, double lambda, int diagonal, double min_diag, double max_diag,
                                                    const double* __restrict__ prior_diag, double* __restrict__ diag0) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  const double d = A[(size_t)i * n + i];
-  double add = diagonal ? lambda * fmin(fmax(d, min_diag), max_diag) : lambda;
-  if (prior_diag) add += prior_diag[i];
-  A[(size_t)i * n + i] = d + add;
+  A[(size_t)i * n + i] = damped_diagonal(A[(size_t)i * n + i], lambda, diagonal, min_diag, max_diag, prior_diag ? prior_diag + i : nullptr);
   diag0[i] = A[(size_t)i * n + i];
 }
 
@@ -110,16 +61,12 @@ __global__ void __launch_bounds__(256) damp_kernel(double* __restrict__ A, int n
 // workgroup i - k (block row i > k) factors A_kk once more for itself (6x6: ~100 flops, cheaper than a kernel boundary) and
 // turns A_ik into L_ik = A_ik L_kk^-T in place.  A_kk itself is left untouched, so the redundant factorisations all read the
 // same data; the substitution kernel takes the diagonal blocks from Ldiag.
-// A pivot must exceed kPivotTolerance x the damped assembled diagonal entry of its column (scale6), the rule of the sparse kernels (gp_sparse.hip: chol6_wave), so that
-// the dense and the sparse step call the same systems indeterminate (include/gtsam_points_hip.h, GP_ERROR_INDETERMINATE).  Before, the dense step asked for piv > 0 and
-// solved a singular system into a huge step whenever rounding left a pivot of ~1e-16 A_pp positive.
-constexpr double kPivotTolerance = 1e-11;
-__device__ __forceinline__ bool chol6(double (*a)[6], const double* scale6) {  // in place, lower triangle; false when a pivot is not above the tolerance
+__device__ __forceinline__ bool chol6(double (*a)[6], const double* scale6) {  // in place, lower triangle; false when a pivot fails pivot_ok
   bool ok = true;
   for (int j = 0; j < 6; j++) {
     double d = a[j][j];
     for (int p = 0; p < j; p++) d -= a[j][p] * a[j][p];
-    if (!(d > kPivotTolerance * scale6[j])) {
+    if (!pivot_ok(d, scale6[j])) {
       ok = false;
       d = 1.0;
     }
@@ -270,53 +217,19 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
                                                                  int num_factors, double lambda, int diagonal, double min_diag, double max_diag, double* __restrict__ A,
                                                                  double* __restrict__ b, double* __restrict__ c_out, double* __restrict__ x, double* __restrict__ Ldiag,
                                                                  int* __restrict__ status, double* __restrict__ out_host, const LmPoseView epi, const int has_epi) {
-  __shared__ double part[256];
   __shared__ double l[6][6], a0[6][6], bb[6], xx[6], sc[6];
   __shared__ int st;
   const int t = threadIdx.x;
   const BlockDest d = dests[0];
-  // sum_errors_kernel: thread i of 256 adds the errors of factors i, i + 256, ...; the halving tree part[i] += part[i + w], w = 128 .. 1
-  for (int i = t; i < 256; i += 64) {
-    double s = 0.0;
-    for (int f = i; f < num_factors; f += 256) s += records[122 * (size_t)f + 1];
-    part[i] = s;
-  }
   // assemble_kernel
   if (t < 36) {
-    const int r = t % 6, c = t / 6;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const Contribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      double v;
-      if (q.take == TAKE_HT) v = rec[REC_HT + c * 6 + r];
-      else if (q.take == TAKE_HS) v = rec[REC_HS + c * 6 + r];
-      else if (q.take == TAKE_HTS) v = rec[REC_HTS + c * 6 + r];
-      else v = rec[REC_HTS + r * 6 + c];
-      s += v;
-    }
-    a0[r][c] = s;
+    a0[t % 6][t / 6] = gather_h(contribs, d.begin, d.count, records, t % 6, t / 6);
   } else if (t < 42) {
-    const int r = t - 36;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const Contribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      s -= q.take == TAKE_HT ? rec[REC_BT + r] : rec[REC_BS + r];
-    }
-    bb[r] = s;
+    bb[t - 36] = gather_g(contribs, d.begin, d.count, records, t - 36);
   }
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    for (int i = t; i < w; i += 64) part[i] += part[i + w];
-    __syncthreads();
-  }
+  const double err = sum_errors<64>(records, num_factors);  // sum_errors_kernel (its barriers publish a0 and bb as well)
   // damp_kernel (no prior: a step with one goes through the multi-launch path)
-  if (t < 6 && lambda > 0.0) {
-    const double dd = a0[t][t];
-    const double add = diagonal ? lambda * fmin(fmax(dd, min_diag), max_diag) : lambda;
-    a0[t][t] = dd + add;
-  }
+  if (t < 6 && lambda > 0.0) a0[t][t] = damped_diagonal(a0[t][t], lambda, diagonal, min_diag, max_diag, nullptr);
   __syncthreads();
   if (t < 36) {
     A[(size_t)(t / 6) * 6 + t % 6] = a0[t % 6][t / 6];  // column-major 6 x 6 (the upper triangle holds what the assembly left: the same sums, mirrored)
@@ -353,9 +266,9 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
     out_host[6 + t] = bb[t];
   }
   if (t == 0) {
-    *c_out = part[0];
+    *c_out = err;
     *status = st;
-    out_host[12] = part[0];
+    out_host[12] = err;
     out_host[13] = (double)st;
   }
   if (has_epi) {  // the device-resident LM trial's poses (gp_lm_poses.hpp) while x is at hand: one launch less behind the step
@@ -374,9 +287,8 @@ struct gp_dense_system {
   std::vector<gp::BlockDest> dests;
   std::vector<gp::Contribution> contribs;
   gp::DeviceArray d_dests, d_contribs, A, b, c, x, status, prior, Ldiag, diag0;  // diag0 [n]: the damped assembled diagonal (the pivots' scale)
-  gp::PinnedArray pinned;  // gp_dense_system_step: x [n] | b [n] | c | status, written by the step's last kernel
+  gp::StepHandoff step;  // gp_dense_system_step: x [n] | b [n] | c | status, written by the step's last kernel
   bool built = false;
-  bool step_in_flight = false;  // gp_dense_system_issue_step went out, gp_dense_system_finish_step has not collected it
   bool one_launch = true;       // a system of ONE pose runs its step as one launch (dense_one_pose_step_kernel); gp_dense_system_set_one_launch(sys, 0): the multi-launch form
 };
 
@@ -387,37 +299,24 @@ int gp_dense_system_create(int num_slots, const int* factor_slots, int num_facto
   *out = nullptr;
   if (num_slots <= 0 || num_slots > kMaxSlots || num_factors < 0 || (num_factors > 0 && !factor_slots))
     return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_create: 1 <= num_slots <= 2048, factor_slots = [num_factors][2] (target, source; < 0 = fixed)");
-  // destination block -> ordered contribution list (factor order = summation order)
-  std::map<std::pair<int, int>, std::vector<gp::Contribution>> lists;
   for (int f = 0; f < num_factors; f++) {
     const int st = factor_slots[2 * f], ss = factor_slots[2 * f + 1];
     if (st >= num_slots || ss >= num_slots) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_create: slot index out of range");
     if (st >= 0 && st == ss) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_create: a factor needs two different poses");
-    if (st >= 0) lists[{st, st}].push_back({f, gp::TAKE_HT});
-    if (ss >= 0) lists[{ss, ss}].push_back({f, gp::TAKE_HS});
-    if (st >= 0 && ss >= 0) {
-      if (st > ss) {
-        lists[{st, ss}].push_back({f, gp::TAKE_HTS});    // row = target, col = source
-      } else {
-        lists[{ss, st}].push_back({f, gp::TAKE_HTS_T});  // row = source, col = target
-      }
-    }
   }
   auto* s = new gp_dense_system;
   s->num_slots = num_slots;
   s->num_factors = num_factors;
   s->n = 6 * num_slots;
   s->stream = (hipStream_t)stream;
-  for (int p = 0; p < num_slots; p++) lists[{p, p}];  // every diagonal block exists (an unconstrained pose gives a singular system, reported by solve)
-  for (auto& kv : lists) {
-    gp::BlockDest d;
-    d.row = kv.first.first;
-    d.col = kv.first.second;
-    d.begin = (int)s->contribs.size();
-    d.count = (int)kv.second.size();
-    s->contribs.insert(s->contribs.end(), kv.second.begin(), kv.second.end());
-    s->dests.push_back(d);
-  }
+  // destination block (row, col) -> ordered contribution list; every diagonal block exists (an unconstrained pose gives a singular system, reported by solve)
+  std::vector<int> slot_pos(num_slots);
+  std::iota(slot_pos.begin(), slot_pos.end(), 0);
+  std::vector<std::pair<int, int>> diagonal;
+  for (int p = 0; p < num_slots; p++) diagonal.push_back({p, p});
+  gp::contribution_lists(
+      factor_slots, num_factors, slot_pos, diagonal, [](int i, int j) { return std::make_pair(i, j); },
+      [](const std::pair<int, int>& key, int begin, int count) { return gp::BlockDest{key.first, key.second, begin, count}; }, &s->dests, &s->contribs);
   const size_t n = (size_t)s->n;
   int rc = GP_OK;
   if ((rc = s->d_dests.alloc(sizeof(gp::BlockDest) * s->dests.size())) || (rc = s->d_contribs.alloc(sizeof(gp::Contribution) * std::max<size_t>(s->contribs.size(), 1))) ||
@@ -455,7 +354,7 @@ int gp_dense_system_build(gp_dense_system_t* s, const gp_linearized6* records_de
   GP_HIP(hipMemsetAsync(s->b.ptr, 0, sizeof(double) * n, s->stream));
   hipLaunchKernelGGL(gp::assemble_kernel, dim3((unsigned)s->dests.size()), dim3(64), 0, s->stream, s->d_dests.as<gp::BlockDest>(), s->d_contribs.as<gp::Contribution>(),
                      reinterpret_cast<const double*>(records_dev), s->n, s->A.as<double>(), s->b.as<double>(), s->diag0.as<double>());
-  hipLaunchKernelGGL(gp::sum_errors_kernel, dim3(1), dim3(256), 0, s->stream, reinterpret_cast<const double*>(records_dev), s->num_factors, s->c.as<double>());
+  hipLaunchKernelGGL(gp::sum_errors_kernel<>, dim3(1), dim3(256), 0, s->stream, reinterpret_cast<const double*>(records_dev), s->num_factors, s->c.as<double>());
   const double* prior = nullptr;
   if (prior_diag_host) {
     GP_HIP(hipMemcpyAsync(s->prior.ptr, prior_diag_host, sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
@@ -532,29 +431,25 @@ static int issue_step_impl(gp_dense_system_t* s, const gp_linearized6* records_d
                            const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) {
   if (fused) *fused = false;
   if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: null system");
-  // a step in flight owns the pinned x | b | c | status block and the device buffers until finish_step / collect_step: a second issue is refused, not queued over it
-  if (s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_issue_step: a step is in flight (finish it first)");
-  const size_t n = (size_t)s->n;
-  GP_TRY(s->pinned.ensure(sizeof(double) * (2 * n + 2)));
+  GP_TRY(s->step.begin("gp_dense_system", (size_t)s->n));
   if (s->num_slots == 1 && !prior_diag_host && s->one_launch) {
     if ((!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: bad arguments");
     hipLaunchKernelGGL(gp::dense_one_pose_step_kernel, dim3(1), dim3(64), 0, s->stream, s->d_dests.as<gp::BlockDest>(), s->d_contribs.as<gp::Contribution>(),
                        reinterpret_cast<const double*>(records_dev), s->num_factors, lambda, diagonal_damping, min_diagonal, max_diagonal, s->A.as<double>(), s->b.as<double>(),
-                       s->c.as<double>(), s->x.as<double>(), s->Ldiag.as<double>(), s->status.as<int>(), s->pinned.as<double>(), epi ? *epi : gp::LmPoseView{}, epi ? 1 : 0);
+                       s->c.as<double>(), s->x.as<double>(), s->Ldiag.as<double>(), s->status.as<int>(), s->step.host(), epi ? *epi : gp::LmPoseView{}, epi ? 1 : 0);
     if (fused) *fused = epi != nullptr;
     GP_HIP(hipGetLastError());
     s->built = false;
-    s->step_in_flight = true;
+    s->step.in_flight = true;
     return GP_OK;
   }
   GP_TRY(gp_dense_system_build(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host));
   GP_TRY(launch_dense_solve(s));
-  double* h = s->pinned.as<double>();
   hipLaunchKernelGGL(gp::dense_step_end_kernel, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, (const double*)s->x.as<double>(), (const double*)s->b.as<double>(),
-                     (const double*)s->c.as<double>(), (const int*)s->status.as<int>(), s->n, h);
+                     (const double*)s->c.as<double>(), (const int*)s->status.as<int>(), s->n, s->step.host());
   GP_HIP(hipGetLastError());
   s->built = false;
-  s->step_in_flight = true;
+  s->step.in_flight = true;
   return GP_OK;
 }
 
@@ -564,16 +459,8 @@ int gp_dense_system_issue_step(gp_dense_system_t* s, const gp_linearized6* recor
 }
 
 static int finish_step(gp_dense_system_t* s, double* x_host, double* b_host, double* c_host, bool wait) {
-  if (!s || !s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_finish_step: no step was issued");
-  const size_t n = (size_t)s->n;
-  const double* h = s->pinned.as<double>();
-  s->step_in_flight = false;
-  if (wait) GP_HIP(hipStreamSynchronize(s->stream));
-  if (b_host) memcpy(b_host, h + n, sizeof(double) * n);
-  if (c_host) *c_host = h[2 * n];
-  if (h[2 * n + 1] != 0.0) return gp::fail(GP_ERROR_INDETERMINATE, "gp_dense_system_step: the system is not positive definite (indeterminate linear system)");
-  if (x_host) memcpy(x_host, h, sizeof(double) * n);
-  return GP_OK;
+  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_finish_step: no step was issued");
+  return s->step.finish("gp_dense_system", s->stream, (size_t)s->n, wait, x_host, b_host, c_host);
 }
 
 int gp_dense_system_finish_step(gp_dense_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, true); }

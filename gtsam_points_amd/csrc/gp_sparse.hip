@@ -27,6 +27,7 @@
 #include <queue>
 #include <vector>
 
+#include "gp_damped_step.hpp"
 #include "gp_host.hpp"
 #include "gp_lm_poses.hpp"
 
@@ -427,16 +428,10 @@ static int sparse_symbolic(int num_slots, const int* factor_slots, int num_facto
 
 // ---- numeric phase ----------------------------------------------------------------------------------------------------------------
 
-enum : int { STAKE_HT = 0, STAKE_HS = 1, STAKE_HTS = 2, STAKE_HTS_T = 3 };
-constexpr int SREC_HT = 2, SREC_HS = 38, SREC_HTS = 74, SREC_BT = 110, SREC_BS = 116;  // offsets (doubles) inside gp_linearized6
-
 struct SparseDest {
   int block;         // destination block of L
   int diag_col;      // >= 0: the block is the diagonal block of this column (b is assembled with it)
   int begin, count;  // range in the contribution list
-};
-struct SparseContribution {
-  int factor, take;
 };
 
 // what gp_sparse_system_step folds into the assembly (one launch for: assemble, damp, b and c handed to the host, the status word cleared)
@@ -454,28 +449,17 @@ struct SparseStepExtras {
 };
 
 // A's blocks into their places in L's storage (every block of L has a destination: fill blocks have an empty contribution list and become zero) + b, one 64-lane
-// workgroup per destination, factor order.  STEP: the damping of sparse_damp_kernel applied to the diagonal as it is written (same operations in the same order:
-// bit-identical), b also stored in slot order where the host reads it, and one extra workgroup that sums the errors (sparse_sum_errors_kernel's order) and clears the status
+// workgroup per destination, factor order.  STEP: the damping of sparse_damp_kernel applied to the diagonal as it is written (damped_diagonal in both), b also stored in
+// slot order where the host reads it, and one extra workgroup that sums the errors (sum_errors, as sum_errors_kernel) and clears the status
 template <bool STEP>
-__global__ void __launch_bounds__(64) sparse_assemble_kernel(const SparseDest* __restrict__ dests, const SparseContribution* __restrict__ contribs,
+__global__ void __launch_bounds__(64) sparse_assemble_kernel(const SparseDest* __restrict__ dests, const Contribution* __restrict__ contribs,
                                                              const double* __restrict__ records, double* __restrict__ L, double* __restrict__ b, const SparseStepExtras ex) {
   const int t = threadIdx.x;
   if (STEP && (int)blockIdx.x == ex.num_dests) {
-    // c = sum of the factors' errors: 256 strided partial sums folded pairwise, exactly as sparse_sum_errors_kernel's 256 threads do (lane t carries threads t, t + 64, t + 128, t + 192)
-    __shared__ double part[256];
-    for (int q = 0; q < 4; q++) {
-      double s = 0.0;
-      for (int f = t + 64 * q; f < ex.num_factors; f += 256) s += records[122 * (size_t)f + 1];
-      part[t + 64 * q] = s;
-    }
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-      for (int i = t; i < w; i += 64) part[i] += part[i + w];
-      __syncthreads();
-    }
+    const double c = sum_errors<64>(records, ex.num_factors);
     if (t == 0) {
-      *ex.c_dev = part[0];
-      *ex.c_host = part[0];
+      *ex.c_dev = c;
+      *ex.c_host = c;
       *ex.status = 0;
     }
     return;
@@ -483,37 +467,14 @@ __global__ void __launch_bounds__(64) sparse_assemble_kernel(const SparseDest* _
   const SparseDest d = dests[blockIdx.x];
   if (t < 36) {
     const int r = t % 6, c = t / 6;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const SparseContribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      double v;
-      if (q.take == STAKE_HT) {
-        v = rec[SREC_HT + c * 6 + r];
-      } else if (q.take == STAKE_HS) {
-        v = rec[SREC_HS + c * 6 + r];
-      } else if (q.take == STAKE_HTS) {
-        v = rec[SREC_HTS + c * 6 + r];
-      } else {
-        v = rec[SREC_HTS + r * 6 + c];
-      }
-      s += v;
-    }
-    if (STEP && d.diag_col >= 0 && r == c && (ex.lambda > 0.0 || ex.prior_diag)) {
-      double add = ex.diagonal ? __dmul_rn(ex.lambda, fmin(fmax(s, ex.min_diag), ex.max_diag)) : ex.lambda;  // (explicit roundings: no contraction here or in sparse_damp_kernel)
-      if (ex.prior_diag) add = __dadd_rn(add, ex.prior_diag[6 * (size_t)d.diag_col + r]);
-      s = __dadd_rn(s, add);
-    }
+    double s = gather_h(contribs, d.begin, d.count, records, r, c);
+    if (STEP && d.diag_col >= 0 && r == c && (ex.lambda > 0.0 || ex.prior_diag))
+      s = damped_diagonal(s, ex.lambda, ex.diagonal, ex.min_diag, ex.max_diag, ex.prior_diag ? ex.prior_diag + 6 * (size_t)d.diag_col + r : nullptr);
     L[36 * (size_t)d.block + t] = s;
     if (d.diag_col >= 0 && r == c) ex.diag0[6 * (size_t)d.diag_col + r] = s;
   } else if (t < 42 && d.diag_col >= 0) {
     const int r = t - 36;
-    double s = 0.0;
-    for (int k = 0; k < d.count; k++) {
-      const SparseContribution q = contribs[d.begin + k];
-      const double* rec = records + 122 * (size_t)q.factor;
-      s -= q.take == STAKE_HT ? rec[SREC_BT + r] : rec[SREC_BS + r];  // g = -b (integrated_matching_cost_factor.cpp:49)
-    }
+    const double s = gather_g(contribs, d.begin, d.count, records, r);
     b[6 * (size_t)d.diag_col + r] = s;
     if (STEP) ex.b_slots_host[6 * (size_t)ex.perm[d.diag_col] + r] = s;
   }
@@ -524,10 +485,7 @@ __global__ void __launch_bounds__(256) sparse_damp_kernel(double* __restrict__ L
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   double* p = L + 36 * (size_t)colptr[i / 6] + 7 * (i % 6);
-  const double d = *p;
-  double add = diagonal ? __dmul_rn(lambda, fmin(fmax(d, min_diag), max_diag)) : lambda;
-  if (prior_diag) add = __dadd_rn(add, prior_diag[i]);
-  *p = __dadd_rn(d, add);
+  *p = damped_diagonal(*p, lambda, diagonal, min_diag, max_diag, prior_diag ? prior_diag + i : nullptr);
   diag0[i] = *p;
 }
 
@@ -586,10 +544,7 @@ __device__ __forceinline__ double lane_bcast_f64(double v, const int src_lane /*
   const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)b, src_lane), hi = __builtin_amdgcn_readlane((int)(unsigned)(b >> 32), src_lane);
   return __builtin_bit_cast(double, ((unsigned long long)hi << 32) | (unsigned long long)lo);
 }
-// A pivot must exceed kPivotTolerance x the diagonal entry of A it came from (scale6: the column's six assembled diagonal entries).  Rounds 1-5 asked for piv > 0: whether
-// a SINGULAR system (gauge freedom: no pose held) was reported then depended on the sign rounding left on a pivot of magnitude ~1e-13 A_pp; GTSAM's own Cholesky treats
-// pivots below a threshold as zero (base/cholesky.cpp: zeroPivotThreshold) for the same reason.  1e-11 relative: a system conditioned worse than that has no digits left.
-constexpr double kPivotTolerance = 1e-11;
+// A pivot is held against the column's six assembled diagonal entries (scale6): pivot_ok.
 __device__ __forceinline__ void chol6_wave(double (*D)[7], double* dinv, const int j, int* bad, const double* scale6) {
   const int r = j % 6, c = j / 6;
   double a = j < 36 ? D[r][c] : 0.0;
@@ -600,7 +555,7 @@ __device__ __forceinline__ void chol6_wave(double (*D)[7], double* dinv, const i
 #pragma unroll
   for (int p = 0; p < 6; p++) {
     double piv = lane_bcast_f64(a, 7 * p);  // D[p][p]: wave-uniform
-    if (!(piv > kPivotTolerance * sc[p])) {
+    if (!pivot_ok(piv, sc[p])) {
       any_bad = true;
       piv = 1.0;
     }
@@ -1005,19 +960,6 @@ __global__ void __launch_bounds__(256) sparse_step_end_kernel(const double* __re
   if (i == 0) *status_host = (double)*status;
 }
 
-__global__ void __launch_bounds__(256) sparse_sum_errors_kernel(const double* __restrict__ records, int num_factors, double* __restrict__ c_out) {
-  __shared__ double part[256];
-  double s = 0.0;
-  for (int f = threadIdx.x; f < num_factors; f += 256) s += records[122 * (size_t)f + 1];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *c_out = part[0];
-}
-
 
 // ---- the damped step of a SMALL graph: the assembly + ONE launch for everything behind it (round 6) -----------------------------------------------------
 // The multi-launch step above costs 0.21 ms on BASELINE configs[2]'s graph (63 free poses, 256 factors) and its launches are NOT the cost: the kernels' own time is
@@ -1174,7 +1116,7 @@ __device__ __forceinline__ void small_wave_column(const int k, const int lane, d
     for (int p = 0; p < 6; p++) {
       if (c0 == 0) {
         double piv = lane_bcast_f64(a[p], p);
-        if (!(piv > kPivotTolerance * sc[p])) {
+        if (!pivot_ok(piv, sc[p])) {
           any_bad = true;
           piv = 1.0;
         }
@@ -1351,7 +1293,7 @@ __device__ __forceinline__ void small_panel_sweep(const int k, const SmallSweepH
     for (int p = 0; p < 6; p++) {
       if (c0 == 0) {
         double piv = lane_bcast_f64(a[p], p);
-        if (!(piv > kPivotTolerance * sc[p])) {
+        if (!pivot_ok(piv, sc[p])) {
           any_bad = true;
           piv = 1.0;
         }
@@ -1821,15 +1763,14 @@ struct gp_sparse_system {
   int num_factors = 0, n = 0;
   hipStream_t stream = nullptr;
   std::vector<gp::SparseDest> dests;
-  std::vector<gp::SparseContribution> contribs;
+  std::vector<gp::Contribution> contribs;
   gp::DeviceArray d_dests, d_contribs, d_int, L, y, x, x_slots, c, status, prior, dinv, diag0;
-  gp::PinnedArray pinned;  // gp_sparse_system_step: x [n] | b [n] | c | status, written by the step's kernels, read by the host behind ONE synchronisation
+  gp::StepHandoff step;  // gp_sparse_system_step: x [n] | b [n] | c | status, written by the step's kernels, read by the host behind ONE synchronisation
   gp::SparseView view{};
   const int* d_perm = nullptr;
   bool built = false;
   // the one-launch step of small graphs (sparse_small_step_kernel): eligible when factor + index lists fit one compute unit's LDS
   bool small_ok = false, one_launch = false;
-  bool step_in_flight = false;        // gp_sparse_system_issue_step went out, gp_sparse_system_finish_step has not collected it
   std::vector<double> prior_staged;  // the permuted prior diagonal of the step in flight (source of its H2D copy)
   size_t small_lds_bytes = 0;
   gp::DeviceArray d_small_arena, d_level_ptr;
@@ -1906,39 +1847,20 @@ int gp_sparse_system_create(int num_slots, const int* factor_slots, int num_fact
   s->num_factors = num_factors;
   s->n = 6 * P;
   s->stream = (hipStream_t)stream;
-  // destination block -> ordered contribution list (factor order = summation order)
-  std::map<int, std::vector<gp::SparseContribution>> lists;
+  // block of L -> ordered contribution list, in elimination order; every block of L is a destination: diagonal blocks carry b, fill blocks get an empty list and are
+  // written as zeros (no memset per build)
   auto block_of = [&](int i, int k) {
     if (i == k) return S.colptr[k];
     const int* b = S.rowidx.data() + S.colptr[k] + 1;
     const int* e = S.rowidx.data() + S.colptr[k + 1];
     return (int)(std::lower_bound(b, e, i) - S.rowidx.data());
   };
-  for (int p = 0; p < nnzL; p++) lists[p];  // every block of L is a destination: diagonal blocks carry b, fill blocks get an empty list and are written as zeros (no memset per build)
-  for (int f = 0; f < num_factors; f++) {
-    const int st = factor_slots[2 * f], ss = factor_slots[2 * f + 1];
-    const int it = st >= 0 ? S.iperm[st] : -1, is = ss >= 0 ? S.iperm[ss] : -1;
-    if (it >= 0) lists[S.colptr[it]].push_back({f, gp::STAKE_HT});
-    if (is >= 0) lists[S.colptr[is]].push_back({f, gp::STAKE_HS});
-    if (it >= 0 && is >= 0) {
-      if (it > is) {
-        lists[block_of(it, is)].push_back({f, gp::STAKE_HTS});    // row = target, col = source
-      } else {
-        lists[block_of(is, it)].push_back({f, gp::STAKE_HTS_T});  // row = source, col = target
-      }
-    }
-  }
-  std::vector<int> diag_of((size_t)nnzL, -1);
+  std::vector<int> all_blocks((size_t)nnzL), diag_of((size_t)nnzL, -1);
+  std::iota(all_blocks.begin(), all_blocks.end(), 0);
   for (int k = 0; k < P; k++) diag_of[S.colptr[k]] = k;
-  for (auto& kv : lists) {
-    gp::SparseDest d;
-    d.block = kv.first;
-    d.diag_col = diag_of[kv.first];
-    d.begin = (int)s->contribs.size();
-    d.count = (int)kv.second.size();
-    s->contribs.insert(s->contribs.end(), kv.second.begin(), kv.second.end());
-    s->dests.push_back(d);
-  }
+  gp::contribution_lists(
+      factor_slots, num_factors, S.iperm, all_blocks, block_of, [&](int block, int begin, int count) { return gp::SparseDest{block, diag_of[block], begin, count}; },
+      &s->dests, &s->contribs);
   // one device arena for all index arrays
   const std::vector<int>* arrs[] = {&S.colptr, &S.rowidx, &S.upd_ptr, &S.upd_a, &S.upd_b, &S.row_ptr, &S.row_blk, &S.row_col, &S.work_ptr, &S.work_cols, &S.perm, &S.upd_bpos};
   size_t total = 0;
@@ -1953,14 +1875,14 @@ int gp_sparse_system_create(int num_slots, const int* factor_slots, int num_fact
   }
   int rc = GP_OK;
   if ((rc = s->d_int.alloc(sizeof(int) * packed.size())) || (rc = s->d_dests.alloc(sizeof(gp::SparseDest) * s->dests.size())) ||
-      (rc = s->d_contribs.alloc(sizeof(gp::SparseContribution) * std::max<size_t>(s->contribs.size(), 1))) || (rc = s->L.alloc(sizeof(double) * 36 * (size_t)nnzL)) ||
+      (rc = s->d_contribs.alloc(sizeof(gp::Contribution) * std::max<size_t>(s->contribs.size(), 1))) || (rc = s->L.alloc(sizeof(double) * 36 * (size_t)nnzL)) ||
       (rc = s->y.alloc(sizeof(double) * (size_t)s->n)) || (rc = s->x.alloc(sizeof(double) * (size_t)s->n)) || (rc = s->x_slots.alloc(sizeof(double) * (size_t)s->n)) ||
       (rc = s->c.alloc(sizeof(double))) || (rc = s->status.alloc(sizeof(int))) || (rc = s->prior.alloc(sizeof(double) * (size_t)s->n)) ||
       (rc = s->dinv.alloc(sizeof(double) * (size_t)s->n)) || (rc = s->diag0.alloc(sizeof(double) * (size_t)s->n)))
     return rc;
   GP_HIP(hipMemcpy(s->d_int.ptr, packed.data(), sizeof(int) * packed.size(), hipMemcpyHostToDevice));
   GP_HIP(hipMemcpy(s->d_dests.ptr, s->dests.data(), sizeof(gp::SparseDest) * s->dests.size(), hipMemcpyHostToDevice));
-  if (!s->contribs.empty()) GP_HIP(hipMemcpy(s->d_contribs.ptr, s->contribs.data(), sizeof(gp::SparseContribution) * s->contribs.size(), hipMemcpyHostToDevice));
+  if (!s->contribs.empty()) GP_HIP(hipMemcpy(s->d_contribs.ptr, s->contribs.data(), sizeof(gp::Contribution) * s->contribs.size(), hipMemcpyHostToDevice));
   const int* base = s->d_int.as<int>();
   s->view.colptr = base + offs[0];
   s->view.rowidx = base + offs[1];
@@ -2064,25 +1986,31 @@ int gp_sparse_system_info(const gp_sparse_system_t* s, int64_t* nnz_a_blocks, in
   return GP_OK;
 }
 
+// a prior diagonal given in slot order, permuted into elimination order (into `staged`, which must outlive the copy) and queued for upload to s->prior
+static int upload_prior(gp_sparse_system_t* s, const double* prior_diag_host, std::vector<double>* staged) {
+  const gp::SparseSymbolic& S = s->sym;
+  staged->resize((size_t)s->n);
+  for (int k = 0; k < S.P; k++)
+    for (int r = 0; r < 6; r++) (*staged)[6 * (size_t)k + r] = prior_diag_host[6 * (size_t)S.perm[k] + r];
+  GP_HIP(hipMemcpyAsync(s->prior.ptr, staged->data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+  return GP_OK;
+}
+
 int gp_sparse_system_build(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
                            const double* prior_diag_host) {
   if (!s || (!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_build: bad arguments");
-  const gp::SparseSymbolic& S = s->sym;
   // (no memsets: the destination list covers every block of L and every entry of y)
   hipLaunchKernelGGL(gp::sparse_assemble_kernel<false>, dim3((unsigned)s->dests.size()), dim3(64), 0, s->stream, s->d_dests.as<gp::SparseDest>(),
-                     s->d_contribs.as<gp::SparseContribution>(), reinterpret_cast<const double*>(records_dev), s->L.as<double>(), s->y.as<double>(), [&] {
+                     s->d_contribs.as<gp::Contribution>(), reinterpret_cast<const double*>(records_dev), s->L.as<double>(), s->y.as<double>(), [&] {
                        gp::SparseStepExtras e0{};
                        e0.diag0 = s->diag0.as<double>();
                        return e0;
                      }());
-  hipLaunchKernelGGL(gp::sparse_sum_errors_kernel, dim3(1), dim3(256), 0, s->stream, reinterpret_cast<const double*>(records_dev), s->num_factors, s->c.as<double>());
+  hipLaunchKernelGGL(gp::sum_errors_kernel<>, dim3(1), dim3(256), 0, s->stream, reinterpret_cast<const double*>(records_dev), s->num_factors, s->c.as<double>());
   const double* prior = nullptr;
   std::vector<double> permuted;
   if (prior_diag_host) {
-    permuted.resize((size_t)s->n);
-    for (int k = 0; k < S.P; k++)
-      for (int r = 0; r < 6; r++) permuted[6 * (size_t)k + r] = prior_diag_host[6 * (size_t)S.perm[k] + r];
-    GP_HIP(hipMemcpyAsync(s->prior.ptr, permuted.data(), sizeof(double) * (size_t)s->n, hipMemcpyHostToDevice, s->stream));
+    GP_TRY(upload_prior(s, prior_diag_host, &permuted));
     prior = s->prior.as<double>();
   }
   if (lambda > 0.0 || prior) {
@@ -2139,11 +2067,8 @@ static void launch_factor_and_substitutions(gp_sparse_system_t* s) {
     // band graph (profiles/r03_solver_time.txt): this form 1.34 ms; 512 threads + batches of eight products 1.45-1.48 ms with or without the next
     // batch's indices prefetched; 1024 threads + batches of eight 2.8 ms (the 128-register cap spills the batch)
     if (count > 0 && l == 0) hipLaunchKernelGGL(gp::sparse_factor_kernel<256>, dim3(count), dim3(256), 0, s->stream, s->view, first);
-    if (count > 0 && l > 0) {
-      constexpr bool staged = true;  // separator chains through the LDS-staged kernel (the per-entry gather for them as well: 1.45 vs 0.93 ms, profiles/r03_solver_time.txt)
-      if (staged) hipLaunchKernelGGL(gp::sparse_factor_staged_kernel<1024>, dim3(count), dim3(1024), 0, s->stream, s->view, first);
-      else hipLaunchKernelGGL(gp::sparse_factor_kernel<1024>, dim3(count), dim3(1024), 0, s->stream, s->view, first);
-    }
+    // separator chains through the LDS-staged kernel (the per-entry gather for them as well: 1.45 vs 0.93 ms, profiles/r03_solver_time.txt)
+    if (count > 0 && l > 0) hipLaunchKernelGGL(gp::sparse_factor_staged_kernel<1024>, dim3(count), dim3(1024), 0, s->stream, s->view, first);
   }
   for (int l = levels - 1; l >= 0; l--) {
     const int first = S.level_ptr[l], count = S.level_ptr[l + 1] - first;
@@ -2178,27 +2103,22 @@ int gp_sparse_system_solve(gp_sparse_system_t* s, double* x_host, double* x_dev_
 static int issue_step_impl(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
                            const double* prior_diag_host, const gp::LmPoseView* epi) {
   if (!s || (!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_step: bad arguments");
-  // a step in flight owns the pinned x | b | c | status block, prior_staged (the source of its pending H2D copy) and the device buffers until finish_step /
-  // collect_step: a second issue is refused, not queued over it
-  if (s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_issue_step: a step is in flight (finish it first)");
+  // (a step in flight also owns prior_staged, the source of its pending H2D copy)
+  GP_TRY(s->step.begin("gp_sparse_system", (size_t)s->n));
   const gp::SparseSymbolic& S = s->sym;
   const size_t n = (size_t)s->n;
-  GP_TRY(s->pinned.ensure(sizeof(double) * (2 * n + 2)));
-  double* h = s->pinned.as<double>();
+  double* h = s->step.host();
   gp::SparseStepExtras ex{};
   ex.lambda = lambda, ex.min_diag = min_diagonal, ex.max_diag = max_diagonal, ex.diagonal = diagonal_damping;
   if (prior_diag_host) {
-    s->prior_staged.resize(n);  // (outlives the copy: no second issue is taken while this step is in flight)
-    for (int k = 0; k < S.P; k++)
-      for (int r = 0; r < 6; r++) s->prior_staged[6 * (size_t)k + r] = prior_diag_host[6 * (size_t)S.perm[k] + r];
-    GP_HIP(hipMemcpyAsync(s->prior.ptr, s->prior_staged.data(), sizeof(double) * n, hipMemcpyHostToDevice, s->stream));
+    GP_TRY(upload_prior(s, prior_diag_host, &s->prior_staged));
     ex.prior_diag = s->prior.as<double>();
   }
   ex.perm = s->d_perm, ex.b_slots_host = h + n, ex.c_dev = s->c.as<double>(), ex.c_host = h + 2 * n, ex.status = s->status.as<int>();
   ex.num_factors = s->num_factors, ex.num_dests = (int)s->dests.size();
   ex.diag0 = s->diag0.as<double>();
   hipLaunchKernelGGL(gp::sparse_assemble_kernel<true>, dim3((unsigned)s->dests.size() + 1), dim3(64), 0, s->stream, s->d_dests.as<gp::SparseDest>(),
-                     s->d_contribs.as<gp::SparseContribution>(), reinterpret_cast<const double*>(records_dev), s->L.as<double>(), s->y.as<double>(), ex);
+                     s->d_contribs.as<gp::Contribution>(), reinterpret_cast<const double*>(records_dev), s->L.as<double>(), s->y.as<double>(), ex);
   if (s->one_launch) {
     // small graph: the assembly as it is (one workgroup per block of L across the chip: a gather of 8-byte values, which ONE compute unit's vector memory path takes
     // 40 us for), then factorisation and both substitutions in ONE launch with every operand in the LDS of one compute unit (sparse_small_step_kernel)
@@ -2215,7 +2135,7 @@ static int issue_step_impl(gp_sparse_system_t* s, const gp_linearized6* records_
   }
   GP_HIP(hipGetLastError());
   s->built = false;
-  s->step_in_flight = true;
+  s->step.in_flight = true;
   return GP_OK;
 }
 
@@ -2226,16 +2146,8 @@ int gp_sparse_system_issue_step(gp_sparse_system_t* s, const gp_linearized6* rec
 
 // waits for the stream and hands over what the step's kernels left in the pinned buffer
 static int finish_step(gp_sparse_system_t* s, double* x_host, double* b_host, double* c_host, bool wait) {
-  if (!s || !s->step_in_flight) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_finish_step: no step was issued");
-  const size_t n = (size_t)s->n;
-  const double* h = s->pinned.as<double>();
-  s->step_in_flight = false;
-  if (wait) GP_HIP(hipStreamSynchronize(s->stream));
-  if (b_host) memcpy(b_host, h + n, sizeof(double) * n);
-  if (c_host) *c_host = h[2 * n];
-  if (h[2 * n + 1] != 0.0) return gp::fail(GP_ERROR_INDETERMINATE, "gp_sparse_system_step: the system is not positive definite (indeterminate linear system)");
-  if (x_host) memcpy(x_host, h, sizeof(double) * n);
-  return GP_OK;
+  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_finish_step: no step was issued");
+  return s->step.finish("gp_sparse_system", s->stream, (size_t)s->n, wait, x_host, b_host, c_host);
 }
 
 int gp_sparse_system_finish_step(gp_sparse_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, true); }

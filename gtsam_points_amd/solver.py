@@ -39,81 +39,95 @@ def linearize_on_device(factors, values, device="cuda:0", stream=None):
     return out
 
 
-class DenseLinearSystemGPU:
-    """A x = b over 6-dof pose slots, built from stacked device-resident gp_linearized6 records.
+class _LinearSystemGPU:
+    """What the dense and the sparse system share: the C entry points gp_<prefix>_*, keyed by _PREFIX and bound once per system, so that a
+    call costs no more host time than a direct one (no name formatting or lookup per call)."""
 
-    factor_slots: [(target_slot, source_slot)] per factor; a negative slot = that pose is not a variable."""
+    _PREFIX = None
 
-    def __init__(self, num_slots, factor_slots, stream=None):
-        self._lib = _capi.load()
+    def _create(self, num_slots, factor_slots, stream, *extra):
+        lib = self._lib = _capi.load()
+        self._create_fn, self._destroy, self._build, self._download, self._solve, self._step = (
+            getattr(lib, f"{self._PREFIX}_{op}") for op in ("create", "destroy", "build", "download", "solve", "step"))
         self.num_slots = int(num_slots)
         self.factor_slots = np.ascontiguousarray(np.asarray(factor_slots, dtype=np.int32).reshape(-1, 2))
         self.stream = stream
         h = C.c_void_p()
-        _capi.check(self._lib.gp_dense_system_create(self.num_slots, self.factor_slots.ctypes.data, len(self.factor_slots), stream, C.byref(h)), "gp_dense_system_create")
+        _capi.check(self._create_fn(self.num_slots, self.factor_slots.ctypes.data, len(self.factor_slots), *extra, stream, C.byref(h)), self._create_fn.__name__)
         self._h = h
 
     def __del__(self):
         h = getattr(self, "_h", None)
         if h:
-            self._lib.gp_dense_system_destroy(h)
+            self._destroy(h)
             self._h = None
 
     @property
     def size(self):
         return 6 * self.num_slots
 
+    def _check_args(self, records_dev, prior_diag):
+        """-> the prior as a contiguous float64 array (or None) after the checks of records_dev and prior_diag"""
+        if tuple(records_dev.shape) != (len(self.factor_slots), _capi.LINEARIZED6_DOUBLES) or not records_dev.is_contiguous():
+            raise ValueError("records_dev must be a contiguous [num_factors, 122] float64 device tensor")
+        if prior_diag is None:
+            return None
+        prior = np.ascontiguousarray(prior_diag, dtype=np.float64)
+        if prior.shape != (self.size,):
+            raise ValueError("prior_diag must have 6 * num_slots entries")
+        return prior
+
     def build(self, records_dev, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, prior_diag=None):
         """records_dev: [F, 122] float64 CUDA tensor.  lam / diagonal_damping: buildDampedSystem; prior_diag: optional
         extra diagonal (length 6 * num_slots)."""
-        if tuple(records_dev.shape) != (len(self.factor_slots), _capi.LINEARIZED6_DOUBLES) or not records_dev.is_contiguous():
-            raise ValueError("records_dev must be a contiguous [num_factors, 122] float64 device tensor")
-        prior = None
-        if prior_diag is not None:
-            prior = np.ascontiguousarray(prior_diag, dtype=np.float64)
-            if prior.shape != (self.size,):
-                raise ValueError("prior_diag must have 6 * num_slots entries")
+        prior = self._check_args(records_dev, prior_diag)
         _capi.check(
-            self._lib.gp_dense_system_build(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
-                                            prior.ctypes.data if prior is not None else None),
-            "gp_dense_system_build",
+            self._build(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
+                              prior.ctypes.data if prior is not None else None),
+            self._build.__name__,
         )
         return self
 
     def download(self):
+        """(A dense symmetric [n, n], b, c) in slot order -- for checkers"""
         n = self.size
         A, b, c = np.zeros((n, n)), np.zeros(n), np.zeros(1)
-        _capi.check(self._lib.gp_dense_system_download(self._h, A.ctypes.data, b.ctypes.data, c.ctypes.data), "gp_dense_system_download")
+        _capi.check(self._download(self._h, A.ctypes.data, b.ctypes.data, c.ctypes.data), self._download.__name__)
         return A.T.copy(), b, float(c[0])  # column-major -> numpy (symmetric anyway)
 
     def solve(self):
         """x with A x = b (consumes the built system); raises GPError when A is not positive definite."""
         x = np.zeros(self.size)
-        _capi.check(self._lib.gp_dense_system_solve(self._h, x.ctypes.data, None), "gp_dense_system_solve")
+        _capi.check(self._solve(self._h, x.ctypes.data, None), self._solve.__name__)
         return x
+
+    def step(self, records_dev, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, prior_diag=None, out=None):
+        """build + download(b, c) + solve as ONE call with one synchronisation -- two with a prior_diag -- (gp_*_system_step): -> (x, b, c); the optimizer's tryLambda
+        (levenberg_marquardt_ext.cpp:188-260).  out: optional (x, b, c) float64 arrays to fill ([n], [n], [1]) instead of new ones.  Raises GPError (indeterminate) when the
+        damped system is not positive definite; out's b and c are filled even then."""
+        prior = self._check_args(records_dev, prior_diag)
+        x, b, c = _step_out(out, self.size)
+        _capi.check(
+            self._step(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
+                             prior.ctypes.data if prior is not None else None, x.ctypes.data, b.ctypes.data, c.ctypes.data),
+            self._step.__name__,
+        )
+        return x, b, float(c[0])
+
+
+class DenseLinearSystemGPU(_LinearSystemGPU):
+    """A x = b over 6-dof pose slots, built from stacked device-resident gp_linearized6 records.
+
+    factor_slots: [(target_slot, source_slot)] per factor; a negative slot = that pose is not a variable."""
+
+    _PREFIX = "gp_dense_system"
+
+    def __init__(self, num_slots, factor_slots, stream=None):
+        self._create(num_slots, factor_slots, stream)
 
     def set_one_launch(self, enable=True):
         """a system of ONE pose runs step() as one launch (default); False: the multi-launch path (bit-identical: tests, A/B).  -> what the next step() runs"""
         return bool(self._lib.gp_dense_system_set_one_launch(self._h, 1 if enable else 0))
-
-    def step(self, records_dev, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, prior_diag=None, out=None):
-        """build + download(b, c) + solve as ONE call with one synchronisation -- two with a prior_diag -- (gp_dense_system_step): -> (x, b, c); the optimizer's tryLambda
-        (levenberg_marquardt_ext.cpp:188-260).  out: optional (x, b, c) float64 arrays to fill ([n], [n], [1]) instead of new ones.  Raises GPError (indeterminate) when the
-        damped system is not positive definite; out's b and c are filled even then."""
-        if tuple(records_dev.shape) != (len(self.factor_slots), _capi.LINEARIZED6_DOUBLES) or not records_dev.is_contiguous():
-            raise ValueError("records_dev must be a contiguous [num_factors, 122] float64 device tensor")
-        prior = None
-        if prior_diag is not None:
-            prior = np.ascontiguousarray(prior_diag, dtype=np.float64)
-            if prior.shape != (self.size,):
-                raise ValueError("prior_diag must have 6 * num_slots entries")
-        x, b, c = _step_out(out, self.size)
-        _capi.check(
-            self._lib.gp_dense_system_step(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
-                                            prior.ctypes.data if prior is not None else None, x.ctypes.data, b.ctypes.data, c.ctypes.data),
-            "gp_dense_system_step",
-        )
-        return x, b, float(c[0])
 
 
 def _step_out(out, n):
@@ -147,7 +161,7 @@ def sparse_symbolic(num_slots, factor_slots, ordering=0):
                 critical_columns=cc.value, num_lists=wl.value, work_lists=lists)
 
 
-class SparseLinearSystemGPU:
+class SparseLinearSystemGPU(_LinearSystemGPU):
     """A x = b over 6-dof pose slots as a block-sparse lower triangle, solved by a block-sparse LL^T on the device.
 
     factor_slots as for DenseLinearSystemGPU; ordering: "natural" (slot order = elimination order), "nd" (nested dissection), "amd" (minimum degree by
@@ -155,26 +169,10 @@ class SparseLinearSystemGPU:
     "auto" (default: "nd" and "amd1" are both tried, the schedule with the shorter critical path is kept)."""
 
     ORDERINGS = {"natural": 0, "nd": 1, "amd": 2, "amd1": 3, "auto": 4}
+    _PREFIX = "gp_sparse_system"
 
     def __init__(self, num_slots, factor_slots, ordering="auto", stream=None):
-        self._lib = _capi.load()
-        self.num_slots = int(num_slots)
-        self.factor_slots = np.ascontiguousarray(np.asarray(factor_slots, dtype=np.int32).reshape(-1, 2))
-        self.stream = stream
-        h = C.c_void_p()
-        _capi.check(self._lib.gp_sparse_system_create(self.num_slots, self.factor_slots.ctypes.data, len(self.factor_slots), self.ORDERINGS[ordering], stream, C.byref(h)),
-                    "gp_sparse_system_create")
-        self._h = h
-
-    def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
-            self._lib.gp_sparse_system_destroy(h)
-            self._h = None
-
-    @property
-    def size(self):
-        return 6 * self.num_slots
+        self._create(num_slots, factor_slots, stream, self.ORDERINGS[ordering])
 
     def set_one_launch(self, enable=True):
         """step() of a system whose factor fits one compute unit's LDS (<= 128 poses, <= ~440 blocks of L) runs as ONE launch by default; False selects the multi-launch
@@ -187,52 +185,6 @@ class SparseLinearSystemGPU:
         na, nl, bp, ns, nt = C.c_int64(), C.c_int64(), C.c_int64(), C.c_int(), C.c_int()
         _capi.check(self._lib.gp_sparse_system_info(self._h, C.byref(na), C.byref(nl), C.byref(bp), C.byref(ns), C.byref(nt)), "gp_sparse_system_info")
         return dict(nnz_a_blocks=na.value, nnz_l_blocks=nl.value, block_products=bp.value, num_subtrees=ns.value, top_columns=nt.value)
-
-    def build(self, records_dev, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, prior_diag=None):
-        if tuple(records_dev.shape) != (len(self.factor_slots), _capi.LINEARIZED6_DOUBLES) or not records_dev.is_contiguous():
-            raise ValueError("records_dev must be a contiguous [num_factors, 122] float64 device tensor")
-        prior = None
-        if prior_diag is not None:
-            prior = np.ascontiguousarray(prior_diag, dtype=np.float64)
-            if prior.shape != (self.size,):
-                raise ValueError("prior_diag must have 6 * num_slots entries")
-        _capi.check(
-            self._lib.gp_sparse_system_build(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
-                                             prior.ctypes.data if prior is not None else None),
-            "gp_sparse_system_build",
-        )
-        return self
-
-    def download(self):
-        """(A dense symmetric [n, n], b, c) in slot order -- for checkers"""
-        n = self.size
-        A, b, c = np.zeros((n, n)), np.zeros(n), np.zeros(1)
-        _capi.check(self._lib.gp_sparse_system_download(self._h, A.ctypes.data, b.ctypes.data, c.ctypes.data), "gp_sparse_system_download")
-        return A.T.copy(), b, float(c[0])
-
-    def solve(self):
-        x = np.zeros(self.size)
-        _capi.check(self._lib.gp_sparse_system_solve(self._h, x.ctypes.data, None), "gp_sparse_system_solve")
-        return x
-
-    def step(self, records_dev, lam=0.0, diagonal_damping=False, min_diagonal=1e-6, max_diagonal=1e32, prior_diag=None, out=None):
-        """build + download(b, c) + solve as ONE call with one synchronisation (gp_sparse_system_step): -> (x, b, c); the optimizer's tryLambda
-        (levenberg_marquardt_ext.cpp:188-260).  out: optional (x, b, c) float64 arrays to fill ([n], [n], [1]) instead of new ones.  Raises GPError (indeterminate) when the
-        damped system is not positive definite; out's b and c are filled even then."""
-        if tuple(records_dev.shape) != (len(self.factor_slots), _capi.LINEARIZED6_DOUBLES) or not records_dev.is_contiguous():
-            raise ValueError("records_dev must be a contiguous [num_factors, 122] float64 device tensor")
-        prior = None
-        if prior_diag is not None:
-            prior = np.ascontiguousarray(prior_diag, dtype=np.float64)
-            if prior.shape != (self.size,):
-                raise ValueError("prior_diag must have 6 * num_slots entries")
-        x, b, c = _step_out(out, self.size)
-        _capi.check(
-            self._lib.gp_sparse_system_step(self._h, C.c_void_p(records_dev.data_ptr()), float(lam), int(bool(diagonal_damping)), float(min_diagonal), float(max_diagonal),
-                                            prior.ctypes.data if prior is not None else None, x.ctypes.data, b.ctypes.data, c.ctypes.data),
-            "gp_sparse_system_step",
-        )
-        return x, b, float(c[0])
 
 
 class LevenbergMarquardtGraphGPU:

@@ -291,7 +291,7 @@ def test_step_is_build_download_solve_in_one_call(gpu, kind):
 
     three, one = make(), make()
     prior = rng.uniform(0.0, 2.0, 6 * P)
-    for lam, diag, pr in [(0.0, False, None), (1e-3, False, None), (10.0, True, None), (1e-2, False, prior), (0.5, True, prior)]:
+    for lam, diag, pr in [(0.0, False, None), (1e-3, False, None), (10.0, True, None), (1e-3, True, None), (0.37, True, None), (1e-2, False, prior), (0.5, True, prior)]:
         three.build(rec_dev, lam=lam, diagonal_damping=diag, prior_diag=pr)
         _, b3, c3 = three.download()
         x3 = three.solve()
@@ -362,7 +362,8 @@ def test_one_launch_step_is_bit_identical(gpu, graph, ordering):
     assert lone.set_one_launch("lone-waves") is True
     prior = rng.uniform(0.0, 2.0, 6 * P)
     Ah, bh, ch = _host_system(rec, slots, P)
-    for lam, diag, pr in [(1e-5, False, None), (0.0, False, None), (1e-3, False, None), (10.0, True, None), (1e-2, False, prior), (0.5, True, prior)]:
+    for lam, diag, pr in [(1e-5, False, None), (0.0, False, None), (1e-3, False, None), (10.0, True, None), (1e-3, True, None), (0.37, True, None), (1e-2, False, prior),
+                          (0.5, True, prior)]:
         x1, b1, c1 = one.step(rec_dev, lam=lam, diagonal_damping=diag, prior_diag=pr)
         xm, bm, cm = multi.step(rec_dev, lam=lam, diagonal_damping=diag, prior_diag=pr)
         assert np.array_equal(x1, xm) and np.array_equal(b1, bm) and c1 == cm, (lam, diag, pr is not None, float(np.abs(x1 - xm).max()))
@@ -448,7 +449,7 @@ def test_one_pose_dense_step_is_bit_identical(gpu, num_factors):
     one, multi = gpu.DenseLinearSystemGPU(1, slots), gpu.DenseLinearSystemGPU(1, slots)
     assert one.set_one_launch(True) is True and multi.set_one_launch(False) is False
     Ah, bh, ch = _host_system(rec, slots, 1)
-    for lam, diag in [(1e-5, False), (0.0, False), (1e-2, False), (3.0, True)]:
+    for lam, diag in [(1e-5, False), (0.0, False), (1e-2, False), (3.0, True), (1e-3, True), (0.37, True)]:  # (diagonal damping at a general lambda: the one launch rounds as damp_kernel)
         x1, b1, c1 = one.step(rec_dev, lam=lam, diagonal_damping=diag)
         xm, bm, cm = multi.step(rec_dev, lam=lam, diagonal_damping=diag)
         assert np.array_equal(x1, xm) and np.array_equal(b1, bm) and c1 == cm, (lam, diag, float(np.abs(x1 - xm).max()))
