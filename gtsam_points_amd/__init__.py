@@ -19,7 +19,16 @@ from .factors import (  # noqa: F401
     pose_inverse,
 )
 from .features import IntegratedGICPFactorGPU, KdTreeGPU, estimate_covariances_gpu  # noqa: F401
-from .solver import DenseLinearSystemGPU, LevenbergMarquardtGraphGPU, SparseLinearSystemGPU, linearize_on_device, sparse_symbolic  # noqa: F401
+from .solver import (  # noqa: F401
+    BetweenFactorPose3,
+    DenseLinearSystemGPU,
+    LevenbergMarquardtGraphGPU,
+    PoseFactorsGPU,
+    PriorFactorPose3,
+    SparseLinearSystemGPU,
+    linearize_on_device,
+    sparse_symbolic,
+)
 from .types import GaussianVoxelMapGPU, PointCloudGPU, merge_frames_gpu, overlap_gpu  # noqa: F401
 
 __all__ = [
@@ -40,8 +49,11 @@ __all__ = [
     "create_nonlinear_factor_set_gpu",
     "overlap_gpu",
     "merge_frames_gpu",
+    "BetweenFactorPose3",
     "DenseLinearSystemGPU",
     "LevenbergMarquardtGraphGPU",
+    "PoseFactorsGPU",
+    "PriorFactorPose3",
     "SparseLinearSystemGPU",
     "sparse_symbolic",
     "linearize_on_device",

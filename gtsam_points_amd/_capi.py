@@ -242,9 +242,29 @@ _SIGNATURES = {
     "gp_lm_graph_accept": (C.c_int, [C.c_void_p]),
     "gp_lm_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_lm_graph_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
+    "gp_lm_graph_create_with_pose_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_pose_factors_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_pose_factors_destroy": (C.c_int, [C.c_void_p]),
+    "gp_pose_factors_size": (C.c_int, [C.c_void_p]),
+    "gp_pose_factors_issue_linearize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_pose_factors_issue_compute_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_pose_factors_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_pose_factors_compute_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_debug_sparse_work_lists": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_time_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }
+
+GP_POSE_FACTOR_BETWEEN, GP_POSE_FACTOR_PRIOR = 0, 1
+
+
+class PoseFactor(C.Structure):
+    """gp_pose_factor (include/gtsam_points_hip.h): a BetweenFactor<Pose3> / PriorFactor<Pose3> with a Gaussian noise model"""
+
+    _fields_ = [("kind", C.c_int), ("pose_a", C.c_int), ("pose_b", C.c_int), ("reserved_", C.c_int), ("measured", C.c_double * 16), ("information", C.c_double * 36)]
+
+
+assert C.sizeof(PoseFactor) == 432
+
 
 class LmParams(C.Structure):
     """gp_lm_params (include/gtsam_points_hip.h): GTSAM's LevenbergMarquardtParams fields the loop reads"""

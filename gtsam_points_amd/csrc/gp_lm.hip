@@ -27,6 +27,7 @@
 
 #include "gp_host.hpp"
 #include "gp_lm_poses.hpp"
+#include "gp_pose_factors.hpp"
 #include "gp_vgicp_shared.hpp"
 
 namespace gp {
@@ -38,11 +39,16 @@ __global__ void __launch_bounds__(256) lm_poses_kernel(const LmPoseView v) {
 }  // namespace gp
 
 struct gp_lm_graph {
-  gp_vgicp_batch_t* batch = nullptr;  // not owned
+  gp_vgicp_batch_t* batch = nullptr;  // not owned; null = a pure pose graph
   gp_sparse_system_t* sparse = nullptr;
   gp_dense_system_t* dense = nullptr;
   hipStream_t stream = nullptr;
   int F = 0, N = 0, slots = 0;
+  // pose factors (gp_pose_factors.hpp): records [F, F + P) of both record buffers; their errors at a trial's values reach the host through h_pose_errors, written by
+  // the launch that also writes their records at those values (speculation) -- queued in front of the batch's error evaluation, so its completion words cover them
+  int P = 0;
+  gp::DeviceArray d_pose_factors;
+  gp::PinnedArray h_pose_errors;
   std::vector<int> slot;
   gp::DeviceArray d_pairs, d_slot, d_values[2], d_deltas[2], d_records[2];
   gp::PinnedArray h_values[2];
@@ -96,29 +102,35 @@ int gp_lm_graph_destroy(gp_lm_graph_t* g) {
   return GP_OK;
 }
 
-int gp_lm_graph_create(gp_vgicp_batch_t* batch, const int* pose_pairs, int num_poses, const unsigned char* pose_fixed, int ordering, gp_lm_graph_t** out) {
-  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: null out");
-  *out = nullptr;
-  const int F = batch ? gp_vgicp_batch_size(batch) : 0;
-  if (!batch || F <= 0 || !pose_pairs || num_poses < 2) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: a batch of >= 1 factors, pose_pairs [F][2], >= 2 poses");
+// gp_lm_graph_create (P = 0: the same graph, the same launches) and gp_lm_graph_create_with_pose_factors; the arguments are checked by the callers
+static int create_graph(gp_vgicp_batch_t* batch, int F, const int* pose_pairs, const gp_pose_factor* pose_factors, int P, int num_poses, const unsigned char* pose_fixed,
+                        int ordering, gp_stream_t stream, gp_lm_graph_t** out) {
   auto* g = new gp_lm_graph;
-  g->batch = batch, g->F = F, g->N = num_poses;
+  g->batch = batch, g->F = F, g->N = num_poses, g->P = P;
   g->slot.assign((size_t)num_poses, -1);
   for (int i = 0; i < num_poses; i++)
     if (!pose_fixed || !pose_fixed[i]) g->slot[i] = g->slots++;
-  std::vector<int> factor_slots(2 * (size_t)F);
+  std::vector<int> factor_slots(2 * ((size_t)F + P));
   int rc = GP_OK;
   for (int f = 0; f < F && rc == GP_OK; f++) {
     const int t = pose_pairs[2 * f], s = pose_pairs[2 * f + 1];
     if (t < 0 || t >= num_poses || s < 0 || s >= num_poses || t == s) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: pose_pairs entries must be two different poses in [0, num_poses)");
     else factor_slots[2 * f] = g->slot[t], factor_slots[2 * f + 1] = g->slot[s];
   }
+  for (int p = 0; p < P; p++) {  // between: (slot[a], slot[b]); prior: a unary record (-1, slot[a])
+    const gp_pose_factor& pf = pose_factors[p];
+    const bool between = pf.kind == GP_POSE_FACTOR_BETWEEN;
+    factor_slots[2 * ((size_t)F + p)] = between ? g->slot[pf.pose_a] : -1;
+    factor_slots[2 * ((size_t)F + p) + 1] = between ? g->slot[pf.pose_b] : g->slot[pf.pose_a];
+  }
   if (rc == GP_OK && g->slots == 0) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: every pose is held");
-  gp_stream_t st = nullptr;
-  if (rc == GP_OK) rc = gp_vgicp_batch_stream(batch, &st);
+  gp_stream_t st = stream;
+  if (rc == GP_OK && batch) rc = gp_vgicp_batch_stream(batch, &st);
+  if (rc == GP_OK && batch && stream && stream != st) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: stream must be NULL or the batch's own");
   g->stream = (hipStream_t)st;
   // one free pose: the dense step (a 6 x 6 system); else the block-sparse one
-  if (rc == GP_OK) rc = g->slots == 1 ? gp_dense_system_create(1, factor_slots.data(), F, st, &g->dense) : gp_sparse_system_create(g->slots, factor_slots.data(), F, ordering, st, &g->sparse);
+  const int R = F + P;
+  if (rc == GP_OK) rc = g->slots == 1 ? gp_dense_system_create(1, factor_slots.data(), R, st, &g->dense) : gp_sparse_system_create(g->slots, factor_slots.data(), R, ordering, st, &g->sparse);
   if (rc == GP_OK) rc = g->sparse ? gp_sparse_system_device_solution(g->sparse, &g->x_dev, &g->status_dev) : gp_dense_system_device_solution(g->dense, &g->x_dev, &g->status_dev);
   const size_t vb = sizeof(double) * 16 * (size_t)num_poses, db = sizeof(double) * 16 * (size_t)F;
   for (int k = 0; k < 2 && rc == GP_OK; k++) {
@@ -126,9 +138,13 @@ int gp_lm_graph_create(gp_vgicp_batch_t* batch, const int* pose_pairs, int num_p
   }
   if (rc == GP_OK) rc = g->d_pairs.alloc(sizeof(int) * 2 * (size_t)F);
   if (rc == GP_OK) rc = g->d_slot.alloc(sizeof(int) * (size_t)num_poses);
-  for (int k = 0; k < 2 && rc == GP_OK; k++) rc = g->d_records[k].alloc(sizeof(gp_linearized6) * (size_t)F);
+  for (int k = 0; k < 2 && rc == GP_OK; k++) rc = g->d_records[k].alloc(sizeof(gp_linearized6) * (size_t)R);
+  if (rc == GP_OK && P > 0) rc = g->d_pose_factors.alloc(sizeof(gp_pose_factor) * (size_t)P);
+  if (rc == GP_OK && P > 0) rc = g->h_pose_errors.ensure(sizeof(double) * (size_t)P);
+  if (rc == GP_OK && P > 0 && hipMemcpy(g->d_pose_factors.ptr, pose_factors, sizeof(gp_pose_factor) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess)
+    rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the pose factors");
   g->errors.assign((size_t)F, 0.0);
-  if (rc == GP_OK && hipMemcpy(g->d_pairs.ptr, pose_pairs, sizeof(int) * 2 * (size_t)F, hipMemcpyHostToDevice) != hipSuccess) rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the pairs");
+  if (rc == GP_OK && F > 0 && hipMemcpy(g->d_pairs.ptr, pose_pairs, sizeof(int) * 2 * (size_t)F, hipMemcpyHostToDevice) != hipSuccess) rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the pairs");
   if (rc == GP_OK && hipMemcpy(g->d_slot.ptr, g->slot.data(), sizeof(int) * (size_t)num_poses, hipMemcpyHostToDevice) != hipSuccess) rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the slots");
   if (rc != GP_OK) {
     gp_lm_graph_destroy(g);
@@ -136,6 +152,25 @@ int gp_lm_graph_create(gp_vgicp_batch_t* batch, const int* pose_pairs, int num_p
   }
   *out = g;
   return GP_OK;
+}
+
+int gp_lm_graph_create(gp_vgicp_batch_t* batch, const int* pose_pairs, int num_poses, const unsigned char* pose_fixed, int ordering, gp_lm_graph_t** out) {
+  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: null out");
+  *out = nullptr;
+  const int F = batch ? gp_vgicp_batch_size(batch) : 0;
+  if (!batch || F <= 0 || !pose_pairs || num_poses < 2) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: a batch of >= 1 factors, pose_pairs [F][2], >= 2 poses");
+  return create_graph(batch, F, pose_pairs, nullptr, 0, num_poses, pose_fixed, ordering, nullptr, out);
+}
+
+int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pose_pairs, const gp_pose_factor* pose_factors, int num_pose_factors, int num_poses,
+                                         const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out) {
+  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: null out");
+  *out = nullptr;
+  const int F = batch ? gp_vgicp_batch_size(batch) : 0;
+  if (F < 0 || (F > 0 && !pose_pairs)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: pose_pairs [F][2]");
+  GP_TRY(gp::check_pose_factors(pose_factors, num_pose_factors, num_poses, "gp_lm_graph_create_with_pose_factors"));
+  if (F + num_pose_factors == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: a graph without factors");
+  return create_graph(batch, F, pose_pairs, pose_factors, num_pose_factors, num_poses, pose_fixed, ordering, stream, out);
 }
 
 // 0: no linearise is queued ahead of the host's decision (measurement / A-B; results are the same bits either way).  Returns the previous setting.
@@ -157,9 +192,11 @@ int gp_lm_graph_num_variables(const gp_lm_graph_t* g) { return g ? 6 * g->slots 
 
 int gp_lm_graph_set_values(gp_lm_graph_t* g, const double* values_host) {
   if (!g || !values_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_set_values: null");
+  bool rigid = true;
+  for (int i = 0; i < g->N; i++) rigid = rigid && gp::pose_is_rigid(values_host + 16 * (size_t)i);
+  if (g->P > 0 && !rigid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_set_values: a graph with pose factors takes rigid values (orthonormal to 1e-9, det > 0)");
   GP_HIP(hipStreamSynchronize(g->stream));  // (a trial in flight still writes the pinned values)
-  g->rigid = true;
-  for (int i = 0; i < g->N; i++) g->rigid = g->rigid && gp::pose_is_rigid(values_host + 16 * (size_t)i);
+  g->rigid = rigid;
   memcpy(g->h_values[g->cur].ptr, values_host, sizeof(double) * 16 * (size_t)g->N);
   GP_HIP(hipMemcpyAsync(g->d_values[g->cur].ptr, g->h_values[g->cur].ptr, sizeof(double) * 16 * (size_t)g->N, hipMemcpyHostToDevice, g->stream));
   GP_TRY(launch_poses(g, g->cur, g->cur, false));
@@ -175,8 +212,10 @@ int gp_lm_graph_get_values(gp_lm_graph_t* g, double* values_host) {
 
 int gp_lm_graph_linearize(gp_lm_graph_t* g) {
   if (!g || !g->have_values) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_linearize: set the values first");
-  if (!g->spec_valid)  // (else: queued behind the accepted trial's error evaluation)
-    GP_TRY(gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[g->cur].as<double>(), g->rigid ? 1 : 0, g->d_records[g->rec].as<gp_linearized6>()));
+  if (!g->spec_valid) {  // (else: queued behind the accepted trial's error evaluation)
+    if (g->batch) GP_TRY(gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[g->cur].as<double>(), g->rigid ? 1 : 0, g->d_records[g->rec].as<gp_linearized6>()));
+    GP_TRY(gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[g->cur].as<double>(), g->d_records[g->rec].as<gp_linearized6>() + g->F, nullptr, g->stream));
+  }
   g->spec_valid = false;
   g->linearized = true, g->tried = false;
   return GP_OK;
@@ -201,19 +240,30 @@ int gp_lm_graph_try_lambda(gp_lm_graph_t* g, double lambda, int diagonal_damping
   if (g->sparse) GP_TRY(gp::sparse_issue_step_with_poses(g->sparse, rec, lambda, diagonal_damping, min_diagonal, max_diagonal, pv, &fused));
   else GP_TRY(gp::dense_issue_step_with_poses(g->dense, rec, lambda, diagonal_damping, min_diagonal, max_diagonal, pv, &fused));
   int rc = fused ? GP_OK : launch_poses(g, g->cur, to, true);
-  if (rc == GP_OK) rc = gp_vgicp_batch_issue_compute_error_dev_begin(g->batch, g->d_deltas[g->cur].as<double>(), g->d_deltas[to].as<double>());
+  // the pose factors at the trial values the retract has just written (an indeterminate step leaves them = the current values): their errors, and with speculation
+  // their records for the next linearisation, in one launch -- in front of the batch's error evaluation, whose completion words therefore cover them
+  if (rc == GP_OK)
+    rc = gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[to].as<double>(), g->speculate ? g->d_records[1 - g->rec].as<gp_linearized6>() + g->F : nullptr,
+                                 g->h_pose_errors.as<double>(), g->stream);
+  if (rc == GP_OK && g->batch) rc = gp_vgicp_batch_issue_compute_error_dev_begin(g->batch, g->d_deltas[g->cur].as<double>(), g->d_deltas[to].as<double>());
   if (rc != GP_OK) {  // the step went out: collect it (its own wait) before the error is reported
     if (g->sparse) (void)gp_sparse_system_finish_step(g->sparse, nullptr, nullptr, nullptr);
     else (void)gp_dense_system_finish_step(g->dense, nullptr, nullptr, nullptr);
     return rc;
   }
   bool spec = false;
-  if (g->speculate) spec = gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[to].as<double>(), g->rigid ? 1 : 0, g->d_records[1 - g->rec].as<gp_linearized6>()) == GP_OK;
-  // the call's ONE wait: the completion words of the error evaluation (everything in front of it on the stream -- the step, the trial values -- is then complete and
-  // its pinned results are readable; the speculative linearise behind it is not waited for)
-  rc = gp_vgicp_batch_compute_error_dev_end(g->batch, g->errors.data());
-  const int rs = g->sparse ? (rc == GP_OK ? gp_sparse_system_collect_step(g->sparse, x_host, b_host, c_host) : gp_sparse_system_finish_step(g->sparse, x_host, b_host, c_host))
-                           : (rc == GP_OK ? gp_dense_system_collect_step(g->dense, x_host, b_host, c_host) : gp_dense_system_finish_step(g->dense, x_host, b_host, c_host));
+  if (g->speculate) spec = !g->batch || gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[to].as<double>(), g->rigid ? 1 : 0, g->d_records[1 - g->rec].as<gp_linearized6>()) == GP_OK;
+  // the call's ONE wait: the completion words of the error evaluation (everything in front of it on the stream -- the step, the trial values, the pose factors -- is
+  // then complete and its pinned results are readable; the speculative linearise behind it is not waited for).  Without a batch: the step's own finish, behind the
+  // pose factors' launch.
+  int rs;
+  if (g->batch) {
+    rc = gp_vgicp_batch_compute_error_dev_end(g->batch, g->errors.data());
+    rs = g->sparse ? (rc == GP_OK ? gp_sparse_system_collect_step(g->sparse, x_host, b_host, c_host) : gp_sparse_system_finish_step(g->sparse, x_host, b_host, c_host))
+                   : (rc == GP_OK ? gp_dense_system_collect_step(g->dense, x_host, b_host, c_host) : gp_dense_system_finish_step(g->dense, x_host, b_host, c_host));
+  } else {
+    rs = g->sparse ? gp_sparse_system_finish_step(g->sparse, x_host, b_host, c_host) : gp_dense_system_finish_step(g->dense, x_host, b_host, c_host);
+  }
   if (rc != GP_OK) return rc;
   if (rs != GP_OK) return rs;  // GP_ERROR_INDETERMINATE: b, c valid; no trial (the kernel behind the step left the trial values = the current ones)
   g->tried = true;
@@ -221,6 +271,8 @@ int gp_lm_graph_try_lambda(gp_lm_graph_t* g, double lambda, int diagonal_damping
   if (new_error) {
     double e = 0.0;
     for (int f = 0; f < g->F; f++) e += g->errors[(size_t)f];
+    const double* pe = g->h_pose_errors.as<double>();
+    for (int p = 0; p < g->P; p++) e += pe[p];
     *new_error = e;
   }
   if (new_values_host) memcpy(new_values_host, g->h_values[to].ptr, sizeof(double) * 16 * (size_t)g->N);

@@ -6,6 +6,8 @@
   SparseLinearSystemGPU <- SparseLinearSystemBuilder<6> (optimizers/linear_system_builder.hpp:41-72) + buildDampedSystem
                            + SparseLinearSolver::solve (optimizers/linear_solver.hpp:24-29): block-sparse LL^T over the pose graph
   linearize_on_device   -- one batched linearise whose records stay in HBM (what the solver consumes)
+  BetweenFactorPose3 / PriorFactorPose3 / PoseFactorsGPU
+                        <- gtsam::BetweenFactor<Pose3> / gtsam::PriorFactor<Pose3> with a Gaussian noise model, linearised on the device into the same records
 
 Poses that are variables get a slot (0..num_slots-1); a factor key without a slot (a fixed pose) drops out of the system.
 """
@@ -37,6 +39,124 @@ def linearize_on_device(factors, values, device="cuda:0", stream=None):
     finally:
         lib.gp_vgicp_batch_destroy(batch)
     return out
+
+
+def _information(information, sigmas):
+    """Lambda in (omega, v) order: `information` as given, or diag(sigmas^-2) (noiseModel::Diagonal::Sigmas); neither = the unit model"""
+    if information is not None and sigmas is not None:
+        raise ValueError("give information or sigmas, not both")
+    if sigmas is not None:
+        s = np.asarray(sigmas, dtype=np.float64).reshape(-1)
+        if s.shape != (6,):
+            raise ValueError("sigmas must have 6 entries (omega, v)")
+        return np.diag(1.0 / (s * s))
+    lam = np.eye(6) if information is None else np.asarray(information, dtype=np.float64)
+    if lam.shape != (6, 6):
+        raise ValueError("information must be 6 x 6")
+    return lam
+
+
+class BetweenFactorPose3:
+    """gtsam::BetweenFactor<Pose3>(key1, key2, measured, Gaussian noise): e = Logmap(measured^-1 T_key1^-1 T_key2), GTSAM's default Jacobians.
+    information: Lambda 6 x 6 in (omega, v) order (noiseModel->R()^T R()); sigmas: noiseModel::Diagonal::Sigmas instead."""
+
+    kind = _capi.GP_POSE_FACTOR_BETWEEN
+
+    def __init__(self, key1, key2, measured, information=None, sigmas=None):
+        self.keys = (int(key1), int(key2))
+        self.measured = np.asarray(measured, dtype=np.float64).reshape(4, 4).copy()
+        self.information = _information(information, sigmas)
+
+    def _struct(self):
+        f = _capi.PoseFactor()
+        f.kind, f.pose_a, f.pose_b = self.kind, self.keys[0], self.keys[1] if len(self.keys) > 1 else -1
+        f.measured[:] = np.ascontiguousarray(self.measured.T).reshape(16)
+        f.information[:] = np.ascontiguousarray(self.information.T).reshape(36)
+        return f
+
+
+class PriorFactorPose3(BetweenFactorPose3):
+    """gtsam::PriorFactor<Pose3>(key, prior, Gaussian noise): e = Logmap(prior^-1 T_key), J = I"""
+
+    kind = _capi.GP_POSE_FACTOR_PRIOR
+
+    def __init__(self, key, prior, information=None, sigmas=None):
+        self.keys = (int(key),)
+        self.measured = np.asarray(prior, dtype=np.float64).reshape(4, 4).copy()
+        self.information = _information(information, sigmas)
+
+
+def _pose_factor_array(pose_factors):
+    arr = (_capi.PoseFactor * max(len(pose_factors), 1))()
+    for i, f in enumerate(pose_factors):
+        arr[i] = f._struct()
+    return arr
+
+
+def _values16(values, num_poses):
+    v = np.asarray(values, dtype=np.float64)
+    if v.shape != (num_poses, 4, 4):
+        raise ValueError(f"values must be [{num_poses}, 4, 4]")
+    return np.ascontiguousarray(v.transpose(0, 2, 1)).reshape(num_poses, 16)
+
+
+class PoseFactorsGPU:
+    """BetweenFactorPose3 / PriorFactorPose3 objects over poses 0..num_poses-1, linearised on the device (gp_pose_factors_*) into gp_linearized6 records: a between
+    factor's target is key1 and its source key2, a prior is a unary record on its source side.  factor_slots(slot) gives the (target, source) slots that
+    DenseLinearSystemGPU / SparseLinearSystemGPU take for these records: (slot[key1], slot[key2]) and (-1, slot[key])."""
+
+    def __init__(self, factors, num_poses, stream=None):
+        self._lib = _capi.load()
+        self.factors = list(factors)
+        self.num_poses = int(num_poses)
+        self.stream = stream
+        h = C.c_void_p()
+        _capi.check(self._lib.gp_pose_factors_create(_pose_factor_array(self.factors), len(self.factors), self.num_poses, stream, C.byref(h)), "gp_pose_factors_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_pose_factors_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return len(self.factors)
+
+    def factor_slots(self, slot):
+        slot = np.asarray(slot)
+        return np.array([(slot[f.keys[0]], slot[f.keys[1]]) if len(f.keys) == 2 else (-1, slot[f.keys[0]]) for f in self.factors], dtype=np.int32).reshape(-1, 2)
+
+    def linearize(self, values):
+        """-> [P, 122] float64 records (host), synchronous"""
+        out = np.zeros((len(self.factors), _capi.LINEARIZED6_DOUBLES))
+        v = _values16(values, self.num_poses)  # (held: the library reads it through its raw pointer)
+        _capi.check(self._lib.gp_pose_factors_linearize(self._h, v.ctypes.data, out.ctypes.data), "gp_pose_factors_linearize")
+        return out
+
+    def error(self, values):
+        """-> [P] the factors' error() = 1/2 e^T Lambda e, synchronous"""
+        out = np.zeros(len(self.factors))
+        v = _values16(values, self.num_poses)
+        _capi.check(self._lib.gp_pose_factors_compute_error(self._h, v.ctypes.data, out.ctypes.data), "gp_pose_factors_compute_error")
+        return out
+
+    def linearize_on_device(self, values, device="cuda:0"):
+        """-> [P, 122] float64 CUDA tensor of records (nothing is copied to the host); values: [num_poses, 4, 4] host array or [num_poses, 16] column-major CUDA tensor"""
+        import torch
+
+        if isinstance(values, torch.Tensor):
+            poses = values.to(dtype=torch.float64).contiguous()
+        else:
+            poses = torch.from_numpy(_values16(values, self.num_poses)).to(device)
+        if tuple(poses.shape) != (self.num_poses, 16):
+            raise ValueError(f"device values must be [{self.num_poses}, 16] (column-major 4x4)")
+        out = torch.zeros((len(self.factors), _capi.LINEARIZED6_DOUBLES), dtype=torch.float64, device=poses.device)
+        torch.cuda.current_stream(out.device).synchronize()
+        _capi.check(self._lib.gp_pose_factors_issue_linearize_dev(self._h, C.c_void_p(poses.data_ptr()), C.c_void_p(out.data_ptr())), "gp_pose_factors_issue_linearize_dev")
+        _capi.check(self._lib.gp_stream_synchronize(self.stream), "gp_stream_synchronize")
+        return out
 
 
 class _LinearSystemGPU:
@@ -193,11 +313,14 @@ class LevenbergMarquardtGraphGPU:
     :188-350) as linearize() / try_lambda() / accept(), one wait per trial; optimize() runs the reference's loop over them natively.
 
     factors: IntegratedVGICPFactorGPU objects; pairs[i] = (target pose, source pose) of factor i, poses 0..num_poses-1; fixed: indices of held poses.
-    values are [num_poses, 4, 4] float64 arrays (rigid)."""
+    pose_factors: BetweenFactorPose3 / PriorFactorPose3 objects over the same poses (gp_lm_graph_create_with_pose_factors): their records follow the VGICP ones,
+    `factors` may then be empty (a pose graph) and `fixed` may be () (the priors fix the gauge).  values are [num_poses, 4, 4] float64 arrays (rigid)."""
 
-    def __init__(self, factors, pairs, num_poses, fixed=(0,), ordering="auto", stream=None):
+    def __init__(self, factors, pairs, num_poses, fixed=(0,), ordering="auto", stream=None, pose_factors=()):
         self._lib = _capi.load()
         self.factors = list(factors)  # (kept alive: the batch holds their handles)
+        self.pose_factors = list(pose_factors)
+        self._stream = stream
         F = len(self.factors)
         self.pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
         if len(self.pairs) != F:
@@ -206,12 +329,21 @@ class LevenbergMarquardtGraphGPU:
         held = np.zeros(self.num_poses, dtype=np.uint8)
         held[list(fixed)] = 1
         self._batch, self._h = C.c_void_p(), C.c_void_p()
-        arr = (C.c_void_p * F)(*[f._h.value for f in self.factors])
-        _capi.check(self._lib.gp_vgicp_batch_create(arr, F, stream, C.byref(self._batch)), "gp_vgicp_batch_create")
+        if F > 0 or not self.pose_factors:
+            arr = (C.c_void_p * F)(*[f._h.value for f in self.factors])
+            _capi.check(self._lib.gp_vgicp_batch_create(arr, F, stream, C.byref(self._batch)), "gp_vgicp_batch_create")
+        else:
+            self._batch = None
         try:
-            _capi.check(self._lib.gp_lm_graph_create(self._batch, self.pairs.ctypes.data, self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], C.byref(self._h)), "gp_lm_graph_create")
+            if self.pose_factors:
+                _capi.check(self._lib.gp_lm_graph_create_with_pose_factors(self._batch, self.pairs.ctypes.data, _pose_factor_array(self.pose_factors), len(self.pose_factors),
+                                                                          self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
+                            "gp_lm_graph_create_with_pose_factors")
+            else:
+                _capi.check(self._lib.gp_lm_graph_create(self._batch, self.pairs.ctypes.data, self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], C.byref(self._h)), "gp_lm_graph_create")
         except Exception:
-            self._lib.gp_vgicp_batch_destroy(self._batch)
+            if self._batch:
+                self._lib.gp_vgicp_batch_destroy(self._batch)
             self._batch = None
             raise
         self.n = self._lib.gp_lm_graph_num_variables(self._h)
@@ -248,7 +380,24 @@ class LevenbergMarquardtGraphGPU:
         _capi.check(self._lib.gp_lm_graph_linearize(self._h), "gp_lm_graph_linearize")
 
     def sync(self):
-        _capi.check(self._lib.gp_vgicp_batch_sync(self._batch), "gp_vgicp_batch_sync")
+        if self._batch:
+            _capi.check(self._lib.gp_vgicp_batch_sync(self._batch), "gp_vgicp_batch_sync")
+        else:
+            _capi.check(self._lib.gp_stream_synchronize(self._stream), "gp_stream_synchronize")
+
+    def records(self):
+        """-> [F + P, 122] float64 CUDA tensor: a copy of the records of the last linearise (the VGICP factors', then the pose factors')"""
+        import torch
+
+        p = C.c_void_p()
+        _capi.check(self._lib.gp_lm_graph_records(self._h, C.byref(p), None), "gp_lm_graph_records")
+        self.sync()
+        n = (len(self.factors) + len(self.pose_factors)) * _capi.LINEARIZED6_DOUBLES
+        out = torch.zeros(n, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()
+        _capi.check(self._lib.gp_memcpy_d2d(C.c_void_p(out.data_ptr()), p, 8 * n, None), "gp_memcpy_d2d")
+        _capi.check(self._lib.gp_stream_synchronize(None), "gp_stream_synchronize")
+        return out.reshape(-1, _capi.LINEARIZED6_DOUBLES)
 
     def try_lambda(self, lam, diagonal=False, min_diagonal=1e-6, max_diagonal=1e32, want_values=False):
         """-> (dx, b, cost at the linearisation point, cost at the trial values[, trial values]); GPError (code 5) on an indeterminate system.

@@ -551,9 +551,45 @@ int gp_lm_graph_set_speculation(gp_lm_graph_t* graph, int enable);
  * its own behind it; default 1: the one-launch step where the system qualifies, the retract as its epilogue).  Same bits. */
 int gp_lm_graph_set_one_launch(gp_lm_graph_t* graph, int enable);
 int gp_lm_graph_optimize(gp_lm_graph_t* graph, const gp_lm_params* params, gp_lm_summary* summary);
-/* for checkers: the records of the last linearise and the relative poses of the current values, where they lie in device memory (valid until the graph is destroyed;
- * contents as of the work queued so far on the batch's stream) */
+/* for checkers: the records of the last linearise (F, then the pose factors' P: gp_lm_graph_create_with_pose_factors) and the relative poses of the current values, where
+ * they lie in device memory (valid until the graph is destroyed; contents as of the work queued so far on the graph's stream) */
 int gp_lm_graph_records(gp_lm_graph_t* graph, const gp_linearized6** records_dev, const double** relative_poses_dev);
+
+/* ---- gtsam::BetweenFactor<Pose3> / gtsam::PriorFactor<Pose3> with a Gaussian noise model (gp_pose_factors.hip) ----
+ * GTSAM 4.2, default build (GTSAM_POSE3_EXPMAP on, GTSAM_SLOW_BUT_CORRECT_BETWEENFACTOR off); poses column-major 4x4, tangent order (omega, v), Lambda = R^T R of the
+ * noise model in that order:
+ *   between (pose_a, pose_b, measured Z):  e = Logmap(Z^-1 T_a^-1 T_b), J_a = -AdjointMap((T_a^-1 T_b)^-1), J_b = I (no LogmapDerivative(e): GTSAM's own choice)
+ *   prior (pose_a, Z; pose_b = -1):        e = Logmap(Z^-1 T_a), J_a = I
+ * Each factor linearises into ONE gp_linearized6 record: error = 1/2 e^T Lambda e (the factor's error(), as a VGICP record's error is that factor's error(); a caller
+ * that builds a gtsam::HessianFactor from a record passes f = 2 error), num_inliers = 0; between: target = pose_a, source = pose_b (a VGICP factor is evaluated at
+ * target^-1 source), H_target = J_a^T Lambda J_a, H_source = Lambda, H_target_source = J_a^T Lambda, b_target = J_a^T Lambda e, b_source = Lambda e; prior: a unary
+ * record (H_source = Lambda, b_source = Lambda e, the rest 0) whose target slot is negative in gp_*_system_create's factor_slots.
+ * create refuses (GP_ERROR_INVALID_ARGUMENT, before any device work): a pose out of [0, num_poses), a between factor with pose_a = pose_b, a prior with pose_b != -1,
+ * an unknown kind, a measured pose that is not orthonormal to 1e-9 with det > 0, an information matrix that is not finite or not symmetric to 1e-12 x its largest entry.
+ * The _dev forms are asynchronous on the stream given to create (poses_dev = double[num_poses][16]); the others copy the poses up, wait and copy the results down. */
+#define GP_POSE_FACTOR_BETWEEN 0
+#define GP_POSE_FACTOR_PRIOR 1
+typedef struct gp_pose_factor {
+  int kind, pose_a, pose_b, reserved_; /* prior: pose_b = -1 */
+  double measured[16];                 /* column-major 4x4, orthonormal to 1e-9 */
+  double information[36];              /* Lambda, (omega, v) order, column-major, symmetric, finite */
+} gp_pose_factor;                      /* 432 B */
+typedef struct gp_pose_factors gp_pose_factors_t;
+int gp_pose_factors_create(const gp_pose_factor* factors, int num_factors, int num_poses, gp_stream_t stream, gp_pose_factors_t** out);
+int gp_pose_factors_destroy(gp_pose_factors_t* pf);
+int gp_pose_factors_size(const gp_pose_factors_t* pf); /* num_factors; 0 for NULL */
+int gp_pose_factors_issue_linearize_dev(gp_pose_factors_t* pf, const double* poses_dev, gp_linearized6* out_dev); /* out_dev [num_factors] */
+int gp_pose_factors_issue_compute_error_dev(gp_pose_factors_t* pf, const double* poses_dev, double* out_dev);      /* out_dev [num_factors] */
+int gp_pose_factors_linearize(gp_pose_factors_t* pf, const double* poses_host, gp_linearized6* out_host);
+int gp_pose_factors_compute_error(gp_pose_factors_t* pf, const double* poses_host, double* out_host);
+/* an LM graph of VGICP factors (batch, pose_pairs as gp_lm_graph_create; batch may be NULL: a pure pose graph) and num_pose_factors pose factors over the same
+ * num_poses poses.  Records: the batch's at [0, F), the pose factors' at [F, F + num_pose_factors) in the caller's order (gp_lm_graph_records); the damped system
+ * covers all of them, c and new_error are the graph's error() (new_error: the VGICP errors in factor order, then the pose factors' in order, one host sum).
+ * try_lambda evaluates the pose factors at the trial values behind the retract (errors -- and, speculating, the records at the trial values -- in ONE launch) and keeps
+ * its one wait.  pose_fixed may be NULL (priors fix the gauge); stream: the graph's stream when batch is NULL, else NULL or the batch's own.  set_values of such a graph
+ * refuses values that are not orthonormal to 1e-9 (GP_ERROR_INVALID_ARGUMENT).  Refusals as gp_pose_factors_create, and a graph with no factor at all. */
+int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pose_pairs, const gp_pose_factor* pose_factors, int num_pose_factors, int num_poses,
+                                         const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out);
 
 /* the symbolic phase alone (pure host code, no device needed): elimination order perm[k] = slot eliminated k-th, elimination tree
  * parent[k] (-1 = root), block counts and the schedule; any output pointer may be NULL */
