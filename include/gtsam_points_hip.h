@@ -400,7 +400,13 @@ int gp_point_grid_destroy(gp_point_grid_t* grid);
 int gp_knn_search(const gp_point_grid_t* grid, const float* queries_dev, int num_queries, int k, double max_sq_dist, int* indices_dev, double* sq_dists_dev,
                   int* num_found_dev, gp_stream_t stream);
 /* estimate_covariances(points, n, k): k-NN incl. the query -> sample covariance -> V diag(1e-3,1,1) V^-1; fewer than k -> identity.
- * covs_dev float[n][9] column-major; cell_size <= 0 picks 0.25 m; *num_short = points with < k neighbours. Synchronous. */
+ * covs_dev float[n][9] column-major; cell_size <= 0 picks 0.25 m; *num_short = points with < k neighbours. Synchronous.
+ * How far an output is determined (tests/knn_ref.py holds every point to it): with l1 <= l2 <= l3 the eigenvalues of the sample covariance and
+ * relgap = (l2 - l1) / l3, the output agrees with I - 0.999 v v^T (v: eigenvector of l1) to 1.5e-7 + 5.6e-7 / relgap in relative Frobenius norm.  Below
+ * relgap 1e-6 -- collinear neighbours, and EVERY point at k = 2, whose sample covariance is rank one -- v is some unit vector of the plane of the two
+ * smallest eigenvectors: which one is decided by the rounding noise of the uncentred sums, here as in the reference, so two correct implementations agree
+ * there only as far as their roundings do.  The eigenvalues of the output are (1e-3, 1, 1) to 1e-5 always.  k = 1 gives diag(1e-3, 1, 1) exactly.  Among
+ * neighbours at exactly the same distance at rank k either may be taken. */
 int gp_estimate_covariances(const float* points_dev, int num_points, int k, double cell_size, float* covs_dev, int* num_short, gp_stream_t stream);
 /* as above with a GP_TUNE_KNN_STRUCTURE value and (measurement) a device buffer of 8 work counters or NULL, see gp_point_grid_create_ex */
 int gp_estimate_covariances_ex(const float* points_dev, int num_points, int k, double cell_size, float* covs_dev, int* num_short, int structure,

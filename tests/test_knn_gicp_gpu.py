@@ -3,6 +3,7 @@
 import numpy as np
 import pytest
 
+import knn_ref
 import oracle
 from helpers import BLOCKS, assert_linearized_close, expmap
 
@@ -53,6 +54,7 @@ def test_covariances_match_oracle(gpu, kitti00):
     assert (rel < 1e-5).mean() > 0.995
     w = np.linalg.eigvalsh(0.5 * (got + got.transpose(0, 2, 1)))
     np.testing.assert_allclose(np.median(w, 0), [1e-3, 1.0, 1.0], atol=1e-5)
+    knn_ref.assert_covariances(p, 10, got, what="gpu kitti00_dec8 source")  # every point: bound by its own relgap, eigenvalues, ties by rule
     # too few points for k neighbours -> identity + count (covariance_estimation.cpp:27-31)
     tiny = gpu.PointCloudGPU(p[:5])
     assert gpu.estimate_covariances_gpu(tiny, 10) == 5
@@ -122,6 +124,7 @@ def test_binned_and_hashed_structures_agree(gpu, kitti00):
         fr0 = gpu.PointCloudGPU(p)
         assert gpu.estimate_covariances_gpu(fr0, 10, structure=mode) == 0
         covs.append(fr0.download("covs").astype(np.float64))
+        knn_ref.assert_covariances(p, 10, covs[-1], what=f"gpu structure {mode} kitti00_dec8 target")
     for other in covs[1:]:
         rel = np.linalg.norm((covs[0] - other).reshape(len(p), -1), axis=1) / np.linalg.norm(other.reshape(len(p), -1), axis=1)
         assert (rel < 1e-5).mean() > 0.999, (rel < 1e-5).mean()  # all but the neighbourhoods with exact distance ties at rank k
@@ -161,6 +164,7 @@ def test_sparse_neighbourhoods_go_through_the_cooperative_pass(gpu, kitti00):
         got[structure] = fr.download("covs")
         rel = _cov_rel(got[structure], ref)
         assert np.median(rel) < 2e-7 and (rel < 1e-5).mean() > 0.995, (structure, np.median(rel), (rel < 1e-5).mean())
+        knn_ref.assert_covariances(cloud, 10, got[structure], what=f"gpu structure {structure} sparse slab")
     rel07 = _cov_rel(got[0], got[7])
     assert (rel07 < 1e-6).mean() > 0.999, (rel07 < 1e-6).mean()  # the same neighbour sets (exact ties at rank k aside)
     # a real scan: near field through the per-lane search, far field through the cooperative pass -- against round 4's search
@@ -169,6 +173,7 @@ def test_sparse_neighbourhoods_go_through_the_cooperative_pass(gpu, kitti00):
         fr = gpu.PointCloudGPU(kitti00["target_points"])
         assert gpu.estimate_covariances_gpu(fr, 10, structure=structure) == 0
         res[structure] = fr.download("covs")
+        knn_ref.assert_covariances(kitti00["target_points"], 10, res[structure], what=f"gpu structure {structure} kitti00_dec8 target")
     rel = _cov_rel(res[0], res[7])
     assert (rel < 1e-6).mean() > 0.999, (rel < 1e-6).mean()
     # k below the list size, and a cloud with fewer than k points in reach of the cooperative pass
@@ -178,6 +183,7 @@ def test_sparse_neighbourhoods_go_through_the_cooperative_pass(gpu, kitti00):
         refk, _ = oracle.estimate_covariances(cloud, k, 4)
         relk = _cov_rel(fr.download("covs"), refk)
         assert np.median(relk) < 2e-7 and (relk < 1e-5).mean() > 0.99, (k, np.median(relk))
+        knn_ref.assert_covariances(cloud, k, fr.download("covs"), what="gpu structure 0 sparse slab")
     few = gpu.PointCloudGPU(cloud[:7])
     assert gpu.estimate_covariances_gpu(few, 10) == 7
     np.testing.assert_array_equal(few.download("covs")[3], np.eye(3, dtype=np.float32))
@@ -204,6 +210,7 @@ def test_cooperative_pass_with_duplicate_points_and_clusters(gpu):
         # (degenerate neighbourhoods -- a point and its two copies among the ten: rank-deficient sample covariances, where the eigenvector of the reference's closed form is
         # itself arbitrary -- are excluded by the same 1e-5 / fraction rule as test_covariances_match_oracle)
         assert np.median(rel) < 1e-6 and (rel < 1e-5).mean() > 0.9, (structure, np.median(rel), (rel < 1e-5).mean())
+        knn_ref.assert_covariances(cloud, 10, fr.download("covs"), what=f"gpu structure {structure} duplicates and clusters")
 
 
 def test_cooperative_pass_skips_empty_shells_and_finds_what_lies_behind_them(gpu):
@@ -230,6 +237,7 @@ def test_cooperative_pass_skips_empty_shells_and_finds_what_lies_behind_them(gpu
         got[structure] = fr.download("covs")
         rel = _cov_rel(got[structure], ref)
         assert np.median(rel) < 1e-6 and (rel < 1e-5).mean() > 0.995, (structure, np.median(rel), (rel < 1e-5).mean())
+        knn_ref.assert_covariances(cloud, 10, got[structure], what=f"gpu structure {structure} wall and gap")
     lonely_idx = np.where(np.abs(cloud[:, 0] - 400.0 * np.round(cloud[:, 0] / 400.0)) < 8.0)[0]  # the points in front of the walls
     assert len(lonely_idx) == 7 * 7
     rel = _cov_rel(got[0][lonely_idx], ref[lonely_idx])
