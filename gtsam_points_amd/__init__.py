@@ -18,7 +18,7 @@ from .factors import (  # noqa: F401
     create_nonlinear_factor_set_gpu,
     pose_inverse,
 )
-from .features import IntegratedGICPFactorGPU, KdTreeGPU, estimate_covariances_gpu  # noqa: F401
+from .features import IntegratedGICPFactorGPU, KdTreeGPU, estimate_covariances_gpu, estimate_normals_covariances_gpu, estimate_normals_gpu  # noqa: F401
 from .solver import (  # noqa: F401
     BetweenFactorPose3,
     DenseLinearSystemGPU,
@@ -39,6 +39,8 @@ __all__ = [
     "IntegratedVGICPFactorGPU",
     "KdTreeGPU",
     "estimate_covariances_gpu",
+    "estimate_normals_gpu",
+    "estimate_normals_covariances_gpu",
     "LinearizationHook",
     "LinearizedSystem6",
     "NonlinearFactorGPU",

@@ -16,6 +16,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 #include <vector>
 
 #include "gp_binning.hpp"
@@ -871,12 +872,31 @@ __device__ __forceinline__ void knn_query_any(const SearchView& g, double qx, do
 }
 
 // non-finite points have no neighbours: identity covariance, counted as "short" (covariance_estimation.cpp:27-31)
-__global__ void __launch_bounds__(256) nonfinite_identity_kernel(const float* __restrict__ points, int n, float* __restrict__ covs, int* __restrict__ num_short) {
+// NORMALS (estimate_normals, features/normal_estimation.cpp:18-50): the identity's eigenbasis is the identity (computeDirect's triple root), so the normal is
+// (1, 0, 0), turned round when p . n = p.x > 1 (:26).  covs may be null then (the normals-only call).
+template <bool NORMALS>
+__device__ __forceinline__ void store_identity(float qx, float* __restrict__ cov_out, float* __restrict__ normal_out) {
+  if constexpr (NORMALS) {
+    normal_out[0] = qx > 1.0f ? -1.0f : 1.0f;
+    normal_out[1] = 0.0f;
+    normal_out[2] = 0.0f;
+    if (!cov_out) return;
+  }
+  for (int j = 0; j < 9; j++) cov_out[j] = (j % 4 == 0) ? 1.0f : 0.0f;
+}
+
+template <bool NORMALS = false>
+__global__ void __launch_bounds__(256) nonfinite_identity_kernel(const float* __restrict__ points, int n, float* __restrict__ covs, int* __restrict__ num_short,
+                                                                 float* __restrict__ normals = nullptr) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
   if (fabsf(x) < 3.0e38f && fabsf(y) < 3.0e38f && fabsf(z) < 3.0e38f) return;
-  for (int j = 0; j < 9; j++) covs[9 * (size_t)i + j] = (j % 4 == 0) ? 1.0f : 0.0f;
+  if constexpr (NORMALS) {
+    store_identity<true>(x, covs ? covs + 9 * (size_t)i : nullptr, normals + 3 * (size_t)i);
+  } else {
+    for (int j = 0; j < 9; j++) covs[9 * (size_t)i + j] = (j % 4 == 0) ? 1.0f : 0.0f;
+  }
   atomicAdd(num_short, 1);
 }
 
@@ -962,6 +982,11 @@ __device__ __forceinline__ void eig3_extract_kernel(const double* mat, double* r
   }
 }
 
+// STATIC_COLUMNS: the column logic a second time, with COMPILE-TIME column numbers (k, l) = (2, 0) or (0, 2).  The default indexes evecs with run-time k / l,
+// which sends the array to memory: the search kernels hold it in the scratch they have anyway, but a kernel with none of its own (normals_from_covs_kernel)
+// would get 72 B per lane of LDS for it.  A second copy rather than one shared form: routing the default through the shared form changes the register
+// allocation of the shipped covariance kernels, which are held to their figures.
+template <bool STATIC_COLUMNS = false>
 __device__ __forceinline__ void eig3_direct(const double* mat /*col-major, lower triangle referenced*/, double* evals, double* evecs) {
   const double eps = 2.220446049250313e-16;
   const double shift = (mat[0] + mat[4] + mat[8]) / 3.0;
@@ -974,34 +999,65 @@ __device__ __forceinline__ void eig3_direct(const double* mat /*col-major, lower
   if ((evals[2] - evals[0]) <= eps) {
     for (int i = 0; i < 9; i++) evecs[i] = (i % 4 == 0) ? 1.0 : 0.0;
   } else {
-    double tmp[9];
-    for (int i = 0; i < 9; i++) tmp[i] = scaled[i];
-    double d0 = evals[2] - evals[1];
-    const double d1 = evals[1] - evals[0];
-    int k = 0, l = 2;
-    if (d0 > d1) {
-      k = 2;
-      l = 0;
-      d0 = d1;
-    }
-    tmp[0] -= evals[k];
-    tmp[4] -= evals[k];
-    tmp[8] -= evals[k];
-    eig3_extract_kernel(tmp, evecs + 3 * k, evecs + 3 * l);
-    if (d0 <= 2.0 * eps * d1) {
-      double* ck = evecs + 3 * k;
-      double* cl = evecs + 3 * l;
-      const double dot = ck[0] * cl[0] + ck[1] * cl[1] + ck[2] * cl[2];
-      for (int r = 0; r < 3; r++) cl[r] -= dot * cl[r];
-      const double nn = sqrt(cl[0] * cl[0] + cl[1] * cl[1] + cl[2] * cl[2]);
-      for (int r = 0; r < 3; r++) cl[r] /= nn;
-    } else {
-      double dummy[3];
+    if constexpr (STATIC_COLUMNS) {
+      double tmp[9];
       for (int i = 0; i < 9; i++) tmp[i] = scaled[i];
-      tmp[0] -= evals[l];
-      tmp[4] -= evals[l];
-      tmp[8] -= evals[l];
-      eig3_extract_kernel(tmp, evecs + 3 * l, dummy);
+      const double d0 = evals[2] - evals[1], d1 = evals[1] - evals[0];
+      auto columns = [&](auto k, auto l, double d0) {  // (k, l: std::integral_constant)
+        tmp[0] -= evals[k];
+        tmp[4] -= evals[k];
+        tmp[8] -= evals[k];
+        eig3_extract_kernel(tmp, evecs + 3 * k, evecs + 3 * l);
+        if (d0 <= 2.0 * eps * d1) {
+          double* ck = evecs + 3 * k;
+          double* cl = evecs + 3 * l;
+          const double dot = ck[0] * cl[0] + ck[1] * cl[1] + ck[2] * cl[2];
+          for (int r = 0; r < 3; r++) cl[r] -= dot * cl[r];
+          const double nn = sqrt(cl[0] * cl[0] + cl[1] * cl[1] + cl[2] * cl[2]);
+          for (int r = 0; r < 3; r++) cl[r] /= nn;
+        } else {
+          double dummy[3];
+          for (int i = 0; i < 9; i++) tmp[i] = scaled[i];
+          tmp[0] -= evals[l];
+          tmp[4] -= evals[l];
+          tmp[8] -= evals[l];
+          eig3_extract_kernel(tmp, evecs + 3 * l, dummy);
+        }
+      };
+      if (d0 > d1)
+        columns(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, d1);
+      else
+        columns(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, d0);
+    } else {
+      double tmp[9];
+      for (int i = 0; i < 9; i++) tmp[i] = scaled[i];
+      double d0 = evals[2] - evals[1];
+      const double d1 = evals[1] - evals[0];
+      int k = 0, l = 2;
+      if (d0 > d1) {
+        k = 2;
+        l = 0;
+        d0 = d1;
+      }
+      tmp[0] -= evals[k];
+      tmp[4] -= evals[k];
+      tmp[8] -= evals[k];
+      eig3_extract_kernel(tmp, evecs + 3 * k, evecs + 3 * l);
+      if (d0 <= 2.0 * eps * d1) {
+        double* ck = evecs + 3 * k;
+        double* cl = evecs + 3 * l;
+        const double dot = ck[0] * cl[0] + ck[1] * cl[1] + ck[2] * cl[2];
+        for (int r = 0; r < 3; r++) cl[r] -= dot * cl[r];
+        const double nn = sqrt(cl[0] * cl[0] + cl[1] * cl[1] + cl[2] * cl[2]);
+        for (int r = 0; r < 3; r++) cl[r] /= nn;
+      } else {
+        double dummy[3];
+        for (int i = 0; i < 9; i++) tmp[i] = scaled[i];
+        tmp[0] -= evals[l];
+        tmp[4] -= evals[l];
+        tmp[8] -= evals[l];
+        eig3_extract_kernel(tmp, evecs + 3 * l, dummy);
+      }
     }
     const double* c2 = evecs + 6;
     const double* c0 = evecs;
@@ -1030,8 +1086,18 @@ __device__ __forceinline__ void inverse3_general(const double* a /*col-major*/, 
 // estimate_covariances (features/covariance_estimation.cpp:18-77): k-NN (query included) -> sample covariance ->
 // V diag(1e-3, 1, 1) V^-1.  Fewer than k neighbours -> identity (:27-31).
 // sample covariance of the k neighbours -> V diag(1e-3, 1, 1) V^-1 (features/covariance_estimation.cpp:33-53)
-template <int KMAX, bool FULL>
-__device__ __forceinline__ void covariance_from_neighbours(const TopK<KMAX, FULL>& top, const float* __restrict__ points, int k, float* __restrict__ out) {
+// NORMALS: the first eigenvector IS estimate_normals(points, n, k)'s normal (features/normal_estimation.cpp:52-55: the eigenvector of the smallest eigenvalue of
+// V diag(1e-3, 1, 1) V^-1 is V's first column), stored beside the covariance, or instead of it when out == nullptr (then no inverse and no V L V^-1 products)
+__device__ __forceinline__ void store_normal(const double* v, double qx, double qy, double qz, float* __restrict__ normal_out) {
+  const bool away = qx * v[0] + qy * v[1] + qz * v[2] > 1.0;  // :26, points in the sensor frame
+  normal_out[0] = (float)(away ? -v[0] : v[0]);
+  normal_out[1] = (float)(away ? -v[1] : v[1]);
+  normal_out[2] = (float)(away ? -v[2] : v[2]);
+}
+
+template <int KMAX, bool FULL, bool NORMALS = false>
+__device__ __forceinline__ void covariance_from_neighbours(const TopK<KMAX, FULL>& top, const float* __restrict__ points, int k, float* __restrict__ out,
+                                                           float* __restrict__ normal_out = nullptr, double qx = 0.0, double qy = 0.0, double qz = 0.0) {
   double sp[3] = {0, 0, 0}, spp[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
   for (int j = 0; j < KMAX; j++)
@@ -1047,6 +1113,10 @@ __device__ __forceinline__ void covariance_from_neighbours(const TopK<KMAX, FULL
     for (int r = 0; r < 3; r++) cov[c * 3 + r] = (spp[c * 3 + r] - (sp[r] / (double)k) * sp[c]) / (double)k;  // :43
   double evals[3], V[9], Vinv[9];
   eig3_direct(cov, evals, V);
+  if constexpr (NORMALS) {
+    store_normal(V, qx, qy, qz, normal_out);
+    if (!out) return;
+  }
   inverse3_general(V, Vinv);
   const double lam[3] = {1e-3, 1.0, 1.0};
   for (int c = 0; c < 3; c++)
@@ -1055,6 +1125,19 @@ __device__ __forceinline__ void covariance_from_neighbours(const TopK<KMAX, FULL
       for (int kk = 0; kk < 3; kk++) s += V[kk * 3 + r] * lam[kk] * Vinv[c * 3 + kk];
       out[c * 3 + r] = (float)s;
     }
+}
+
+// estimate_normals(points, covs, n) (features/normal_estimation.cpp:18-50): the eigenvector of the smallest eigenvalue of a GIVEN covariance (column-major; the
+// lower triangle is read, as computeDirect reads it), turned by the sign rule.  One lane per point, f64 arithmetic, one rounding at the store.
+__global__ void __launch_bounds__(256) normals_from_covs_kernel(const float* __restrict__ points, const float* __restrict__ covs, int n, float* __restrict__ normals) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* c = covs + 9 * (size_t)i;
+  const double c10 = (double)c[1], c20 = (double)c[2], c21 = (double)c[5];
+  const double m[9] = {(double)c[0], c10, c20, c10, (double)c[4], c21, c20, c21, (double)c[8]};
+  double evals[3], V[9];
+  eig3_direct<true>(m, evals, V);
+  store_normal(V, (double)points[3 * (size_t)i], (double)points[3 * (size_t)i + 1], (double)points[3 * (size_t)i + 2], normals + 3 * (size_t)i);
 }
 
 // Heavy queries first (round 4).  A query whose own cell holds fewer than k points cannot settle in shell 0: it walks shell 1 at least -- 26 more cells, dense ones
@@ -1121,11 +1204,12 @@ struct FarGroupLds {
   int count;
   int pad_[3];
 };
-template <int KMAX>
+template <int KMAX, bool NORMALS = false>
 // (four waves per SIMD = 128 registers, 560 B of scratch per lane: uncapped -- 256 registers, no scratch -- the kernel is 20 % faster ALONE (190 vs 240 us), but beside the
 // other launch, whose waves hold a quarter of a SIMD's registers each, a 256-register wave waits until two of them on one SIMD have retired: profiles/r05_c5_summary.txt)
 __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) covariance_far_kernel(BinGridView g, const float* __restrict__ points, int k, float* __restrict__ covs, int* __restrict__ num_short,
-                                                             const int* __restrict__ far_list, const float* __restrict__ far_bound, const int* __restrict__ far_count) {
+                                                             const int* __restrict__ far_list, const float* __restrict__ far_bound, const int* __restrict__ far_count,
+                                                             float* __restrict__ normals = nullptr) {
   constexpr int kGroups = 64 / kFarLanes;
   // these few waves are chains of dependent round trips with short bursts of arithmetic in between, and they run beside the other launch's waves (four per SIMD, busy
   // with list insertions): at equal issue priority every burst takes four times as long -- the kernel measured 350 us beside the light queries' launch, 190 alone
@@ -1427,16 +1511,17 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
     if (fl && sub == 0) fl[3] = __builtin_amdgcn_s_memrealtime(), fl[4] = far_cands;
 #endif
     if (active && sub == 0) {
-      float* out = covs + 9 * (size_t)i;
+      float* out = (!NORMALS || covs) ? covs + 9 * (size_t)i : nullptr;
+      float* nout = NORMALS ? normals + 3 * (size_t)i : nullptr;
       if (have < k) {
         atomicAdd(num_short, 1);
-        for (int j = 0; j < 9; j++) out[j] = (j % 4 == 0) ? 1.0f : 0.0f;
+        store_identity<NORMALS>(self.x, out, nout);
       } else {
         TopK<KMAX, false> fin;
         fin.init(k, kInf);
 #pragma unroll
         for (int r = 0; r < KMAX; r++) fin.idx[r] = fin_i[r];
-        covariance_from_neighbours<KMAX, false>(fin, points, k, out);
+        covariance_from_neighbours<KMAX, false, NORMALS>(fin, points, k, out, nout, qx, qy, qz);
       }
     }
   }
@@ -1444,11 +1529,11 @@ __global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4)))
 
 // far_list / far_count (optional): queries whose neighbourhood is sparse (knn_query_bins, `sparse`) are not searched lane by lane -- one lane walking hundreds of
 // empty blocks holds its 63 neighbours for 400-600 us, the launch's tail (profiles/r05_c5_wavelog_near_first.txt) -- but appended here for covariance_far_kernel
-template <int KMAX, int MIN_WAVES = 1, bool FULL = false>
+template <int KMAX, int MIN_WAVES = 1, bool FULL = false, bool NORMALS = false>
 __global__ void __launch_bounds__(128, MIN_WAVES) covariance_kernel(SearchView g, const float* __restrict__ points, int n, int k, float* __restrict__ covs,
                                                          int* __restrict__ num_short, const int* __restrict__ todo_list, const int* __restrict__ todo_count,
                                                          int* __restrict__ far_list = nullptr, int* __restrict__ far_count = nullptr, float* __restrict__ far_bound = nullptr,
-                                                         const int* __restrict__ todo_begin = nullptr) {
+                                                         const int* __restrict__ todo_begin = nullptr, float* __restrict__ normals = nullptr) {
   int t = blockIdx.x * 128 + threadIdx.x;
   if (todo_list) {  // positions [*todo_begin, *todo_count) of the list (round 5: the heavy part and the rest are two launches on two streams)
     if (todo_begin) t += *todo_begin;
@@ -1487,13 +1572,14 @@ __global__ void __launch_bounds__(128, MIN_WAVES) covariance_kernel(SearchView g
     }
     if (sparse) return;
   }
-  float* out = covs + 9 * (size_t)i;
+  float* out = (!NORMALS || covs) ? covs + 9 * (size_t)i : nullptr;
+  float* nout = NORMALS ? normals + 3 * (size_t)i : nullptr;
   if (top.count() < k) {
     atomicAdd(num_short, 1);
-    for (int j = 0; j < 9; j++) out[j] = (j % 4 == 0) ? 1.0f : 0.0f;
+    store_identity<NORMALS>(self.x, out, nout);
     return;
   }
-  covariance_from_neighbours<KMAX, FULL>(top, points, k, out);
+  covariance_from_neighbours<KMAX, FULL, NORMALS>(top, points, k, out, nout, qx, qy, qz);
 #ifdef GP_KNN_WAVELOG
   if (g.binned && g.bins[0].counters && (threadIdx.x & 63) == 0) {
     unsigned long long* wl = g.bins[0].counters + 8 + 8 * (size_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -1720,9 +1806,10 @@ __global__ void __launch_bounds__(kRowThreads) covariance_rows_kernel(BinGridVie
 // rounding -- everything that was filtered out has an f32 distance >= that, i.e. a true distance >= bound * (1 - 1e-5), so it cannot
 // belong to the k nearest -- and (ii) it is no larger than the distance to the region's border, so nothing outside the region can
 // either.  The rest is listed for the per-lane search.
-template <int KMAX>
+template <int KMAX, bool NORMALS = false>
 __global__ void __launch_bounds__(128) covariance_settle_kernel(const float4* __restrict__ sorted, RowScanOut in, const float* __restrict__ points, int k,
-                                                                float* __restrict__ covs, int* __restrict__ todo_list, int* __restrict__ todo_count) {
+                                                                float* __restrict__ covs, int* __restrict__ todo_list, int* __restrict__ todo_count,
+                                                                float* __restrict__ normals = nullptr) {
   static_assert(KMAX + 2 <= kTileKeep, "two entries of slack");
   const int pos = blockIdx.x * 128 + threadIdx.x;
   const bool active = pos < in.nq;
@@ -1749,7 +1836,8 @@ __global__ void __launch_bounds__(128) covariance_settle_kernel(const float4* __
       const double safe = (double)in.safe[pos];
       const bool separated = exact.worst() <= (double)bound * (1.0 - 1.0e-5);
       if (exact.found >= k && separated && exact.worst() <= safe * safe) {
-        covariance_from_neighbours<KMAX>(exact, points, k, covs + 9 * (size_t)__float_as_int(self.w));
+        const size_t i = (size_t)__float_as_int(self.w);
+        covariance_from_neighbours<KMAX, false, NORMALS>(exact, points, k, (!NORMALS || covs) ? covs + 9 * i : nullptr, NORMALS ? normals + 3 * i : nullptr, q[0], q[1], q[2]);
         leftover = false;
       }
     }
@@ -2368,9 +2456,11 @@ int gp_estimate_covariances(const float* points_dev, int n, int k, double cell_s
   return gp_estimate_covariances_ex(points_dev, n, k, cell_size, covs_dev, num_short, 0, nullptr, stream);
 }
 
-int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cell_size, float* covs_dev, int* num_short, int structure, unsigned long long* counters_dev,
-                               gp_stream_t stream) {
-  if (!points_dev || n < 0 || k <= 0 || k > 32 || !covs_dev) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_estimate_covariances: bad arguments (1 <= k <= 32)");
+// One search, the covariances (NORMALS = false: gp_estimate_covariances, the kernels as they always were) or the normals and / or the covariances (NORMALS = true:
+// gp_estimate_normals_covariances; covs_dev may be null).  The flag is a template parameter of every kernel behind it: the covariance call keeps its registers.
+extern "C++" template <bool NORMALS>
+static int estimate_covariances_impl(const float* points_dev, int n, int k, double cell_size, float* covs_dev, float* normals_dev, int* num_short, int structure,
+                                     unsigned long long* counters_dev, gp_stream_t stream) {
   if (num_short) *num_short = 0;
   if (n == 0) return GP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -2390,7 +2480,7 @@ int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cel
     if (!zeroed) (void)hipMemsetAsync(d_short.ptr, 0, zero_bytes, s);
     const gp::SearchView v = g->view();
     const int nq = g->binned ? g->num_binned : n;  // queries = the cell-sorted points; non-finite points are not among them
-    if (nq < n) hipLaunchKernelGGL(gp::nonfinite_identity_kernel, dim3((n + 255) / 256), dim3(256), 0, s, points_dev, n, covs_dev, d_short.as<int>());
+    if (nq < n) hipLaunchKernelGGL(gp::nonfinite_identity_kernel<NORMALS>, dim3((n + 255) / 256), dim3(256), 0, s, points_dev, n, covs_dev, d_short.as<int>(), normals_dev);
     const dim3 grid((nq + 127) / 128), block(128);
     gp::DeviceArray todo;  // [nq] positions + the count behind them
     gp::DeviceArray scan_buf;  // RowScanOut: kept [kTileKeep][nq] | bound [nq] | safe [nq]
@@ -2405,7 +2495,8 @@ int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cel
                                   reinterpret_cast<float*>(scan_buf.as<int>() + (size_t)(gp::kTileKeep + 1) * nq), nq};
         hipLaunchKernelGGL(gp::covariance_rows_kernel, dim3(16u * (unsigned)g->bin_levels[0]->bins.num_occ_blocks), dim3(gp::kRowThreads), 0, s, v.bins[0],
                            (const int*)g->bin_levels[0]->bins.occ_blocks.as<int>(), scan, 0);
-        hipLaunchKernelGGL(gp::covariance_settle_kernel<10>, grid, block, 0, s, v.bins[0].sorted, scan, points_dev, k, covs_dev, todo.as<int>(), todo.as<int>() + nq);
+        hipLaunchKernelGGL((gp::covariance_settle_kernel<10, NORMALS>), grid, block, 0, s, v.bins[0].sorted, scan, points_dev, k, covs_dev, todo.as<int>(), todo.as<int>() + nq,
+                           normals_dev);
         d_todo = todo.as<int>();
       }
     }
@@ -2446,34 +2537,34 @@ int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cel
         // launch's waves.  Both cover the whole order with their grids and leave by the counts on the device (the split is not known to the host).
         const int* d_heavy = d_todo + nq + 1;
         bool forked = hipEventRecord(side.fork, s) == hipSuccess && hipStreamWaitEvent(side.stream, side.fork, 0) == hipSuccess;
-        hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_heavy, d_far, d_far_count, d_far_bound,
-                           (const int*)nullptr);
-        hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true>), grid, block, 0, forked ? side.stream : s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count,
-                           (int*)nullptr, (int*)nullptr, (float*)nullptr, d_heavy);
+        hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true, NORMALS>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_heavy, d_far, d_far_count, d_far_bound,
+                           (const int*)nullptr, normals_dev);
+        hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true, NORMALS>), grid, block, 0, forked ? side.stream : s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count,
+                           (int*)nullptr, (int*)nullptr, (float*)nullptr, d_heavy, normals_dev);
         const unsigned far_wgs = (unsigned)std::min<long long>(((long long)nq + 3) / 4, 8192);  // one wave = four queries per workgroup
-        hipLaunchKernelGGL(gp::covariance_far_kernel<10>, dim3(far_wgs), dim3(64), 0, s, v.bins[0], points_dev, k, covs_dev, d_short.as<int>(), (const int*)d_far, (const float*)d_far_bound,
-                           (const int*)d_far_count);
+        hipLaunchKernelGGL((gp::covariance_far_kernel<10, NORMALS>), dim3(far_wgs), dim3(64), 0, s, v.bins[0], points_dev, k, covs_dev, d_short.as<int>(), (const int*)d_far, (const float*)d_far_bound,
+                           (const int*)d_far_count, normals_dev);
         if (forked && (hipEventRecord(side.join, side.stream) != hipSuccess || hipStreamWaitEvent(s, side.join, 0) != hipSuccess)) {
           (void)hipStreamSynchronize(side.stream);  // (the join could not be queued: wait for the side stream here, the call is synchronous anyway)
         }
       } else {
         if (k == 10 && cov_waves == 4 && cov_full)  // (capped at 96 registers for five waves per SIMD: 41 spilled, 1.08 vs 1.07 ms -- no gain)
-          hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
-                             (const int*)nullptr);
+          hipLaunchKernelGGL((gp::covariance_kernel<10, 4, true, NORMALS>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
+                             (const int*)nullptr, normals_dev);
         else if (k <= 10 && cov_waves == 4)
-          hipLaunchKernelGGL((gp::covariance_kernel<10, 4>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
-                             (const int*)nullptr);
+          hipLaunchKernelGGL((gp::covariance_kernel<10, 4, false, NORMALS>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
+                             (const int*)nullptr, normals_dev);
         else if (k <= 10)
-          hipLaunchKernelGGL((gp::covariance_kernel<10, 1>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
-                             (const int*)nullptr);
+          hipLaunchKernelGGL((gp::covariance_kernel<10, 1, false, NORMALS>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, d_far, d_far_count, d_far_bound,
+                             (const int*)nullptr, normals_dev);
         else
-          hipLaunchKernelGGL(gp::covariance_kernel<32>, grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, (int*)nullptr, (int*)nullptr, (float*)nullptr,
-                             (const int*)nullptr);
+          hipLaunchKernelGGL((gp::covariance_kernel<32, 1, false, NORMALS>), grid, block, 0, s, v, points_dev, nq, k, covs_dev, d_short.as<int>(), d_todo, d_count, (int*)nullptr, (int*)nullptr, (float*)nullptr,
+                             (const int*)nullptr, normals_dev);
         if (d_far) {
           // a fixed grid (the count stays on the device): 4 waves per workgroup, 4 queries per wave, every group of 16 lanes takes queries w, w + groups, ... of the list
           const unsigned far_wgs = (unsigned)std::min<long long>(((long long)nq + 3) / 4, 8192);
-          hipLaunchKernelGGL(gp::covariance_far_kernel<10>, dim3(far_wgs), dim3(64), 0, s, v.bins[0], points_dev, k, covs_dev, d_short.as<int>(), (const int*)d_far, (const float*)d_far_bound,
-                             (const int*)d_far_count);
+          hipLaunchKernelGGL((gp::covariance_far_kernel<10, NORMALS>), dim3(far_wgs), dim3(64), 0, s, v.bins[0], points_dev, k, covs_dev, d_short.as<int>(), (const int*)d_far, (const float*)d_far_bound,
+                             (const int*)d_far_count, normals_dev);
         }
       }
     }
@@ -2502,6 +2593,28 @@ int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cel
   }
   delete g;
   return rc;
+}
+
+int gp_estimate_covariances_ex(const float* points_dev, int n, int k, double cell_size, float* covs_dev, int* num_short, int structure, unsigned long long* counters_dev,
+                               gp_stream_t stream) {
+  if (!points_dev || n < 0 || k <= 0 || k > 32 || !covs_dev) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_estimate_covariances: bad arguments (1 <= k <= 32)");
+  return estimate_covariances_impl<false>(points_dev, n, k, cell_size, covs_dev, nullptr, num_short, structure, counters_dev, stream);
+}
+
+int gp_estimate_normals_covariances(const float* points_dev, int n, int k, double cell_size, float* normals_dev, float* covs_dev, int* num_short, gp_stream_t stream) {
+  if (!points_dev || n < 0 || k <= 0 || k > 32 || (!normals_dev && !covs_dev))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_estimate_normals_covariances: bad arguments (1 <= k <= 32, normals_dev and covs_dev not both null)");
+  if (!normals_dev) return estimate_covariances_impl<false>(points_dev, n, k, cell_size, covs_dev, nullptr, num_short, 0, nullptr, stream);
+  return estimate_covariances_impl<true>(points_dev, n, k, cell_size, covs_dev, normals_dev, num_short, 0, nullptr, stream);
+}
+
+// estimate_normals(points, covs, n) (features/normal_estimation.cpp:18-50): one lane per point, 48 B in and 12 B out
+int gp_estimate_normals_from_covs(const float* points_dev, const float* covs_dev, int n, float* normals_dev, gp_stream_t stream) {
+  if (!points_dev || !covs_dev || !normals_dev || n < 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_estimate_normals_from_covs: bad arguments");
+  if (n == 0) return GP_OK;
+  hipLaunchKernelGGL(gp::normals_from_covs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, points_dev, covs_dev, n, normals_dev);
+  GP_HIP(hipGetLastError());
+  return GP_OK;
 }
 
 // ---- GICP factor ----------------------------------------------------------------------------------------------------

@@ -2,6 +2,7 @@
 
   KdTreeGPU                 <- ann/kdtree.hpp / small_kdtree.hpp (exact k-NN; here a cell-sorted point grid)
   estimate_covariances_gpu  <- features/covariance_estimation.hpp:estimate_covariances(points, k=10)
+  estimate_normals_gpu      <- features/normal_estimation.hpp:estimate_normals(points, k=10); estimate_normals_covariances_gpu: both from one search
   IntegratedGICPFactorGPU   <- factors/integrated_gicp_factor.hpp (CPU-only upstream), same calc_delta / HessianFactor protocol
 """
 import ctypes as C
@@ -66,6 +67,54 @@ def estimate_covariances_gpu(frame: PointCloudGPU, k_neighbors=10, cell_size=0.0
     frame.covs_gpu = covs
     frame._host.pop("covs", None)  # the host copy (if any) described the previous covariances
     frame.generation += 1
+    return short.value
+
+
+def _replace_normals(frame, normals):
+    # a new tensor where the old one may be handed out again by torch's caching allocator: factors that cached the pointer re-read it on the generation bump
+    # (the packed stream mirror holds points and covariances only, so there is no mirror to forget)
+    frame.normals_gpu = normals
+    frame._host.pop("normals", None)  # the host copy (if any) described the previous normals
+    frame.generation += 1
+
+
+def estimate_normals_gpu(frame: PointCloudGPU, k_neighbors=10, cell_size=0.0, stream=None):
+    """estimate_normals(const PointCloud&, k) (features/normal_estimation.cpp:57-62): fills frame.normals_gpu (float [N][3]).  With frame.covs_gpu present the
+    normals are read off those covariances (returns 0); otherwise one k-NN search with the covariances left unwritten (returns the
+    number of points with < k neighbours)."""
+    import torch
+
+    lib = _capi.load()
+    normals = torch.empty((frame.size(), 3), dtype=torch.float32, device=frame.device)
+    GaussianVoxelMapGPU._sync_torch(frame)
+    short = C.c_int(0)
+    if frame.covs_gpu is not None:
+        _capi.check(lib.gp_estimate_normals_from_covs(frame.ptr(frame.points_gpu), frame.ptr(frame.covs_gpu), frame.size(), C.c_void_p(normals.data_ptr()), stream),
+                    "gp_estimate_normals_from_covs")
+        _capi.check(lib.gp_stream_synchronize(stream), "sync")  # (the C entry is asynchronous; the tensor is handed to torch and to factors on other streams)
+    else:
+        _capi.check(lib.gp_estimate_normals_covariances(frame.ptr(frame.points_gpu), frame.size(), int(k_neighbors), float(cell_size), C.c_void_p(normals.data_ptr()), None,
+                                                        C.byref(short), stream), "gp_estimate_normals_covariances")
+    _replace_normals(frame, normals)
+    return short.value
+
+
+def estimate_normals_covariances_gpu(frame: PointCloudGPU, k_neighbors=10, cell_size=0.0, stream=None):
+    """one k-NN search, both attributes: frame.covs_gpu as estimate_covariances_gpu writes it (bit for bit) and frame.normals_gpu as estimate_normals(points, n, k);
+    returns the number of points with < k neighbours."""
+    import torch
+
+    lib = _capi.load()
+    normals = torch.empty((frame.size(), 3), dtype=torch.float32, device=frame.device)
+    covs = torch.empty((frame.size(), 9), dtype=torch.float32, device=frame.device)
+    GaussianVoxelMapGPU._sync_torch(frame)
+    short = C.c_int(0)
+    _capi.check(lib.gp_estimate_normals_covariances(frame.ptr(frame.points_gpu), frame.size(), int(k_neighbors), float(cell_size), C.c_void_p(normals.data_ptr()),
+                                                    C.c_void_p(covs.data_ptr()), C.byref(short), stream), "gp_estimate_normals_covariances")
+    frame._forget_mirrors("covs")  # as estimate_covariances_gpu: the old covariance block may be handed out again under a live packed mirror
+    frame.covs_gpu = covs
+    frame._host.pop("covs", None)
+    _replace_normals(frame, normals)
     return short.value
 
 

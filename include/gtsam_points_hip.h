@@ -411,6 +411,17 @@ int gp_estimate_covariances(const float* points_dev, int num_points, int k, doub
 /* as above with a GP_TUNE_KNN_STRUCTURE value and (measurement) a device buffer of 8 work counters or NULL, see gp_point_grid_create_ex */
 int gp_estimate_covariances_ex(const float* points_dev, int num_points, int k, double cell_size, float* covs_dev, int* num_short, int structure,
                                unsigned long long* counters_dev, gp_stream_t stream);
+/* estimate_normals(points, covs, n), features/normal_estimation.cpp:18-50: n_i = the eigenvector of the smallest eigenvalue of covs_dev[i] (computeDirect, lower
+ * triangle), turned round when p_i . n_i > 1 (points in the sensor frame: towards the origin once the tangent plane passes more than 1 m from it).
+ * normals_dev float[n][3], f64 arithmetic rounded once at the store.  Within |p . n| <= 1 the sign is whatever the closed-form solver gives.  Asynchronous. */
+int gp_estimate_normals_from_covs(const float* points_dev, const float* covs_dev, int num_points, float* normals_dev, gp_stream_t stream);
+/* ONE k-NN search, both outputs: estimate_normals(points, n, k) (:52-55) and/or estimate_covariances.
+ * normals_dev / covs_dev: either may be NULL, not both.  cell_size, *num_short, synchronous: as gp_estimate_covariances.  covs_dev is bit-identical to what
+ * gp_estimate_covariances writes.  The normal is the eigenvector of the smallest eigenvalue of the sample covariance (which IS that of the regularised one),
+ * determined like the covariance: sin of the angle to the true one <= (1.5e-7 + 5.6e-7 / relgap) / (0.999 sqrt 2).  Fewer than k neighbours or a non-finite
+ * point: (+-1, 0, 0).  With normals_dev only, the V diag(1e-3,1,1) V^-1 products are skipped. */
+int gp_estimate_normals_covariances(const float* points_dev, int num_points, int k, double cell_size, float* normals_dev, float* covs_dev, int* num_short,
+                                    gp_stream_t stream);
 
 typedef struct gp_gicp_factor gp_gicp_factor_t;
 /* IntegratedGICPFactor(target, source) with its target 1-NN structure; max_correspondence_distance_sq defaults to 1.0 upstream (:30) */
