@@ -19,6 +19,7 @@ from .factors import (  # noqa: F401
     pose_inverse,
 )
 from .features import IntegratedGICPFactorGPU, KdTreeGPU, estimate_covariances_gpu, estimate_normals_covariances_gpu, estimate_normals_gpu  # noqa: F401
+from .sampling import VoxelGridPlan, randomgrid_sampling_gpu, sample_gpu, voxelgrid_sampling_gpu  # noqa: F401
 from .solver import (  # noqa: F401
     BetweenFactorPose3,
     DenseLinearSystemGPU,
@@ -51,6 +52,10 @@ __all__ = [
     "create_nonlinear_factor_set_gpu",
     "overlap_gpu",
     "merge_frames_gpu",
+    "VoxelGridPlan",
+    "sample_gpu",
+    "voxelgrid_sampling_gpu",
+    "randomgrid_sampling_gpu",
     "BetweenFactorPose3",
     "DenseLinearSystemGPU",
     "LevenbergMarquardtGraphGPU",

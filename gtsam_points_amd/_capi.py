@@ -190,6 +190,15 @@ _SIGNATURES = {
     "gp_gicp_factor_create_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_estimate_normals_from_covs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gp_estimate_normals_covariances": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    # voxelgrid_sampling / randomgrid_sampling / sample on the device (gp_sampling.hip)
+    "gp_voxelgrid_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_voxelgrid_plan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gp_voxelgrid_plan_average": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gp_voxelgrid_plan_random_indices": (C.c_int, [C.c_void_p, C.c_double, C.c_uint64, C.c_void_p, C.POINTER(C.c_int)]),
+    "gp_voxelgrid_plan_destroy": (C.c_int, [C.c_void_p]),
+    "gp_cloud_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "gp_debug_voxelgrid_hooks": (C.c_int, [C.c_int, C.c_int]),
+    "gp_debug_sample_hash": (C.c_uint, [C.c_uint64, C.c_uint]),
     # per-handle tuning (no process-global switches)
     "gp_vgicp_batch_set_tuning": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
     "gp_vgicp_batch_get_tuning": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int)]),

@@ -176,6 +176,68 @@ PointCloud::Ptr merge_frames_gpu(const std::vector<Eigen::Isometry3d>& poses, co
   return merged;
 }
 
+// ---- voxelgrid_sampling_gpu / randomgrid_sampling_gpu (point_cloud_cpu_funcs.cpp:119-295, 298-456; CPU-only upstream) ----------------------
+namespace {
+
+struct VoxelGridPlan {
+  gp_voxelgrid_plan_t* plan = nullptr;
+  int num_voxels = 0, num_dropped = 0;
+  VoxelGridPlan(const PointCloud::ConstPtr& frame, double resolution, CUstream_st* stream) {
+    make_sure_loaded_on_gpu(frame, stream);
+    check_error << gp_voxelgrid_plan_create(as_floats(frame->points_gpu), static_cast<int>(frame->size()), resolution, gp_stream(stream), &plan);
+    if (plan) check_error << gp_voxelgrid_plan_info(plan, &num_voxels, &num_dropped);
+  }
+  ~VoxelGridPlan() { check_error << gp_voxelgrid_plan_destroy(plan); }
+};
+
+// one output array per attribute the frame holds on the device; `fill` writes it
+template <typename Fill>
+PointCloud::Ptr sampled_cloud(const PointCloud::ConstPtr& frame, size_t rows, CUstream_st* stream, const Fill& fill) {
+  const float* src[5] = {as_floats(frame->points_gpu), as_floats(frame->covs_gpu), as_floats(frame->normals_gpu), frame->intensities_gpu, frame->times_gpu};
+  const int width[5] = {3, 9, 3, 1, 1};
+  float* dst[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+  for (int a = 0; a < 5; a++) {
+    if (!src[a]) continue;
+    void* p = nullptr;
+    check_error << gp_malloc(&p, sizeof(float) * width[a] * std::max<size_t>(rows, 1));
+    dst[a] = static_cast<float*>(p);
+    if (rows) fill(src[a], width[a], dst[a]);
+  }
+  check_error << gp_stream_synchronize(gp_stream(stream));
+  auto out = std::make_shared<PointCloudGPU>();
+  out->adopt(dst[0], dst[1], dst[2], dst[3], dst[4], rows);
+  out->download_attributes(stream);  // the CPU side as well, like merge_frames_gpu's result
+  return out;
+}
+
+}  // namespace
+
+PointCloud::Ptr voxelgrid_sampling_gpu(const PointCloud::ConstPtr& frame, double voxel_resolution, CUstream_st* stream, int* num_dropped) {
+  if (frame->size() == 0) return std::make_shared<PointCloudGPU>();  // :120-122
+  VoxelGridPlan vg(frame, voxel_resolution, stream);
+  if (num_dropped) *num_dropped = vg.num_dropped;
+  if (!vg.plan) return std::make_shared<PointCloudGPU>();
+  return sampled_cloud(frame, static_cast<size_t>(vg.num_voxels), stream,
+                       [&](const float* src, int width, float* dst) { check_error << gp_voxelgrid_plan_average(vg.plan, src, width, dst); });
+}
+
+PointCloud::Ptr randomgrid_sampling_gpu(const PointCloud::ConstPtr& frame, double voxel_resolution, double sampling_rate, std::uint64_t seed, CUstream_st* stream,
+                                        int* num_dropped) {
+  if (frame->size() == 0) return std::make_shared<PointCloudGPU>();
+  VoxelGridPlan vg(frame, voxel_resolution, stream);
+  if (num_dropped) *num_dropped = vg.num_dropped;
+  if (!vg.plan) return std::make_shared<PointCloudGPU>();
+  void* indices = nullptr;
+  int selected = 0;
+  check_error << gp_malloc(&indices, sizeof(int) * frame->size());
+  check_error << gp_voxelgrid_plan_random_indices(vg.plan, sampling_rate, seed, static_cast<int*>(indices), &selected);
+  auto out = sampled_cloud(frame, static_cast<size_t>(selected), stream, [&](const float* src, int width, float* dst) {
+    check_error << gp_cloud_gather(src, width, static_cast<const int*>(indices), selected, dst, gp_stream(stream));
+  });
+  check_error << gp_free(indices);
+  return out;
+}
+
 // ---- download_* ---------------------------------------------------------------------------------------------------------------------
 std::vector<VoxelBucket> download_buckets(const GaussianVoxelMapGPU& m, CUstream_st* stream) {
   return download_array<VoxelBucket>(m.buckets, (size_t)m.voxelmap_info.num_buckets, stream);

@@ -303,6 +303,16 @@ struct PointCloudGPU : public PointCloud, public OffloadableGPU {
     intensities_host.clear();
     generation++;
   }
+  // ... with every attribute (the device-side samplers hand their results over this way); a null array leaves that attribute absent
+  void adopt(float* points, float* covs, float* normals, float* intensities, float* times, size_t n) {
+    adopt(points, covs, intensities, n);
+    release(reinterpret_cast<void**>(&normals_gpu));
+    release(reinterpret_cast<void**>(&times_gpu));
+    normals_gpu = reinterpret_cast<Eigen::Vector3f*>(normals);
+    times_gpu = times;
+    normals_host.clear();
+    times_host.clear();
+  }
 
 private:
   std::vector<float> times_host, points_host, normals_host, covs_host, intensities_host;  // packed device-layout copies for reload_gpu()
@@ -367,5 +377,13 @@ std::vector<Eigen::Vector3f> download_points_gpu(const gtsam_points::PointCloud&
 std::vector<Eigen::Matrix3f> download_covs_gpu(const gtsam_points::PointCloud& frame, CUstream_st* stream = nullptr);
 std::vector<Eigen::Vector3f> download_normals_gpu(const gtsam_points::PointCloud& frame, CUstream_st* stream = nullptr);
 std::vector<float> download_intensities_gpu(const gtsam_points::PointCloud& frame, CUstream_st* stream = nullptr);
+
+// Device counterparts of voxelgrid_sampling / randomgrid_sampling (types/point_cloud_cpu.hpp:124-156; CPU-only upstream); defined in gtsam_points_hip_host.cpp over
+// gp_voxelgrid_plan_* / gp_cloud_gather.  The result is a PointCloudGPU with every attribute the frame holds on the device, device to device, and the same attributes
+// on the CPU side.  One row per occupied voxel in ascending (z, y, x) order; points without a voxel (non-finite, beyond +-2^20 voxels) are dropped and counted in
+// *num_dropped.  randomgrid_sampling_gpu takes a seed where the reference takes a std::mt19937: the selection is a counter-based hash of (seed, point index).
+PointCloud::Ptr voxelgrid_sampling_gpu(const PointCloud::ConstPtr& frame, double voxel_resolution, CUstream_st* stream = nullptr, int* num_dropped = nullptr);
+PointCloud::Ptr randomgrid_sampling_gpu(const PointCloud::ConstPtr& frame, double voxel_resolution, double sampling_rate, std::uint64_t seed = 0, CUstream_st* stream = nullptr,
+                                        int* num_dropped = nullptr);
 
 }  // namespace gtsam_points

@@ -608,6 +608,41 @@ int gp_pose_factors_compute_error(gp_pose_factors_t* pf, const double* poses_hos
 int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pose_pairs, const gp_pose_factor* pose_factors, int num_pose_factors, int num_poses,
                                          const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out);
 
+/* ---- voxelgrid_sampling / randomgrid_sampling / sample on the device (gp_sampling.hip) ----
+ * Device counterparts of types/point_cloud_cpu.hpp:110-156 (point_cloud_cpu_funcs.cpp:27-75, 119-295, 298-456; CPU-only upstream).
+ * A plan is built once per (cloud, resolution); any number of attribute reductions or index selections then run on it, on the plan's stream.
+ *   voxel      floor(double(p) * (1.0 / resolution)) per axis (:128,136).
+ *   dropped    a point that is not finite, or whose coordinate + 2^20 falls outside [0, 2^21 - 1] on some axis (:132-140): counted in num_dropped, in NO output
+ *              (the reference lumps such points under one invalid key and emits a NaN row for them; that row is not reproduced).
+ *   order      voxels are numbered in ascending order of the reference's packed key (z << 42 | y << 21 | x of the offset coordinates, :143-146), i.e.
+ *              lexicographically by (z, y, x) -- the order of the reference's single-threaded run; inside a voxel the points are in ascending point index.
+ *   one row per voxel: the reference cuts its sorted array into blocks of 1024 and emits a voxel that straddles a cut once per block (:188-206), an artefact of
+ *              its threading.  The device emits exactly one row per occupied voxel.
+ * plan_create waits once (for num_voxels); num_points == 0 gives a valid empty plan without touching a device.
+ * plan_average: out[v] = arithmetic mean of the rows of voxel v (Averager, :95-116) for any float attribute of width 1 .. 16 (points 3, covariances 9, normals 3 --
+ *   not re-normalised, as upstream --, intensities 1, times 1): accumulated and divided in f64, rounded once to f32, no floating-point atomics; bit-identical from
+ *   run to run and independent of which other attributes are reduced.  attr_dev float[num_points][width], out_dev float[num_voxels][width].  Asynchronous.
+ * plan_random_indices (randomgrid_sampling): points_per_voxel = ceil(sampling_rate * N / num_voxels) (:377) with N = the valid points and num_voxels = the occupied
+ *   voxels (the reference counts the key CHANGES of its sorted array, one less than its groups, the invalid group included); a voxel with fewer points keeps all
+ *   of them, every other voxel exactly points_per_voxel: those with the smallest counter-based hash of (seed, point index), ties by index.  No generator state: the
+ *   same seed gives the same selection on every run (mt19937 parity is neither possible nor wanted).  If the total exceeds size_t(N * sampling_rate * 1.2)
+ *   (:378,445-449) that many are kept, again the smallest hashes.  sampling_rate >= 0.99 selects every valid point (:300-303).  The indices are written in ascending
+ *   order (:451-452) to indices_out_dev (capacity num_points); *num_selected is valid on return (the call waits).
+ * gp_cloud_gather: out[i] = attr[indices[i]] for float rows of `width` -- sample() (:27-75); the indices must lie inside attr (not checked).  Asynchronous.
+ * GP_ERROR_INVALID_ARGUMENT before any device work: NULL arrays, a resolution that is not positive and finite, width outside 1 .. 16, a sampling rate outside (0, 1]. */
+typedef struct gp_voxelgrid_plan gp_voxelgrid_plan_t;
+int gp_voxelgrid_plan_create(const float* points_dev, int num_points, double resolution, gp_stream_t stream, gp_voxelgrid_plan_t** out);
+int gp_voxelgrid_plan_info(const gp_voxelgrid_plan_t* plan, int* num_voxels, int* num_dropped);
+int gp_voxelgrid_plan_average(gp_voxelgrid_plan_t* plan, const float* attr_dev, int width, float* out_dev);
+int gp_voxelgrid_plan_random_indices(gp_voxelgrid_plan_t* plan, double sampling_rate, unsigned long long seed, int* indices_out_dev, int* num_selected);
+int gp_voxelgrid_plan_destroy(gp_voxelgrid_plan_t* plan);
+int gp_cloud_gather(const float* attr_dev, int width, const int* indices_dev, int num_indices, float* out_dev, gp_stream_t stream);
+/* test hooks (thread-local, no device state): force_wide_keys != 0 makes every plan of this thread take the two-sort route (the one a bounding box of more than
+ * 2^32 - 1 cells takes); the next `sort_faults` plan builds / index selections see their first sort report an expired wait and must run again through the one-class
+ * sort.  Returns how many did so far.  gp_debug_sample_hash: the rank value of (seed, point index), host code. */
+int gp_debug_voxelgrid_hooks(int force_wide_keys, int sort_faults);
+unsigned gp_debug_sample_hash(unsigned long long seed, unsigned index);
+
 /* the symbolic phase alone (pure host code, no device needed): elimination order perm[k] = slot eliminated k-th, elimination tree
  * parent[k] (-1 = root), block counts and the schedule; any output pointer may be NULL */
 int gp_sparse_symbolic(int num_slots, const int* factor_slots, int num_factors, int ordering, int* perm_out, int* parent_out, int64_t* nnz_a_blocks, int64_t* nnz_l_blocks,
