@@ -18,7 +18,15 @@ from .factors import (  # noqa: F401
     create_nonlinear_factor_set_gpu,
     pose_inverse,
 )
-from .features import IntegratedGICPFactorGPU, KdTreeGPU, estimate_covariances_gpu, estimate_normals_covariances_gpu, estimate_normals_gpu  # noqa: F401
+from .features import (  # noqa: F401
+    IntegratedGICPFactorGPU,
+    IntegratedICPFactorGPU,
+    IntegratedPointToPlaneICPFactorGPU,
+    KdTreeGPU,
+    estimate_covariances_gpu,
+    estimate_normals_covariances_gpu,
+    estimate_normals_gpu,
+)
 from .sampling import VoxelGridPlan, randomgrid_sampling_gpu, sample_gpu, voxelgrid_sampling_gpu  # noqa: F401
 from .solver import (  # noqa: F401
     BetweenFactorPose3,
@@ -37,6 +45,8 @@ __all__ = [
     "GaussianVoxelMapGPU",
     "HessianFactor",
     "IntegratedGICPFactorGPU",
+    "IntegratedICPFactorGPU",
+    "IntegratedPointToPlaneICPFactorGPU",
     "IntegratedVGICPFactorGPU",
     "KdTreeGPU",
     "estimate_covariances_gpu",

@@ -4,6 +4,7 @@
   estimate_covariances_gpu  <- features/covariance_estimation.hpp:estimate_covariances(points, k=10)
   estimate_normals_gpu      <- features/normal_estimation.hpp:estimate_normals(points, k=10); estimate_normals_covariances_gpu: both from one search
   IntegratedGICPFactorGPU   <- factors/integrated_gicp_factor.hpp (CPU-only upstream), same calc_delta / HessianFactor protocol
+  IntegratedICPFactorGPU    <- factors/integrated_icp_factor.hpp (point-to-point / point-to-plane; CPU-only upstream), on a shared KdTreeGPU
 """
 import ctypes as C
 
@@ -186,3 +187,87 @@ class IntegratedGICPFactorGPU:
 
     def num_inliers(self):
         return self._num_inliers
+
+
+class IntegratedICPFactorGPU:
+    """ICP matching-cost factor on the GPU (IntegratedICPFactor_, impl/integrated_icp_factor_impl.hpp): 1-NN correspondences within max_correspondence_distance
+    (default 1 m, :30), point-to-point residuals or, with use_point_to_plane, the reference's element-wise r = n_B o (mu_B - T p) on the target's normals.
+    target_tree: a KdTreeGPU over `target` that many factors may share (held by reference, never rebuilt); None builds one and holds it (:47-51)."""
+
+    def __init__(self, target_key, source_key, target: PointCloudGPU, source: PointCloudGPU, target_tree=None, use_point_to_plane=False, max_correspondence_distance=1.0,
+                 stream=None, _fixed_target_pose=None):
+        self._lib = _capi.load()
+        self.is_binary = _fixed_target_pose is None
+        self._keys = [target_key, source_key] if self.is_binary else [source_key]
+        self.fixed_target_pose = np.eye(4) if self.is_binary else np.asarray(_fixed_target_pose, dtype=np.float64)
+        if target.points_gpu is None or (use_point_to_plane and target.normals_gpu is None):
+            raise _capi.GPError("error: target frame doesn't have required attributes for icp")
+        if source.points_gpu is None:
+            raise _capi.GPError("error: source frame doesn't have required attributes for icp")
+        self.target, self.source = target, source
+        self.use_point_to_plane = bool(use_point_to_plane)
+        self.target_tree = target_tree if target_tree is not None else KdTreeGPU(target, stream=stream)
+        if self.target_tree.frame.points_gpu is None or self.target_tree.frame.points_gpu.data_ptr() != target.points_gpu.data_ptr():
+            raise _capi.GPError("error: target_tree was not built over the target frame's points")
+        GaussianVoxelMapGPU._sync_torch(target)
+        GaussianVoxelMapGPU._sync_torch(source)
+        h = C.c_void_p()
+        _capi.check(
+            self._lib.gp_icp_factor_create(self.target_tree._h, target.ptr(target.points_gpu), target.ptr(target.normals_gpu) if use_point_to_plane else None, target.size(),
+                                           source.ptr(source.points_gpu), source.size(), float(max_correspondence_distance) ** 2, int(self.use_point_to_plane), stream, C.byref(h)),
+            "gp_icp_factor_create",
+        )
+        self._h = h
+        self.linearization_point = np.eye(4)
+        self._num_inliers = 0
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_icp_factor_destroy(self._h)  # (before the tree it borrows: self.target_tree is still referenced here)
+            self._h = None
+
+    def keys(self):
+        return self._keys
+
+    def set_correspondence_update_tolerance(self, angle, trans):
+        """keep the stored correspondences while a linearisation pose stays within (angle [rad], trans [m]) of the pose they were searched at (:128-141)"""
+        _capi.check(self._lib.gp_icp_factor_set_correspondence_update_tolerance(self._h, float(angle), float(trans)), "gp_icp_factor_set_correspondence_update_tolerance")
+
+    def calc_delta(self, values):
+        if not self.is_binary:
+            return pose_inverse(self.fixed_target_pose) @ np.asarray(values[self._keys[0]], dtype=np.float64)
+        return pose_inverse(values[self._keys[0]]) @ np.asarray(values[self._keys[1]], dtype=np.float64)
+
+    def linearize_delta(self, delta):
+        rec = _capi.Linearized6()
+        _capi.check(self._lib.gp_icp_factor_linearize(self._h, _pose16(delta), C.byref(rec)), "gp_icp_factor_linearize")
+        l = LinearizedSystem6(rec)
+        self._num_inliers = l.num_inliers
+        self.linearization_point = np.asarray(delta, dtype=np.float64)
+        self._linearized = True
+        return l
+
+    def linearize(self, values):
+        l = self.linearize_delta(self.calc_delta(values))
+        if self.is_binary:
+            return HessianFactor(self._keys, {(0, 0): l.H_target, (0, 1): l.H_target_source, (1, 1): l.H_source}, [-l.b_target, -l.b_source], l.error)
+        return HessianFactor(self._keys, {(0, 0): l.H_source}, [-l.b_source], l.error)
+
+    def error(self, values):
+        """evaluate(delta) on the stored correspondences; without any they are computed at `delta` itself first (:188-190)"""
+        delta = self.calc_delta(values)
+        if not getattr(self, "_linearized", False):
+            self.linearization_point = np.asarray(delta, dtype=np.float64)
+            self._linearized = True
+        out = C.c_double()
+        _capi.check(self._lib.gp_icp_factor_compute_error(self._h, _pose16(self.linearization_point), _pose16(delta), C.byref(out)), "gp_icp_factor_compute_error")
+        return out.value
+
+    def num_inliers(self):
+        return self._num_inliers
+
+
+def IntegratedPointToPlaneICPFactorGPU(target_key, source_key, target, source, target_tree=None, max_correspondence_distance=1.0, stream=None, _fixed_target_pose=None):
+    """IntegratedPointToPlaneICPFactor_ (factors/integrated_icp_factor.hpp): the ICP factor with use_point_to_plane = true"""
+    return IntegratedICPFactorGPU(target_key, source_key, target, source, target_tree=target_tree, use_point_to_plane=True,
+                                  max_correspondence_distance=max_correspondence_distance, stream=stream, _fixed_target_pose=_fixed_target_pose)

@@ -437,6 +437,29 @@ int gp_gicp_factor_linearize(gp_gicp_factor_t* f, const double pose[16], gp_line
  * again at pose_lin.  gp_gicp_factor_linearize always searches, as update_correspondences does with its default (zero) tolerances. */
 int gp_gicp_factor_compute_error(gp_gicp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
 
+/* IntegratedICPFactor_ (factors/integrated_icp_factor.hpp, impl/integrated_icp_factor_impl.hpp): point-to-point, or point-to-plane with the reference's
+ * element-wise residual r = n_B o (mu_B - T p) (:210-213, :228-232), on the 1-NN correspondences of T_lin p with squared distance < max (:146-157; the
+ * search and the transform in f64 on the f32 inputs).  error = sum r^T r (no 1/2, :215), H = sum J^T J, b = sum J^T r with J_t = diag(n_B) [-[q]x, I],
+ * J_s = diag(n_B) [R [p]x, -R], R the pose's 3x3 block as given (:220-238).  Two linearises at one pose are bit-identical.
+ * `grid` is BORROWED: a search structure over target_points_dev that the caller keeps alive for as long as the factor lives -- the reference's
+ * target_tree argument (:47-51), many factors against one target share one.  target_normals_dev may be NULL unless point_to_plane (then
+ * GP_ERROR_INVALID_ARGUMENT).  max_correspondence_distance_sq defaults to 1.0 upstream (:30). */
+typedef struct gp_icp_factor gp_icp_factor_t;
+int gp_icp_factor_create(const gp_point_grid_t* grid, const float* target_points_dev, const float* target_normals_dev, int num_target, const float* points_dev,
+                         int num_points, double max_correspondence_distance_sq, int point_to_plane, gp_stream_t stream, gp_icp_factor_t** out);
+int gp_icp_factor_destroy(gp_icp_factor_t* f); /* leaves the grid alone */
+/* update_correspondences(delta) + evaluate (:128-248).  With the default (zero) tolerances every linearise searches. */
+int gp_icp_factor_linearize(gp_icp_factor_t* f, const double pose[16], gp_linearized6* out_host);
+/* evaluate(delta_eval) on the stored correspondences when pose_lin is bit for bit the pose of the last linearise or the pose they were searched at
+ * (the reference's error() never searches once correspondences exist, :188-190); otherwise the search runs again at pose_lin. */
+int gp_icp_factor_compute_error(gp_icp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
+/* set_correspondence_update_tolerance(angle, trans) (:128-141): with either > 0 and correspondences stored, a linearise at delta keeps them when the
+ * rotation angle of delta^-1 * last_correspondence_point is < angle AND the norm of its translation is < trans (both strict: with one of the two left at
+ * zero the search always runs); otherwise it searches and moves the correspondence point.  The decision is made on the host. */
+int gp_icp_factor_set_correspondence_update_tolerance(gp_icp_factor_t* f, double angle, double trans);
+/* source points that had a correspondence in the last linearise (= its record's num_inliers); 0 before one */
+int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f);
+
 /* ---- the step after the path: damped normal equations assembled and solved on the device ----
  * DenseLinearSystemBuilder (optimizers/linear_system_builder.cpp:39-48): A = sum of the Hessian blocks scattered by key,
  *   b = sum of g (= -b_target / -b_source, integrated_matching_cost_factor.cpp:49), c = sum of the errors;
