@@ -669,7 +669,7 @@ def run_configs(args, lib, gpa, _capi, synthetic, torch, device, stream, want=No
                                                       "reference code is the stand-in Jacobi iteration of oracle/ref_shim, not Eigen's closed form)"),
                              parity_vs_reference=dict(rel_err_median=float(np.median(rel)), frac_within_1e5=float((rel < 1e-5).mean()))),
             gicp=dict(ms=round(gicp_ms, 4), corr_per_s=round(1e6 / gicp_ms * 1e3, 1),
-                      roofline=dict(bound="issue", kernel="gicp_correspond_kernel + gicp_tile_kernel<CORR> (gp_knn.hip)", unit="ms",
+                      roofline=dict(bound="issue", kernel="nearest_correspond_kernel (gp_knn.hip) + corr_tile_kernel<GicpTerm> (gp_corr_factors.hip)", unit="ms",
                                     note="1-NN walk of the cell grid per point, then the VGICP algebra on the matched target point; arithmetic- and divergence-bound (DESIGN.md 4.8)",
                                     compulsory_bytes=96 * 1_000_000, hbm_frac_of_compulsory=round(96e6 / (gicp_ms * 1e-3) / 8e12, 5)),
                       cpu_baseline=dict(value=round(1e6 / gicp_cpu_ms * 1e3, 1), unit="point-correspondences/s", cores=cores, cores_available=avail, kind=kind, ms=round(gicp_cpu_ms, 2),

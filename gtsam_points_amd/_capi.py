@@ -190,7 +190,7 @@ _SIGNATURES = {
     "gp_gicp_factor_create_ex": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_estimate_normals_from_covs": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gp_estimate_normals_covariances": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
-    # IntegratedICPFactor_ on a borrowed gp_point_grid (gp_knn.hip)
+    # IntegratedICPFactor_ on a borrowed gp_point_grid (gp_corr_factors.hip)
     "gp_icp_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_icp_factor_destroy": (C.c_int, [C.c_void_p]),
     "gp_icp_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(Linearized6)]),

@@ -409,6 +409,13 @@ struct HostSlots {
 void release_side_streams();  // gp_knn.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
 }  // namespace gp
 
+struct gp_point_grid;  // private to gp_knn.hip
+namespace gp {
+// gp_knn.hip, for the factors of gp_corr_factors.hip: corr[i] = index of the point of `grid` nearest to pose_lin * points[i] (column-major 4x4, f64 on the f32
+// inputs) with squared distance < max_sq_dist, or -1; n > 0.  Asynchronous on `stream`.
+int launch_nearest_correspondences(const gp_point_grid* grid, const float* points, int n, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream);
+}  // namespace gp
+
 // TempBufferManager (cuda/stream_temp_buffer_roundrobin.cu:11-47)
 struct gp_temp_buffer {
   struct Buffer {

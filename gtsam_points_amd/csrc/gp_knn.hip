@@ -1,11 +1,10 @@
-// gp_knn.hip -- exact k-nearest-neighbour search on a cell-sorted point grid, covariance estimation, and a GICP
-// linearisation that uses it (BASELINE.json configs[4]).
+// gp_knn.hip -- exact k-nearest-neighbour search on a cell-sorted point grid, covariance and normal estimation, and the
+// correspondence pass of the GICP / ICP factors of gp_corr_factors.hip (BASELINE.json configs[4]).
 //
 // Replaces (reference, CPU only -- there is no GPU counterpart upstream):
 //   ann/small_kdtree.hpp:124-186,437-474 + ann/knn_result.hpp:89-109   exact k-NN (kd-tree)      -> uniform-grid shell search
 //   features/covariance_estimation.cpp:18-77                          estimate_covariances      -> gp_estimate_covariances
-//   factors/impl/integrated_gicp_factor_impl.hpp:132-296              GICP correspondences+H/b  -> gp_gicp_factor_*
-//   factors/impl/integrated_icp_factor_impl.hpp:128-157,180-248       ICP correspondences+H/b   -> gp_icp_factor_*
+//   factors/impl/integrated_gicp_factor_impl.hpp:132-172              update_correspondences    -> gp::launch_nearest_correspondences
 //
 // Exactness: a query visits the cells of growing cubes around its own cell and stops after radius r once it holds k
 // neighbours whose k-th squared distance is <= d_safe(r)^2, where d_safe(r) = r*h + (distance from the query to the
@@ -23,7 +22,6 @@
 #include "gp_binning.hpp"
 #include "gp_scan.hpp"
 #include "gp_host.hpp"
-#include "gp_vgicp_tile.hpp"
 
 namespace gp {
 
@@ -1846,32 +1844,24 @@ __global__ void __launch_bounds__(128) covariance_settle_kernel(const float4* __
   todo_append(leftover, pos, todo_list, todo_count);
 }
 
-// ---- GICP: 1-NN correspondence within max distance + the same H/b algebra as VGICP ------------------------------------
-struct GicpDesc {
+// ---- the correspondence pass of the matching-cost factors (gp_corr_factors.hip) ----------------------------------------------------
+struct NearestDesc {
   const float* points;
-  const float* covs;
-  const float* target_points;
-  const float* target_covs;
   SearchView grid;
   int n;
   double max_sq_dist;
+  double pose[16];  // rides in the kernel arguments (no H2D copy in front of the launch)
 };
 
-// the poses ride in the kernel arguments (no H2D copy in front of the launch)
-struct GicpPoses {
-  double lin[16], eval[16];
-};
-
-// correspondence pass of the GICP factor (IntegratedGICPFactor_::update_correspondences, integrated_gicp_factor_impl.hpp:132-172):
-// corr[i] = index of the nearest target point of T_lin p_i with squared distance < max, or -1.  ONE query per lane and nothing else in
-// the kernel: the fused search + algebra kernel below holds 32 f64 accumulators and the algebra's temporaries next to the search state
-// (157 VGPRs: three waves per SIMD, and a 1 M-point cloud only brings 3.8), and the search is a chain of dependent round trips that
-// only occupancy hides.  The stored correspondences are also what the reference's error() evaluates on (it does not search again).
+// update_correspondences of the GICP and ICP factors (integrated_gicp_factor_impl.hpp:132-172, integrated_icp_factor_impl.hpp:146-157):
+// corr[i] = index of the nearest target point of T p_i with squared distance < max, or -1.  ONE query per lane and nothing else in
+// the kernel: the search is a chain of dependent round trips that only occupancy hides, and a kernel that also held a factor's 32 f64
+// accumulators and the algebra's temporaries next to the search state took 157 VGPRs (three waves per SIMD, and a 1 M-point cloud only brings 3.8).
 // (92 VGPRs, five waves per SIMD.  Capped at 80 VGPRs -- six waves, eleven registers spilled -- it measured 2 % faster: not worth the scratch.)
-__global__ void __launch_bounds__(256) gicp_correspond_kernel(GicpDesc f, const GicpPoses poses, int* __restrict__ corr) {
+__global__ void __launch_bounds__(256) nearest_correspond_kernel(NearestDesc f, int* __restrict__ corr) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= f.n) return;
-  const Pose Tl = load_pose(poses.lin);
+  const Pose Tl = load_pose(f.pose);
   const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
   const double lx = Tl.r00 * px + Tl.r01 * py + Tl.r02 * pz + Tl.tx;
   const double ly = Tl.r10 * px + Tl.r11 * py + Tl.r12 * pz + Tl.ty;
@@ -1880,184 +1870,6 @@ __global__ void __launch_bounds__(256) gicp_correspond_kernel(GicpDesc f, const 
   top.init(1, f.max_sq_dist);
   knn_query_any<1>(f.grid, lx, ly, lz, 1, top);
   corr[i] = top.found ? top.idx[0] : -1;
-}
-
-// CORR: the correspondences come from gicp_correspond_kernel (corr[]) instead of a search of this kernel's own
-template <int MODE, bool CORR = false>  // MODE_LIN (rigid pose: 29 sums + adjoint finalize), MODE_ERR, MODE_LIN_GENERAL (any 3x3 block: 92 explicit sums)
-__global__ void __launch_bounds__(256) gicp_tile_kernel(GicpDesc f, const GicpPoses poses,
-                                                        int tile_points, double* __restrict__ partials, const int* __restrict__ corr = nullptr) {
-  constexpr int NACC = MODE == MODE_ERR ? 2 : (MODE == MODE_LIN ? ACC_SIZE : ACCG_SIZE);
-  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
-  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : 32;
-  const Pose Tl = load_pose(poses.lin);
-  const Pose Te = MODE == MODE_ERR ? load_pose(poses.eval) : Tl;
-  double acc[NREG];
-#pragma unroll
-  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
-  const int begin = blockIdx.x * tile_points;
-  const int end = min(begin + tile_points, f.n);
-  for (int i = begin + threadIdx.x; i < end; i += 256) {
-    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
-    const double lx = Tl.r00 * px + Tl.r01 * py + Tl.r02 * pz + Tl.tx;
-    const double ly = Tl.r10 * px + Tl.r11 * py + Tl.r12 * pz + Tl.ty;
-    const double lz = Tl.r20 * px + Tl.r21 * py + Tl.r22 * pz + Tl.tz;
-    // correspondence: nearest target point with sq_dist < max (integrated_gicp_factor_impl.hpp:166-170)
-    size_t j;
-    if constexpr (CORR) {
-      const int c = corr[i];
-      if (c < 0) continue;
-      j = (size_t)c;
-    } else {
-      TopK<1> top;
-      top.init(1, f.max_sq_dist);
-      knn_query_any<1>(f.grid, lx, ly, lz, 1, top);
-      if (top.found == 0) continue;
-      j = (size_t)top.idx[0];
-    }
-    const float* cp = f.covs + 9 * (size_t)i;
-    const float* cq = f.target_covs + 9 * j;
-    // reuse the VGICP per-point algebra: the "voxel" is the matched target point (mu_B, C_B)
-    const double mux = (double)f.target_points[3 * j], muy = (double)f.target_points[3 * j + 1], muz = (double)f.target_points[3 * j + 2];
-    // symmetric parts of both column-major 3x3 covariances (exactly the inputs when they are symmetric)
-    const double cb[6] = {(double)cq[0], 0.5 * ((double)cq[3] + (double)cq[1]), 0.5 * ((double)cq[6] + (double)cq[2]),
-                          (double)cq[4], 0.5 * ((double)cq[7] + (double)cq[5]), (double)cq[8]};
-    if constexpr (MODE == MODE_LIN_GENERAL) {
-      const double ca[6] = {(double)cp[0], 0.5 * ((double)cp[3] + (double)cp[1]), 0.5 * ((double)cp[6] + (double)cp[2]),
-                            (double)cp[4], 0.5 * ((double)cp[7] + (double)cp[5]), (double)cp[8]};
-      double m[6];
-      fused_mahalanobis(Tl, ca, cb, m);
-      accumulate_sums<MODE_LIN_GENERAL>(Tl, m, px, py, pz, lx, ly, lz, mux - lx, muy - ly, muz - lz, acc);
-    } else {
-      const v2d c01 = {cb[0], cb[1]}, c23 = {cb[2], cb[3]}, c45 = {cb[4], cb[5]};
-      accumulate_terms_mu<MODE, double>(Tl, Te, (float)px, (float)py, (float)pz, cp, mux, muy, muz, c01, c23, c45, acc);
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ double lds[4][STRIDE];
-  if constexpr (MODE == MODE_LIN) {
-    const double s = butterfly_reduce32(acc, lane);
-    if ((lane & 1) == 0) lds[wave][butterfly_component(lane)] = s;
-  } else {
-#pragma unroll
-    for (int k = 0; k < NACC; k++) {
-      double v = acc[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane == 0) lds[wave][k] = v;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < STRIDE) {
-    double s = 0.0;
-    if (threadIdx.x < NACC) s = (lds[0][threadIdx.x] + lds[1][threadIdx.x]) + (lds[2][threadIdx.x] + lds[3][threadIdx.x]);
-    partials[(size_t)blockIdx.x * STRIDE + threadIdx.x] = s;
-  }
-}
-
-// ---- ICP: the same correspondence pass, point-to-point or point-to-plane residuals (integrated_icp_factor_impl.hpp:180-248) --------
-struct IcpDesc {
-  const float* points;          // [n][3] source
-  const float* target_points;   // [num_target][3]
-  const float* target_normals;  // [num_target][3]; read by the point-to-plane kernels only
-  int n;
-};
-
-// The per-point body of IntegratedICPFactor_::evaluate (:199-240) on the correspondences gicp_correspond_kernel left in corr[]:
-//   q = T p, d = mu_B - q, r = n_B o d (element-wise, :212; point-to-point: r = d), error += r^T r (:215, no 1/2),
-//   J_t = diag(n_B) [-[q]x, I], J_s = diag(n_B) [R [p]x, -R] (:220-232), H += J^T J, b += J^T r (:234-238).
-// That is the GICP algebra with M = diag(n_B o n_B) (or I) in place of the fused Mahalanobis matrix, so the sums go into the SAME
-// partial-row layout (gp_device.hpp ACC / ACCG) and through the same finalize kernels: b_t = [q x w; w] with w = n_B o r = M d,
-// K = M [q]x and TL = -[q]x K written out for a diagonal M (the off-diagonal slots of ACC_M and the diagonal of K stay zero).
-// A matched point costs 4 B (index) + 12 B (source point) + 12 B (target point) [+ 12 B (normal)]; no covariance is read and nothing is
-// inverted.  A non-orthonormal 3x3 block takes the 92 explicit sums of accumulate_sums<MODE_LIN_GENERAL>, J_s from the block AS GIVEN.
-// One workgroup per tile of `tile_points` points, lane t of 256 takes points t, t + 256, ... of its tile; the lanes meet in the
-// butterfly / shuffle tree and the four waves in wave order: a fixed order, two linearises at one pose are bit-identical.
-template <int MODE, bool PLANE>  // MODE_LIN (rigid pose: 29 sums + adjoint finalize), MODE_ERR, MODE_LIN_GENERAL (any 3x3 block: 92 explicit sums)
-__global__ void __launch_bounds__(256) icp_tile_kernel(IcpDesc f, const GicpPoses poses, int tile_points, double* __restrict__ partials, const int* __restrict__ corr) {
-  constexpr int NACC = MODE == MODE_ERR ? 2 : (MODE == MODE_LIN ? ACC_SIZE : ACCG_SIZE);
-  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
-  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? 2 : 32);
-  const Pose Tl = load_pose(poses.lin);
-  const Pose Te = MODE == MODE_ERR ? load_pose(poses.eval) : Tl;
-  double acc[NREG];
-#pragma unroll
-  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
-  const int begin = blockIdx.x * tile_points;
-  const int end = min(begin + tile_points, f.n);
-  for (int i = begin + threadIdx.x; i < end; i += 256) {
-    const int c = corr[i];
-    if (c < 0) continue;  // no target point within the cut-off (:200-202)
-    const size_t j = (size_t)c;
-    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
-    const double mux = (double)f.target_points[3 * j], muy = (double)f.target_points[3 * j + 1], muz = (double)f.target_points[3 * j + 2];
-    double nx = 1.0, ny = 1.0, nz = 1.0;
-    if constexpr (PLANE) {
-      nx = (double)f.target_normals[3 * j];
-      ny = (double)f.target_normals[3 * j + 1];
-      nz = (double)f.target_normals[3 * j + 2];
-    }
-    const double qx = Te.r00 * px + Te.r01 * py + Te.r02 * pz + Te.tx;
-    const double qy = Te.r10 * px + Te.r11 * py + Te.r12 * pz + Te.ty;
-    const double qz = Te.r20 * px + Te.r21 * py + Te.r22 * pz + Te.tz;
-    const double dx = mux - qx, dy = muy - qy, dz = muz - qz;
-    if constexpr (MODE == MODE_LIN_GENERAL) {
-      const double m[6] = {nx * nx, 0.0, 0.0, ny * ny, 0.0, nz * nz};
-      accumulate_sums<MODE_LIN_GENERAL>(Tl, m, px, py, pz, qx, qy, qz, dx, dy, dz, acc);
-    } else {
-      const double rx = PLANE ? nx * dx : dx, ry = PLANE ? ny * dy : dy, rz = PLANE ? nz * dz : dz;  // r = n_B o d
-      acc[ACC_COUNT] += 1.0;
-      acc[ACC_ERR] += rx * rx + ry * ry + rz * rz;
-      if constexpr (MODE == MODE_LIN) {
-        const double m0 = PLANE ? nx * nx : 1.0, m3 = PLANE ? ny * ny : 1.0, m5 = PLANE ? nz * nz : 1.0;  // M = diag(n_B o n_B)
-        const double wx = PLANE ? nx * rx : rx, wy = PLANE ? ny * ry : ry, wz = PLANE ? nz * rz : rz;     // w = n_B o r
-        acc[ACC_M + 0] += m0;
-        acc[ACC_M + 3] += m3;
-        acc[ACC_M + 5] += m5;
-        // K = M [q]x, row-major
-        const double k01 = -m0 * qz, k02 = m0 * qy, k10 = m3 * qz, k12 = -m3 * qx, k20 = -m5 * qy, k21 = m5 * qx;
-        acc[ACC_K + 1] += k01;
-        acc[ACC_K + 2] += k02;
-        acc[ACC_K + 3] += k10;
-        acc[ACC_K + 5] += k12;
-        acc[ACC_K + 6] += k20;
-        acc[ACC_K + 7] += k21;
-        // TL = -[q]x K (= [q]x^T M [q]x), upper triangle
-        acc[ACC_TL + 0] += qz * k10 - qy * k20;
-        acc[ACC_TL + 1] += -qy * k21;
-        acc[ACC_TL + 2] += qz * k12;
-        acc[ACC_TL + 3] += qx * k21 - qz * k01;
-        acc[ACC_TL + 4] += -qz * k02;
-        acc[ACC_TL + 5] += qy * k02 - qx * k12;
-        // b_t = [q x w; w]
-        acc[ACC_QXMR + 0] += qy * wz - qz * wy;
-        acc[ACC_QXMR + 1] += qz * wx - qx * wz;
-        acc[ACC_QXMR + 2] += qx * wy - qy * wx;
-        acc[ACC_MR + 0] += wx;
-        acc[ACC_MR + 1] += wy;
-        acc[ACC_MR + 2] += wz;
-      }
-    }
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ double lds[4][STRIDE];
-  if constexpr (MODE == MODE_LIN) {
-    const double s = butterfly_reduce32(acc, lane);
-    if ((lane & 1) == 0) lds[wave][butterfly_component(lane)] = s;
-  } else {
-#pragma unroll
-    for (int k = 0; k < NACC; k++) {
-      double v = acc[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-      if (lane == 0) lds[wave][k] = v;
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < STRIDE) {
-    double s = 0.0;
-    if (threadIdx.x < NACC) s = (lds[0][threadIdx.x] + lds[1][threadIdx.x]) + (lds[2][threadIdx.x] + lds[3][threadIdx.x]);
-    partials[(size_t)blockIdx.x * STRIDE + threadIdx.x] = s;
-  }
 }
 
 }  // namespace gp
@@ -2143,87 +1955,20 @@ struct gp_point_grid {
 };
 
 
-struct gp_gicp_factor {
-  gp_point_grid* grid = nullptr;
-  gp::GicpDesc desc{};
-  hipStream_t stream = nullptr;
-  int tile_points = 1024;
-  int num_tiles = 0;
-  gp::DeviceArray partials, d_poses, d_out;
-  gp::PinnedArray h_out;
-  void* h_out_dev = nullptr;
-  gp::PinnedArray h_done;  // completion word of the synchronous calls (gp_vgicp_shared.hpp: DoneFlags)
-  void* h_done_dev = nullptr;
-  unsigned long long seq = 0;
-  gp::DeviceArray corr;          // [n] correspondences of the last correspondence pass (gicp_correspond_kernel)
-  double corr_pose[16] = {0};    // ... and the linearisation pose they belong to
-  bool corr_valid = false;
-};
-
-// correspondences at `pose_lin`.  A linearise always searches (IntegratedGICPFactor_::linearize calls update_correspondences every time,
-// the default update tolerances being zero); an error evaluation re-uses the stored correspondences when they belong to its
-// linearisation pose -- the reference's error() evaluates on the correspondences of the last linearise (impl.hpp:183-185).
-static int gicp_correspond(gp_gicp_factor* f, const gp::GicpPoses& P, bool reuse) {
-  constexpr bool split = true;  // the correspondence pass is its own kernel (the fused kernel: 0.233 vs 0.160 ms per linearise, profiles/r02_gicp_split_ab.jsonl)
-  if (!split || f->desc.n <= 0) return 0;
-  if (!f->corr.ptr) {
-    if (f->corr.alloc(sizeof(int) * (size_t)f->desc.n) != GP_OK) return 0;  // no memory for the index array: the fused kernel still works
-    f->corr_valid = false;
-  }
-  if (!reuse || !f->corr_valid || memcmp(f->corr_pose, P.lin, sizeof(double) * 16) != 0) {
-    hipLaunchKernelGGL(gp::gicp_correspond_kernel, dim3((f->desc.n + 255) / 256), dim3(256), 0, f->stream, f->desc, P, f->corr.as<int>());
-    memcpy(f->corr_pose, P.lin, sizeof(double) * 16);
-    f->corr_valid = true;
-  }
-  return 1;
-}
-
-struct gp_icp_factor {
-  const gp_point_grid* grid = nullptr;  // BORROWED: the caller's search structure over the target (the reference's target_tree), shared between factors
-  gp::GicpDesc search{};                // what gicp_correspond_kernel reads: source points, the grid's view, the cut-off (no covariances)
-  gp::IcpDesc desc{};
-  bool plane = false;
-  hipStream_t stream = nullptr;
-  int tile_points = 1024;
-  int num_tiles = 0;
-  gp::DeviceArray partials, corr;  // corr: [n] correspondences of the last correspondence pass
-  gp::PinnedArray h_out;
-  void* h_out_dev = nullptr;
-  gp::PinnedArray h_done;  // completion word of the synchronous calls (gp_vgicp_shared.hpp: DoneFlags)
-  void* h_done_dev = nullptr;
-  unsigned long long seq = 0;
-  double corr_pose[16] = {0};  // last_correspondence_point: the pose the stored correspondences were searched at
-  double lin_pose[16] = {0};   // the pose of the last linearise (which may have kept older correspondences: the update tolerances)
-  bool corr_valid = false, lin_valid = false;
-  double tol_rot = 0.0, tol_trans = 0.0;  // correspondence_update_tolerance_rot / _trans (:32-33)
-  int num_correspondences = 0;
-};
-
-// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137) on two column-major 4x4 poses: diff = delta^-1 * last (the
-// isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
-static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta) {
-  if (!f->corr_valid || !(f->tol_trans > 0.0 || f->tol_rot > 0.0)) return false;
-  const double* last = f->corr_pose;
-  double D[3][3], t[3];
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) D[r][c] = delta[4 * r] * last[4 * c] + delta[4 * r + 1] * last[4 * c + 1] + delta[4 * r + 2] * last[4 * c + 2];
-    t[r] = delta[4 * r] * (last[12] - delta[12]) + delta[4 * r + 1] * (last[13] - delta[13]) + delta[4 * r + 2] * (last[14] - delta[14]);
-  }
-  // angle in [0, pi] from sin (the skew part) and cos (the trace): what Eigen::AngleAxisd(diff.linear()).angle() gives for a rotation
-  const double sx = 0.5 * (D[2][1] - D[1][2]), sy = 0.5 * (D[0][2] - D[2][0]), sz = 0.5 * (D[1][0] - D[0][1]);
-  const double diff_rot = std::atan2(std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0));
-  const double diff_trans = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  return diff_rot < f->tol_rot && diff_trans < f->tol_trans;
-}
-
-// the correspondence pass at P.lin: the GICP factor's kernel, unchanged
-static int icp_search(gp_icp_factor* f, const gp::GicpPoses& P) {
-  hipLaunchKernelGGL(gp::gicp_correspond_kernel, dim3((f->desc.n + 255) / 256), dim3(256), 0, f->stream, f->search, P, f->corr.as<int>());
+namespace gp {
+// the one thing the matching-cost factors need of the search (declared in gp_host.hpp; n > 0)
+int launch_nearest_correspondences(const gp_point_grid* grid, const float* points, int n, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream) {
+  NearestDesc f;
+  f.points = points;
+  f.grid = grid->view();  // the max-distance bound terminates the search early (worst() starts at max_sq_dist)
+  f.n = n;
+  f.max_sq_dist = max_sq_dist;
+  memcpy(f.pose, pose_lin, sizeof(double) * 16);
+  hipLaunchKernelGGL(nearest_correspond_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, f, corr);
   GP_HIP(hipGetLastError());
-  memcpy(f->corr_pose, P.lin, sizeof(double) * 16);
-  f->corr_valid = true;
   return GP_OK;
 }
+}  // namespace gp
 
 extern "C" {
 
@@ -2768,211 +2513,6 @@ int gp_estimate_normals_from_covs(const float* points_dev, const float* covs_dev
   if (n == 0) return GP_OK;
   hipLaunchKernelGGL(gp::normals_from_covs_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, points_dev, covs_dev, n, normals_dev);
   GP_HIP(hipGetLastError());
-  return GP_OK;
-}
-
-// ---- GICP factor ----------------------------------------------------------------------------------------------------
-
-int gp_gicp_factor_create(const float* target_points_dev, const float* target_covs_dev, int n_target, const float* points_dev, const float* covs_dev, int n,
-                          double max_correspondence_distance_sq, gp_stream_t stream, gp_gicp_factor_t** out) {
-  return gp_gicp_factor_create_ex(target_points_dev, target_covs_dev, n_target, points_dev, covs_dev, n, max_correspondence_distance_sq, 0, nullptr, stream, out);
-}
-
-int gp_gicp_factor_create_ex(const float* target_points_dev, const float* target_covs_dev, int n_target, const float* points_dev, const float* covs_dev, int n,
-                             double max_correspondence_distance_sq, int structure, unsigned long long* counters_dev, gp_stream_t stream, gp_gicp_factor_t** out) {
-  if (!target_points_dev || !target_covs_dev || !points_dev || !covs_dev || n < 0 || n_target < 0 || !(max_correspondence_distance_sq > 0.0) || !out)
-    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_gicp_factor_create: bad arguments");
-  auto* f = new gp_gicp_factor;
-  f->stream = (hipStream_t)stream;
-  // finest cell = 1/4 of the correspondence radius (coarser levels x4, x16); the max-distance bound ends every search
-  // cell = 1/4 of the correspondence radius: the fine shells 0 and 1 settle the well-matched points, and one block edge = the
-  // radius, so the block walk behind them ends at the first block shell at the latest
-  int rc = gp_point_grid_create_ex(target_points_dev, n_target, std::sqrt(max_correspondence_distance_sq) / 4.0, structure, counters_dev, stream, &f->grid);
-  if (rc != GP_OK) {
-    delete f;
-    return rc;
-  }
-  f->desc.points = points_dev;
-  f->desc.covs = covs_dev;
-  f->desc.target_points = target_points_dev;
-  f->desc.target_covs = target_covs_dev;
-  f->desc.grid = f->grid->view();  // the max-distance bound terminates the search early (worst() starts at max_sq_dist)
-  f->desc.n = n;
-  f->desc.max_sq_dist = max_correspondence_distance_sq;
-  f->num_tiles = (n + f->tile_points - 1) / f->tile_points;
-  if ((rc = f->partials.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(f->num_tiles, 1))) || (rc = f->d_poses.alloc(sizeof(double) * 32)) ||
-      (rc = f->d_out.alloc(sizeof(gp_linearized6))) || (rc = f->h_out.ensure(sizeof(gp_linearized6)))) {
-    gp_point_grid_destroy(f->grid);
-    delete f;
-    return rc;
-  }
-  GP_HIP(hipHostGetDevicePointer(&f->h_out_dev, f->h_out.ptr, 0));
-  if ((rc = f->h_done.ensure(sizeof(unsigned long long))) != GP_OK) {
-    gp_point_grid_destroy(f->grid);
-    delete f;
-    return rc;
-  }
-  memset(f->h_done.ptr, 0, f->h_done.bytes);
-  GP_HIP(hipHostGetDevicePointer(&f->h_done_dev, f->h_done.ptr, 0));
-  *out = f;
-  return GP_OK;
-}
-
-int gp_gicp_factor_destroy(gp_gicp_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  gp_point_grid_destroy(f->grid);
-  delete f;
-  return GP_OK;
-}
-
-int gp_gicp_factor_linearize(gp_gicp_factor_t* f, const double pose[16], gp_linearized6* out_host) {
-  if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_gicp_factor_linearize: null");
-  gp::GicpPoses P;
-  memcpy(P.lin, pose, sizeof(double) * 16);
-  memcpy(P.eval, pose, sizeof(double) * 16);
-  // the 29-sum kernel + adjoint finalize is exact only for an orthonormal 3x3 block; any other pose (e.g. built from 6-digit
-  // quaternions, src/test/test_matching_cost_factors.cpp:50-55) takes the 92-sum path with the explicit J_s, like the VGICP factor
-  const bool rigid = gp::pose_is_rigid(pose);
-  if (f->num_tiles > 0) {
-    const int* corr = gicp_correspond(f, P, false) ? f->corr.as<int>() : nullptr;
-    if (rigid && corr)
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_LIN, true>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    else if (rigid)
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_LIN, false>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    else if (corr)
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_LIN_GENERAL, true>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    else
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_LIN_GENERAL, false>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    GP_HIP(hipGetLastError());
-  }
-  const gp::DoneFlags done{static_cast<unsigned long long*>(f->h_done_dev), ++f->seq};
-  GP_TRY(gp::launch_finalize_single(f->stream, nullptr, pose, f->partials.as<double>(), f->num_tiles, reinterpret_cast<gp_linearized6*>(f->h_out_dev), !rigid, done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(f->h_done.ptr), 1, done.seq, f->stream, 100 + (long)f->num_tiles * (long)f->tile_points / 1000));  // spin budget ~4x the kernel (0.2 ns per point)
-  memcpy(out_host, f->h_out.ptr, sizeof(gp_linearized6));
-  return GP_OK;
-}
-
-int gp_gicp_factor_compute_error(gp_gicp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
-  if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_gicp_factor_compute_error: null");
-  gp::GicpPoses P;
-  memcpy(P.lin, pose_lin, sizeof(double) * 16);
-  memcpy(P.eval, pose_eval, sizeof(double) * 16);
-  if (f->num_tiles > 0) {
-    const int* corr = gicp_correspond(f, P, true) ? f->corr.as<int>() : nullptr;
-    if (corr)
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_ERR, true>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    else
-      hipLaunchKernelGGL((gp::gicp_tile_kernel<gp::MODE_ERR, false>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), corr);
-    GP_HIP(hipGetLastError());
-  }
-  const gp::DoneFlags done{static_cast<unsigned long long*>(f->h_done_dev), ++f->seq};
-  GP_TRY(gp::launch_finalize_error_single(f->stream, f->partials.as<double>(), f->num_tiles, reinterpret_cast<double*>(f->h_out_dev), done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(f->h_done.ptr), 1, done.seq, f->stream, 100 + (long)f->num_tiles * (long)f->tile_points / 1000));  // spin budget ~4x the kernel (0.2 ns per point)
-  memcpy(out_host, f->h_out.ptr, sizeof(double));
-  return GP_OK;
-}
-
-// ---- ICP factor -----------------------------------------------------------------------------------------------------
-
-int gp_icp_factor_create(const gp_point_grid_t* grid, const float* target_points_dev, const float* target_normals_dev, int n_target, const float* points_dev, int n,
-                         double max_correspondence_distance_sq, int point_to_plane, gp_stream_t stream, gp_icp_factor_t** out) {
-  if (!grid || !target_points_dev || !points_dev || n < 0 || n_target < 0 || !(max_correspondence_distance_sq > 0.0) || !out)
-    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_create: bad arguments");
-  if (point_to_plane && !target_normals_dev) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_create: a point-to-plane factor needs the target's normals");
-  auto f = std::make_unique<gp_icp_factor>();
-  f->grid = grid;
-  f->stream = (hipStream_t)stream;
-  f->plane = point_to_plane != 0;
-  f->search.points = points_dev;
-  f->search.target_points = target_points_dev;
-  f->search.grid = grid->view();  // the cut-off ends every search (worst() starts at max_sq_dist), whatever cell size the caller built the grid with
-  f->search.n = n;
-  f->search.max_sq_dist = max_correspondence_distance_sq;
-  f->desc.points = points_dev;
-  f->desc.target_points = target_points_dev;
-  f->desc.target_normals = target_normals_dev;
-  f->desc.n = n;
-  f->num_tiles = (n + f->tile_points - 1) / f->tile_points;
-  GP_TRY(f->partials.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(f->num_tiles, 1)));
-  GP_TRY(f->corr.alloc(sizeof(int) * (size_t)std::max(n, 1)));
-  GP_TRY(f->h_out.ensure(sizeof(gp_linearized6)));
-  GP_HIP(hipHostGetDevicePointer(&f->h_out_dev, f->h_out.ptr, 0));
-  GP_TRY(f->h_done.ensure(sizeof(unsigned long long)));
-  memset(f->h_done.ptr, 0, f->h_done.bytes);
-  GP_HIP(hipHostGetDevicePointer(&f->h_done_dev, f->h_done.ptr, 0));
-  *out = f.release();
-  return GP_OK;
-}
-
-int gp_icp_factor_destroy(gp_icp_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (the grid is the caller's)
-  return GP_OK;
-}
-
-int gp_icp_factor_set_correspondence_update_tolerance(gp_icp_factor_t* f, double angle, double trans) {
-  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_set_correspondence_update_tolerance: null");
-  f->tol_rot = angle;
-  f->tol_trans = trans;
-  return GP_OK;
-}
-
-int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f) { return f ? f->num_correspondences : 0; }
-
-extern "C++" template <int MODE>
-static void icp_launch_tiles(gp_icp_factor* f, const gp::GicpPoses& P) {
-  if (f->plane)
-    hipLaunchKernelGGL((gp::icp_tile_kernel<MODE, true>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), f->corr.as<int>());
-  else
-    hipLaunchKernelGGL((gp::icp_tile_kernel<MODE, false>), dim3(f->num_tiles), dim3(256), 0, f->stream, f->desc, P, f->tile_points, f->partials.as<double>(), f->corr.as<int>());
-}
-
-int gp_icp_factor_linearize(gp_icp_factor_t* f, const double pose[16], gp_linearized6* out_host) {
-  if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_linearize: null");
-  gp::GicpPoses P;
-  memcpy(P.lin, pose, sizeof(double) * 16);
-  memcpy(P.eval, pose, sizeof(double) * 16);
-  // as the GICP factor: the 29-sum kernel + adjoint finalize is exact only for an orthonormal 3x3 block, any other pose takes the 92 explicit sums
-  const bool rigid = gp::pose_is_rigid(pose);
-  if (f->num_tiles > 0) {
-    if (!icp_keep_correspondences(f, pose)) GP_TRY(icp_search(f, P));
-    if (rigid)
-      icp_launch_tiles<gp::MODE_LIN>(f, P);
-    else
-      icp_launch_tiles<gp::MODE_LIN_GENERAL>(f, P);
-    GP_HIP(hipGetLastError());
-  }
-  memcpy(f->lin_pose, pose, sizeof(double) * 16);
-  f->lin_valid = true;
-  const gp::DoneFlags done{static_cast<unsigned long long*>(f->h_done_dev), ++f->seq};
-  GP_TRY(gp::launch_finalize_single(f->stream, nullptr, pose, f->partials.as<double>(), f->num_tiles, reinterpret_cast<gp_linearized6*>(f->h_out_dev), !rigid, done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(f->h_done.ptr), 1, done.seq, f->stream, 100 + (long)f->num_tiles * (long)f->tile_points / 1000));
-  memcpy(out_host, f->h_out.ptr, sizeof(gp_linearized6));
-  f->num_correspondences = (int)out_host->num_inliers;
-  return GP_OK;
-}
-
-int gp_icp_factor_compute_error(gp_icp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
-  if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_compute_error: null");
-  gp::GicpPoses P;
-  memcpy(P.lin, pose_lin, sizeof(double) * 16);
-  memcpy(P.eval, pose_eval, sizeof(double) * 16);
-  if (f->num_tiles > 0) {
-    // the stored correspondences serve when pose_lin is the pose of the last linearise (which may itself have kept older ones) or the pose they were searched at
-    const bool stored = f->corr_valid && ((f->lin_valid && memcmp(f->lin_pose, pose_lin, sizeof(double) * 16) == 0) || memcmp(f->corr_pose, pose_lin, sizeof(double) * 16) == 0);
-    if (!stored) {
-      GP_TRY(icp_search(f, P));
-      f->lin_valid = false;
-    }
-    icp_launch_tiles<gp::MODE_ERR>(f, P);
-    GP_HIP(hipGetLastError());
-  }
-  const gp::DoneFlags done{static_cast<unsigned long long*>(f->h_done_dev), ++f->seq};
-  GP_TRY(gp::launch_finalize_error_single(f->stream, f->partials.as<double>(), f->num_tiles, reinterpret_cast<double*>(f->h_out_dev), done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(f->h_done.ptr), 1, done.seq, f->stream, 100 + (long)f->num_tiles * (long)f->tile_points / 1000));
-  memcpy(out_host, f->h_out.ptr, sizeof(double));
   return GP_OK;
 }
 

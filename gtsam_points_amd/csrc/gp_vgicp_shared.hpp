@@ -92,7 +92,7 @@ enum : int { MODE_LIN = 0, MODE_ERR = 1, MODE_LIN_GENERAL = 2 };
 // the sums of one correspondence given M (6, symmetric), the source point p, q = T_eval p and r = mu_B - q, in f64:
 // MODE_ERR: count and r^T M r; MODE_LIN: + the 27 target-side sums; MODE_LIN_GENERAL: + the explicit source-side and cross
 // blocks (92 sums, vgicp_derivatives.cuh:57-70) for poses whose 3x3 block is not orthonormal.  Shared by the reference-shaped
-// VGICP kernel (gp_vgicp.hip) and the GICP kernel's general path (gp_knn.hip).
+// VGICP kernel (gp_vgicp.hip) and the GICP / ICP kernels' general path (gp_corr_factors.hip).
 template <int MODE>
 __device__ __forceinline__ void accumulate_sums(const Pose& Tl, const double* m, double px, double py, double pz, double qx, double qy, double qz, double rx, double ry,
                                                 double rz, double* acc) {
@@ -189,7 +189,7 @@ __device__ __forceinline__ void accumulate_sums(const Pose& Tl, const double* m,
   }
 }
 
-// host-side launchers of the finalize kernels (defined in gp_vgicp.hip; used by gp_knn.hip for the GICP factor, whose
+// host-side launchers of the finalize kernels (defined in gp_vgicp.hip; used by gp_corr_factors.hip for the GICP and ICP factors, whose
 // partial rows have the same layout): one factor, rigid pose given both on the host (kernel arguments) and on the device
 // general == true: the partial rows hold the 92 explicit sums (ACCG layout) and are expanded without the adjoint identity
 // Completion words in host-mapped memory: a finalize kernel writes `seq` into done.flags[factor] behind its record, and the

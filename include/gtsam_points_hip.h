@@ -424,7 +424,9 @@ int gp_estimate_normals_covariances(const float* points_dev, int num_points, int
                                     gp_stream_t stream);
 
 typedef struct gp_gicp_factor gp_gicp_factor_t;
-/* IntegratedGICPFactor(target, source) with its target 1-NN structure; max_correspondence_distance_sq defaults to 1.0 upstream (:30) */
+/* IntegratedGICPFactor(target, source) with its target 1-NN structure; max_correspondence_distance_sq defaults to 1.0 upstream (:30).
+ * The factor owns that structure and an int per source point for the correspondences; both are allocated here, so a create that cannot
+ * have the index array fails with the allocator's status (there is no slower kernel without it to fall back to later). */
 int gp_gicp_factor_create(const float* target_points_dev, const float* target_covs_dev, int num_target, const float* points_dev, const float* covs_dev, int num_points,
                           double max_correspondence_distance_sq, gp_stream_t stream, gp_gicp_factor_t** out);
 int gp_gicp_factor_create_ex(const float* target_points_dev, const float* target_covs_dev, int num_target, const float* points_dev, const float* covs_dev, int num_points,

@@ -8,7 +8,7 @@ Covariances and normals come from estimate_normals_covariances_gpu (k = 10).  Ev
 minimum and the spread (inter-quartile range and max - min) of each.  The yardstick is the GICP linearise of the same run: the ICP factor runs the same search and reads
 28-40 B per matched point where GICP reads 96 B.  One JSON object per line; --out <file> appends them there too.  Run it under a time limit:
 
-  timeout -k 10 900 python scripts/icp_time.py --out profiles/icp_time.jsonl"""
+  timeout -k 10 900 python scripts/icp_time.py --out profiles/corr_factors_time.jsonl"""
 import ctypes as C, json, os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1,21 +1,36 @@
-"""CPU checks of the ICP factor's build products: the tile kernels' resources as the compiler reports them (no scratch, no spills) and the argument refusals that are
-made on the host before any device work."""
+"""CPU checks of the ICP and GICP factors' build products: the tile kernels' resources as the compiler reports them (no scratch, no spills) and the argument refusals
+that are made on the host before any device work."""
 import ctypes as C
 import os
 import re
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-RES = os.path.join(ROOT, "gtsam_points_amd", "csrc", "gp_knn.resources.txt")
+RES = os.path.join(ROOT, "gtsam_points_amd", "csrc", "gp_corr_factors.resources.txt")
 
 
-def test_icp_tile_kernels_use_no_scratch():
+def _tile_kernels(term):
+    """the compiler's remarks on the instantiations of corr_tile_kernel<MODE, TERM> whose (mangled) TERM contains `term`"""
     assert os.path.exists(RES), "build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')"
     blocks = {b.split()[0]: b for b in open(RES).read().split("remark: Function Name: ")[1:]}
-    ks = {k: v for k, v in blocks.items() if "icp_tile_kernel" in k and "gicp_tile_kernel" not in k}
-    assert len(ks) == 6  # {linearise, error, general linearise} x {point-to-point, point-to-plane}
+    return {k: v for k, v in blocks.items() if "corr_tile_kernel" in k and term in k}
+
+
+def _assert_no_scratch(ks):
     for name, b in ks.items():
         get = lambda key: int(re.search(re.escape(key) + r":\s+(\d+)", b).group(1))  # noqa: E731
         assert get("ScratchSize [bytes/lane]") == 0 and get("VGPRs Spill") == 0 and get("SGPRs Spill") == 0, name
+
+
+def test_icp_tile_kernels_use_no_scratch():
+    ks = _tile_kernels("IcpTerm")
+    assert len(ks) == 6  # {linearise, error, general linearise} x {point-to-point, point-to-plane}
+    _assert_no_scratch(ks)
+
+
+def test_gicp_tile_kernels_use_no_scratch():
+    ks = _tile_kernels("GicpTerm")
+    assert len(ks) == 3  # linearise, error, general linearise
+    _assert_no_scratch(ks)
 
 
 def test_icp_entry_points_refuse_bad_arguments_without_a_device():

@@ -3,12 +3,16 @@
 import numpy as np
 import pytest
 
+import icp_ref
 import knn_ref
 import oracle
 from helpers import BLOCKS, assert_linearized_close, expmap
 
 pytestmark = pytest.mark.gpu
 PARITY_TOL = 1e-7
+MARGIN = 1e-9  # test_icp_gpu.py's: the smallest relative tie / cut-off gap at which two f64 searches must agree
+XI = np.array([0.01, -0.02, 0.015, 0.10, -0.05, 0.03])
+NEARBY = np.array([0.002, -0.001, 0.003, 0.01, 0.02, -0.01])
 
 
 def test_knn_matches_bruteforce(gpu):
@@ -90,6 +94,72 @@ def test_gicp_linearize_matches_oracle(gpu, kitti00, xi):
     L2 = f.linearize_delta(delta)
     for k in BLOCKS:
         assert np.array_equal(getattr(L2, k), getattr(L, k)), k
+
+
+def _check_gicp(gpu, tp, tc, sp, sc, delta, what, tgt=None):
+    """one GICP factor on the device against the oracle's at `delta`: record, inlier count, error at a nearby pose on the stored correspondences.  The search
+    is the ICP factor's: the same condition on the inputs (icp_ref's margins: no tie, nothing on the cut-off) before anything is compared."""
+    tie, cut = icp_ref.ICPFactorRef(tp, sp).margins(delta)
+    assert tie.min() > MARGIN and cut.min() > MARGIN, f"{what}: a correspondence two f64 implementations could decide differently (tie {tie.min():.2e}, cut-off {cut.min():.2e})"
+    f = gpu.IntegratedGICPFactorGPU(0, 1, tgt if tgt is not None else gpu.PointCloudGPU(tp, tc), gpu.PointCloudGPU(sp, sc))
+    fo = oracle.OracleGICPFactor(tp, tc, sp, sc, 4)
+    L, Lo = f.linearize_delta(delta), fo.linearize(delta)
+    print(f"[gicp] {what}: inliers {L.num_inliers} / {Lo.num_inliers}, error {L.error!r} / {Lo.error!r}")
+    assert_linearized_close(L, Lo, PARITY_TOL, what)  # (the inlier counts are compared for equality)
+    for k in BLOCKS + ["error"]:
+        assert np.isfinite(getattr(L, k)).all(), k
+    de = delta @ expmap(NEARBY)
+    e, eo = f.error({0: np.eye(4), 1: de}), fo.evaluate(de).error
+    assert abs(e - eo) <= PARITY_TOL * max(eo, 1e-300), (e, eo)
+    return f, L, Lo
+
+
+@pytest.fixture(scope="module")
+def gicp_target(gpu, kitti00):
+    return gpu.PointCloudGPU(kitti00["target_points"], kitti00["target_covs"])
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 1024, 1025])
+def test_gicp_source_sizes_at_lane_workgroup_and_tile_edges(gpu, kitti00, gicp_target, n):
+    """one lane, one short of / one past a workgroup's stride, exactly one tile, one point into a second tile"""
+    sp, sc = kitti00["source_points"][100 : 100 + n], kitti00["source_covs"][100 : 100 + n]
+    _, L, _ = _check_gicp(gpu, kitti00["target_points"], kitti00["target_covs"], sp, sc, expmap(XI), f"n={n}", gicp_target)
+    assert L.num_inliers == {1: 1, 255: 214, 257: 216, 1024: 909, 1025: 910}[n]  # the oracle's counts on this fixture
+
+
+def test_gicp_every_point_beyond_the_cut_off(gpu, kitti00, gicp_target):
+    far = expmap([0.0, 0.0, 0.0, 0.0, 0.0, 500.0])  # half a kilometre above the scan
+    f, L, Lo = _check_gicp(gpu, kitti00["target_points"], kitti00["target_covs"], kitti00["source_points"][:1025], kitti00["source_covs"][:1025], far, "all beyond", gicp_target)
+    assert Lo.num_inliers == 0 and L.num_inliers == 0 and L.error == 0.0
+    for k in BLOCKS:
+        assert not np.any(getattr(L, k)), k
+    assert f.error({0: np.eye(4), 1: far}) == 0.0
+
+
+def test_gicp_non_orthonormal_pose_takes_the_explicit_sums(gpu, kitti00, gicp_target):
+    delta = expmap(XI)
+    delta[:3, :3] = delta[:3, :3] @ (np.eye(3) + 1e-6 * np.random.default_rng(11).normal(size=(3, 3)))  # orthonormal to 1e-6 only, as test_icp_gpu.py builds it
+    assert np.abs(delta[:3, :3].T @ delta[:3, :3] - np.eye(3)).max() > 1e-7
+    _, L, _ = _check_gicp(gpu, kitti00["target_points"], kitti00["target_covs"], kitti00["source_points"], kitti00["source_covs"], delta, "non-orthonormal", gicp_target)
+    assert L.num_inliers == 14989
+
+
+def test_gicp_target_of_one_point(gpu, kitti00):
+    tp, tc = kitti00["target_points"][:1], kitti00["target_covs"][:1]
+    sp = (tp.astype(np.float64) + np.random.default_rng(5).uniform(-0.9, 0.9, (300, 3))).astype(np.float32)  # some within 1 m of the one point, some beyond
+    _, L, _ = _check_gicp(gpu, tp, tc, sp, kitti00["source_covs"][:300], np.eye(4), "one target point")
+    assert 0 < L.num_inliers < 300
+
+
+def test_gicp_two_linearises_are_bit_identical(gpu, kitti00, gicp_target):
+    src = gpu.PointCloudGPU(kitti00["source_points"], kitti00["source_covs"])
+    for delta in (expmap(XI), expmap(XI) @ np.diag([1.0 + 1e-6, 1.0, 1.0, 1.0])):  # the rigid and the general kernels
+        f = gpu.IntegratedGICPFactorGPU(0, 1, gicp_target, src)
+        A, B = f.linearize_delta(delta), f.linearize_delta(delta)
+        Cc = gpu.IntegratedGICPFactorGPU(0, 1, gicp_target, src).linearize_delta(delta)
+        for k in BLOCKS + ["error", "num_inliers"]:
+            assert np.array_equal(getattr(A, k), getattr(B, k)) and np.array_equal(getattr(A, k), getattr(Cc, k)), k
+        assert A.num_inliers > 14000
 
 
 def test_binned_and_hashed_structures_agree(gpu, kitti00):
