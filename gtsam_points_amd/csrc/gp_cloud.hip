@@ -281,7 +281,8 @@ extern "C" {
 
 int gp_voxelmap_overlap_multi(const gp_voxelmap_t* const* targets, const double* deltas, int num_targets, const float* points_dev, int num_points, int* num_hits,
                               gp_stream_t stream) {
-  if (!targets || !deltas || num_targets < 0 || !num_hits || num_points < 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_overlap_multi: bad arguments");
+  if (num_targets < 0 || (num_targets > 0 && (!targets || !deltas)) || !num_hits || num_points < 0)  // (an empty union has no arrays)
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_overlap_multi: bad arguments");
   if (!points_dev && num_points > 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "error: GPU source points have not been allocated!!");  // :270-273
   std::vector<gp::OverlapTarget> ts((size_t)num_targets);
   for (int k = 0; k < num_targets; k++) GP_TRY(fill_target(targets[k], deltas + 16 * (size_t)k, &ts[k]));

@@ -1119,7 +1119,8 @@ int gp_voxelmap_reload(gp_voxelmap_t* map, gp_stream_t stream) {
 
 int gp_voxelmap_lookup(const gp_voxelmap_t* map, const float* points_dev, const float* normals_dev, int n, const double delta[16], int* voxel_indices_dev,
                        gp_stream_t stream) {
-  if (!map || !points_dev || !delta || !voxel_indices_dev || n < 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_lookup: bad arguments");
+  // (an empty cloud has no arrays: n == 0 asks for no pointer)
+  if (!map || !delta || n < 0 || (n > 0 && (!points_dev || !voxel_indices_dev))) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_lookup: bad arguments");
   if (!map->loaded()) return gp::fail(GP_ERROR_NOT_LOADED, "gp_voxelmap_lookup: voxel map is not on the GPU");
   if (n == 0) return GP_OK;
   hipStream_t s = (hipStream_t)stream;
@@ -1134,7 +1135,7 @@ int gp_voxelmap_lookup(const gp_voxelmap_t* map, const float* points_dev, const 
 }
 
 int gp_voxelmap_overlap(const gp_voxelmap_t* map, const float* points_dev, int n, const double delta[16], int* num_hits, gp_stream_t stream) {
-  if (!map || !points_dev || !delta || !num_hits || n < 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_overlap: bad arguments");
+  if (!map || !delta || !num_hits || n < 0 || (n > 0 && !points_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_overlap: bad arguments");
   if (!map->loaded()) return gp::fail(GP_ERROR_NOT_LOADED, "gp_voxelmap_overlap: voxel map is not on the GPU");
   *num_hits = 0;
   if (n == 0) return GP_OK;

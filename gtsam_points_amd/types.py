@@ -367,6 +367,11 @@ class GaussianVoxelMapGPU(OffloadableGPU):
     def lookup(self, frame: PointCloudGPU, delta=np.eye(4), surface_validation=False):
         import torch
 
+        if frame.points_gpu is None:
+            raise _capi.GPError("error: GPU source points have not been allocated!!")
+        if surface_validation and frame.normals_gpu is None:
+            # (a null normals pointer means "no validation" to the library: asking for it without normals must not pass silently)
+            raise _capi.GPError("error: frame does not have normals on GPU!!")
         self._sync_torch(frame)
         out = torch.empty(frame.size(), dtype=torch.int32, device=frame.device)
         normals = frame.ptr(frame.normals_gpu) if surface_validation else None

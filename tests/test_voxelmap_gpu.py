@@ -93,8 +93,11 @@ def test_overlap_matches_cpu(gpu, kitti00):
         n = len(kitti00["source_points"])
         assert round(gpu.overlap_gpu(vm, src, T) * n) == round(om.overlap(kitti00["source_points"], T) * n)
     idx = vm.lookup(src, np.eye(4))
-    oidx = np.array([om.lookup_coord(np.floor(p.astype(np.float64) / 0.5).astype(int)) for p in kitti00["source_points"][:500]])
-    assert ((idx[:500] >= 0) == (oidx >= 0)).all()
+    floor_coords = np.floor(kitti00["source_points"].astype(np.float64) / 0.5).astype(int)
+    oidx = np.array([om.lookup_coord(c) for c in floor_coords])
+    assert ((idx >= 0) == (oidx >= 0)).all()  # every point, not a sample
+    coords = vm.download_f64()[0]
+    np.testing.assert_array_equal(coords[idx[idx >= 0]], floor_coords[idx >= 0])  # and the voxel a hit names is the point's own
 
 
 def test_intensity_max_semantics(gpu, kitti00):
