@@ -27,7 +27,16 @@ from .features import (  # noqa: F401
     estimate_normals_covariances_gpu,
     estimate_normals_gpu,
 )
-from .sampling import VoxelGridPlan, randomgrid_sampling_gpu, sample_gpu, voxelgrid_sampling_gpu  # noqa: F401
+from .sampling import (  # noqa: F401
+    VoxelGridPlan,
+    filter_gpu,
+    find_inlier_points_gpu,
+    randomgrid_sampling_gpu,
+    remove_outliers_gpu,
+    sample_gpu,
+    sort_by_time_gpu,
+    voxelgrid_sampling_gpu,
+)
 from .solver import (  # noqa: F401
     BetweenFactorPose3,
     DenseLinearSystemGPU,
@@ -64,6 +73,10 @@ __all__ = [
     "merge_frames_gpu",
     "VoxelGridPlan",
     "sample_gpu",
+    "find_inlier_points_gpu",
+    "remove_outliers_gpu",
+    "filter_gpu",
+    "sort_by_time_gpu",
     "voxelgrid_sampling_gpu",
     "randomgrid_sampling_gpu",
     "BetweenFactorPose3",

@@ -936,6 +936,76 @@ __global__ void __launch_bounds__(128) knn_kernel(SearchView g, const float* __r
   if (num_found) num_found[i] = top.found;
 }
 
+// find_inlier_points (point_cloud_cpu_funcs.cpp:576-600) without its neighbour lists: one query per lane as knn_kernel, but the list never leaves the registers --
+// d_i = (sum_{j < k} sqrt(d2_j)) / k in list order (ascending distance; the point itself comes first with 0), 8 B per point stored instead of 12 k B.
+// SHORT points -- a non-finite coordinate (no search is run for it) or fewer than k neighbours in the cloud -- store +inf and are counted.
+
+template <int KMAX>
+__global__ void __launch_bounds__(128) mean_neighbor_distance_kernel(SearchView g, const float* __restrict__ points, int n, int k, double* __restrict__ mean_dists,
+                                                                     int* __restrict__ num_short) {
+  const int i = blockIdx.x * 128 + threadIdx.x;
+  if (i >= n) return;
+  const float x = points[3 * (size_t)i], y = points[3 * (size_t)i + 1], z = points[3 * (size_t)i + 2];
+  double mean = __longlong_as_double(0x7ff0000000000000ll);
+  if (finite3(x, y, z)) {
+    TopK<KMAX> top;
+    top.init(k, 1.7976931348623157e308);
+    knn_query_any<KMAX>(g, (double)x, (double)y, (double)z, 2 * k, top);
+    if (top.found >= k) {
+      double sum = 0.0;
+#pragma unroll
+      for (int j = 0; j < KMAX; j++)
+        if (j < k) sum += sqrt(top.d[j]);
+      mean = sum / (double)k;
+    }
+  }
+  mean_dists[i] = mean;
+  if (num_short && !(mean < 1.7976931348623157e308)) atomicAdd(num_short, 1);
+}
+
+// the same quantity from the caller's neighbour lists (the overload that takes them, :576-617): differences in f64 on the f32 coordinates, summed in list order.  An index
+// outside [0, n) makes the point short and is never dereferenced; so does a non-finite coordinate of the point or of a listed neighbour.
+__global__ void __launch_bounds__(256) mean_neighbor_distance_from_kernel(const float* __restrict__ points, int n, const int* __restrict__ neighbors, int k,
+                                                                          double* __restrict__ mean_dists, int* __restrict__ num_short) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (size_t)n) return;
+  const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
+  const double qx = (double)x, qy = (double)y, qz = (double)z;
+  bool ok = finite3(x, y, z);
+  double sum = 0.0;
+  for (int j = 0; j < k && ok; j++) {
+    const int nb = neighbors[i * (size_t)k + j];
+    ok = nb >= 0 && nb < n;
+    if (ok) {
+      const float vx = points[3 * (size_t)nb], vy = points[3 * (size_t)nb + 1], vz = points[3 * (size_t)nb + 2];
+      // the search's own expression.  That the two paths give the same bits rests on the compiler contracting it the same way in both kernels: not guaranteed by
+      // construction (the search's kernels are left as they are), held by tests/test_outliers_gpu.py on every build
+      const double ddx = (double)vx - qx, ddy = (double)vy - qy, ddz = (double)vz - qz;
+      sum += sqrt(ddx * ddx + ddy * ddy + ddz * ddz);
+    }
+  }
+  const double mean = sum / (double)k;
+  ok = ok && mean < 1.7976931348623157e308;  // (false for inf and NaN)
+  mean_dists[i] = ok ? mean : __longlong_as_double(0x7ff0000000000000ll);
+  if (num_short && !ok) atomicAdd(num_short, 1);
+}
+
+// *num_short (when asked for) through a zeroed device counter behind the kernel: the one wait of gp_cloud_mean_neighbor_distances / _from
+template <typename Launch>
+int count_short_points(int* num_short, hipStream_t s, const Launch& launch) {
+  if (!num_short) return launch(nullptr);
+  DeviceArray counter;
+  GP_TRY(counter.alloc_pooled(sizeof(int), s));
+  GP_HIP(hipMemsetAsync(counter.ptr, 0, sizeof(int), s));
+  GP_TRY(launch(counter.as<int>()));
+  HostWords hw;
+  GP_TRY(HostWords::get(&hw));
+  GP_TRY(hw.finish(s, counter.as<int>(), 8));
+  *num_short = reinterpret_cast<volatile int*>(hw.host)[8];
+  counter.release_on(s);
+  return GP_OK;
+}
+
 // ---- Eigen 3.4.0 SelfAdjointEigenSolver<Matrix3d>::computeDirect, restated from the published closed-form algorithm -----
 __device__ __forceinline__ void eig3_roots(const double* m /*col-major sym*/, double* roots) {
   const double s_inv3 = 1.0 / 3.0, s_sqrt3 = 1.7320508075688772;
@@ -2349,6 +2419,39 @@ int gp_knn_search(const gp_point_grid_t* g, const float* queries_dev, int nq, in
     hipLaunchKernelGGL(gp::knn_kernel<32>, grid, block, 0, s, v, queries_dev, nq, k, max_sq_dist, indices_dev, sq_dists_dev, num_found_dev);
   GP_HIP(hipGetLastError());
   return GP_OK;
+}
+
+int gp_cloud_mean_neighbor_distances(const gp_point_grid_t* g, const float* points_dev, int n, int k, double* mean_dists_dev, int* num_short, gp_stream_t stream) {
+  if (n < 0 || k < 1 || k > 32) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_mean_neighbor_distances: bad arguments (n >= 0, 1 <= k <= 32)");
+  if (n > 0 && (!g || !points_dev || !mean_dists_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_mean_neighbor_distances: NULL grid / array");
+  if (num_short) *num_short = 0;
+  if (n == 0) return GP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  const gp::SearchView v = g->view();
+  const dim3 grid((n + 127) / 128), block(128);
+  return gp::count_short_points(num_short, s, [&](int* counter) {
+    if (k == 1)
+      hipLaunchKernelGGL(gp::mean_neighbor_distance_kernel<1>, grid, block, 0, s, v, points_dev, n, k, mean_dists_dev, counter);
+    else if (k <= 10)
+      hipLaunchKernelGGL(gp::mean_neighbor_distance_kernel<10>, grid, block, 0, s, v, points_dev, n, k, mean_dists_dev, counter);
+    else
+      hipLaunchKernelGGL(gp::mean_neighbor_distance_kernel<32>, grid, block, 0, s, v, points_dev, n, k, mean_dists_dev, counter);
+    GP_HIP(hipGetLastError());
+    return (int)GP_OK;
+  });
+}
+
+int gp_cloud_mean_neighbor_distances_from(const float* points_dev, int n, const int* neighbors_dev, int k, double* mean_dists_dev, int* num_short, gp_stream_t stream) {
+  if (n < 0 || k < 1) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_mean_neighbor_distances_from: bad arguments (n >= 0, k >= 1)");
+  if (n > 0 && (!points_dev || !neighbors_dev || !mean_dists_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_mean_neighbor_distances_from: NULL array");
+  if (num_short) *num_short = 0;
+  if (n == 0) return GP_OK;
+  hipStream_t s = (hipStream_t)stream;
+  return gp::count_short_points(num_short, s, [&](int* counter) {
+    hipLaunchKernelGGL(gp::mean_neighbor_distance_from_kernel, dim3((n + 255) / 256), dim3(256), 0, s, points_dev, n, neighbors_dev, k, mean_dists_dev, counter);
+    GP_HIP(hipGetLastError());
+    return (int)GP_OK;
+  });
 }
 
 int gp_estimate_covariances(const float* points_dev, int n, int k, double cell_size, float* covs_dev, int* num_short, gp_stream_t stream) {

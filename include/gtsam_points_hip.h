@@ -668,6 +668,32 @@ int gp_cloud_gather(const float* attr_dev, int width, const int* indices_dev, in
 int gp_debug_voxelgrid_hooks(int force_wide_keys, int sort_faults);
 unsigned gp_debug_sample_hash(unsigned long long seed, unsigned index);
 
+/* ---- remove_outliers / filter / sort_by_time on the device: index selections for gp_cloud_gather (gp_knn.hip, gp_sampling.hip) ----
+ * Device counterparts of find_inlier_points / remove_outliers (point_cloud_cpu_funcs.cpp:576-650), filter / filter_by_index (point_cloud_cpu.hpp:158-203) and
+ * sort_by_time (point_cloud_cpu_funcs.cpp:459-465); CPU-only upstream.  Each produces int indices; sample() = gp_cloud_gather carries the attributes.
+ * mean_neighbor_distances: d_i = (sum_{j < k} |p_nbr(i,j) - p_i|) / k over the k nearest points of the cloud itself (the point is its own first neighbour, distance
+ *   0), 1 <= k <= 32, on a gp_point_grid built over these same points.  One fused kernel: the search's list stays in registers, the k square roots are added in list
+ *   order (ascending distance, so the sum does not depend on which of several equidistant neighbours the search kept) in f64, one double per point is stored; no
+ *   [n][k] array exists on this path.  SHORT points -- a non-finite coordinate, or fewer than k neighbours (n < k) -- store +inf and are counted in *num_short
+ *   (host int, may be NULL; the call waits only when it is given).
+ * mean_neighbor_distances_from: the same from the caller's lists neighbors_dev int[n][k], any k >= 1 (the second upstream overload); differences in f64 on the f32
+ *   coordinates, written as the search writes them (the tests hold the two paths to the same bytes; by contract they agree to (k + 8) 2^-52 d_i).  An index outside [0, n) makes the point short and is never dereferenced.
+ * inlier_threshold: over the FINITE entries of mean_dists (m of them): mean = sum d / m, var = sum d^2 / m - mean^2 (one pass, not clamped, :598-600),
+ *   thresh = mean + sqrt(var) * std_thresh; stats_host double[4] = {mean, var, thresh, m}; m = 0 gives all zeros.  Sums in f64 in an order fixed by n alone
+ *   (per-workgroup partials in workgroup order, lanes in a shuffle tree): two runs are bit-identical.  Waits.
+ * select_below: the i with values[i] < thresh (strict) and values[i] finite; select_mask: the i with mask[i] != 0.  Both write ascending indices to
+ *   indices_out_dev (capacity n) and wait: *num_selected is valid on return.
+ * sort_by_time_indices: the permutation that sorts times ascending, stable (equal times in ascending index -- one of std::sort's legal outcomes); -0.0 = +0.0,
+ *   NaN times last in ascending index.  indices_out_dev int[n].  Waits (for the radix sort's fault words; a faulted sort runs again in its one-class form).
+ * GP_ERROR_INVALID_ARGUMENT before any device work: NULL arrays with n > 0, n < 0, k outside its range, a std_thresh that is not finite.  n == 0 is legal
+ * everywhere: nothing is launched, nothing selected. */
+int gp_cloud_mean_neighbor_distances(const gp_point_grid_t* grid, const float* points_dev, int n, int k, double* mean_dists_dev, int* num_short, gp_stream_t stream);
+int gp_cloud_mean_neighbor_distances_from(const float* points_dev, int n, const int* neighbors_dev, int k, double* mean_dists_dev, int* num_short, gp_stream_t stream);
+int gp_cloud_inlier_threshold(const double* mean_dists_dev, int n, double std_thresh, double* stats_host, gp_stream_t stream);
+int gp_cloud_select_below(const double* values_dev, int n, double thresh, int* indices_out_dev, int* num_selected, gp_stream_t stream);
+int gp_cloud_select_mask(const unsigned char* mask_dev, int n, int* indices_out_dev, int* num_selected, gp_stream_t stream);
+int gp_cloud_sort_by_time_indices(const float* times_dev, int n, int* indices_out_dev, gp_stream_t stream);
+
 /* the symbolic phase alone (pure host code, no device needed): elimination order perm[k] = slot eliminated k-th, elimination tree
  * parent[k] (-1 = root), block counts and the schedule; any output pointer may be NULL */
 int gp_sparse_symbolic(int num_slots, const int* factor_slots, int num_factors, int ordering, int* perm_out, int* parent_out, int64_t* nnz_a_blocks, int64_t* nnz_l_blocks,
