@@ -239,6 +239,8 @@ _SIGNATURES = {
     "gp_debug_drop_error_words": (C.c_int, [C.c_void_p, C.c_int]),
     "gp_trim_device_cache": (C.c_int, []),
     "gp_vgicp_batch_issue_linearize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gp_vgicp_batch_takes_rigid_path": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
+    "gp_vgicp_factor_takes_rigid_path": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int)]),
     "gp_vgicp_batch_issue_compute_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_compute_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_issue_compute_error_dev_begin": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -315,6 +317,7 @@ GP_TUNE_TEST_ARRIVAL_SKEW = 20
 GP_TUNE_SOURCE_MIRROR, GP_TUNE_EFFECTIVE_MIRROR = 21, 22
 GP_TUNE_EXPERIMENT = 23
 GP_TUNE_BUCKET_LOAD = 24
+GP_TUNE_FAR_POSE_RATIO = 25
 GP_TUNE_MAP_BUILD, GP_TUNE_KNN_STRUCTURE = 16, 32
 KERNEL_FAMILIES = [GP_KERNEL_REFERENCE, GP_KERNEL_HASHED, GP_KERNEL_GRID_F64, GP_KERNEL_LOOKAHEAD, GP_KERNEL_STREAM]
 

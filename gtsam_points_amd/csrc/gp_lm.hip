@@ -50,6 +50,7 @@ struct gp_lm_graph {
   gp::DeviceArray d_pose_factors;
   gp::PinnedArray h_pose_errors;
   std::vector<int> slot;
+  std::vector<int> pairs;      // host copy of the VGICP factors' (target pose, source pose), for the far-pose rule at set_values
   gp::DeviceArray d_pairs, d_slot, d_values[2], d_deltas[2], d_records[2];
   gp::PinnedArray h_values[2];
   int cur = 0;                 // d_values[cur] / d_deltas[cur] / h_values[cur] are the current values; [1 - cur] the last trial's
@@ -144,6 +145,7 @@ static int create_graph(gp_vgicp_batch_t* batch, int F, const int* pose_pairs, c
   if (rc == GP_OK && P > 0 && hipMemcpy(g->d_pose_factors.ptr, pose_factors, sizeof(gp_pose_factor) * (size_t)P, hipMemcpyHostToDevice) != hipSuccess)
     rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the pose factors");
   g->errors.assign((size_t)F, 0.0);
+  if (F > 0) g->pairs.assign(pose_pairs, pose_pairs + 2 * (size_t)F);
   if (rc == GP_OK && F > 0 && hipMemcpy(g->d_pairs.ptr, pose_pairs, sizeof(int) * 2 * (size_t)F, hipMemcpyHostToDevice) != hipSuccess) rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the pairs");
   if (rc == GP_OK && hipMemcpy(g->d_slot.ptr, g->slot.data(), sizeof(int) * (size_t)num_poses, hipMemcpyHostToDevice) != hipSuccess) rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create: upload of the slots");
   if (rc != GP_OK) {
@@ -196,6 +198,22 @@ int gp_lm_graph_set_values(gp_lm_graph_t* g, const double* values_host) {
   for (int i = 0; i < g->N; i++) rigid = rigid && gp::pose_is_rigid(values_host + 16 * (size_t)i);
   if (g->P > 0 && !rigid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_set_values: a graph with pose factors takes rigid values (orthonormal to 1e-9, det > 0)");
   GP_HIP(hipStreamSynchronize(g->stream));  // (a trial in flight still writes the pinned values)
+  if (rigid && g->batch && g->F > 0) {
+    // ... and no factor's relative pose inverse(T_t) T_s is far from its source cloud (gp_vgicp_batch_takes_rigid_path: the rule of the host-pose entry points, decided
+    // here for the values as set; the retracts that follow move them by steps, not by kilometres).  Only |t| of the relative pose enters the rule, and
+    // |Ra^T (tb - ta)| = |tb - ta|: the rotation blocks asked about are identities, so that rounding in a product of two rotations cannot change the answer above
+    std::vector<double> rel(16 * (size_t)g->F, 0.0);
+    for (int f = 0; f < g->F; f++) {
+      const double* A = values_host + 16 * (size_t)g->pairs[2 * (size_t)f];
+      const double* B = values_host + 16 * (size_t)g->pairs[2 * (size_t)f + 1];
+      double* D = rel.data() + 16 * (size_t)f;  // column-major
+      D[0] = D[5] = D[10] = D[15] = 1.0;
+      for (int r = 0; r < 3; r++) D[12 + r] = B[12 + r] - A[12 + r];
+    }
+    int near = 1;
+    GP_TRY(gp_vgicp_batch_takes_rigid_path(g->batch, rel.data(), &near));
+    rigid = near != 0;
+  }
   g->rigid = rigid;
   memcpy(g->h_values[g->cur].ptr, values_host, sizeof(double) * 16 * (size_t)g->N);
   GP_HIP(hipMemcpyAsync(g->d_values[g->cur].ptr, g->h_values[g->cur].ptr, sizeof(double) * 16 * (size_t)g->N, hipMemcpyHostToDevice, g->stream));

@@ -458,6 +458,7 @@ struct gp_vgicp_tuning {
   int balance = kDefaultSkewPermille;  // stream kernel, one large factor: how much more a dispatch round takes than the next, in 1/1000 of the mean share (0 = flat)
   int experiment = 0;             // GP_TUNE_EXPERIMENT: measurement instantiations of the stream kernel (gp_vgicp_stream.hpp, EXP), 0 = the product kernel
   int source_mirror = 1;          // stream family: stream the sources' packed mirrors (36 B per point, gp::SourceMirror) when every factor of the batch has one; 0 = the caller's arrays
+  int far_pose_ratio = GP_FAR_POSE_RATIO_DEFAULT;  // GP_TUNE_FAR_POSE_RATIO: a rigid pose with |t| > this x the source cloud's extent takes the explicit-J_s sums (0 = none does)
 };
 
 struct gp_vgicp_factor {
@@ -469,6 +470,8 @@ struct gp_vgicp_factor {
   int device = 0;  // the device the source arrays live on (hipPointerGetAttributes at creation)
   bool surface_validation = false;
   uint64_t generation = 0;  // bumped when the source pointers or flags change (tables that hold this factor go stale)
+  double extent = 0.0;      // largest |coordinate| of the source's finite points (source_extent_kernel, at the first table build that holds this factor) ...
+  uint64_t extent_generation = ~0ull;  // ... for this generation of the source arrays
   double inlier_thresh_trans = 1e-6, inlier_thresh_angle = 1e-6;  // integrated_vgicp_derivatives.cu:26-27 (kept for API parity)
   hipStream_t stream = nullptr;
   bool owns_stream = false;
@@ -659,6 +662,52 @@ int make_stream_plan(int n, int skew_permille, const int* xcd_weights, gp::Strea
 }
 constexpr int kPlanMinPoints = 65536;  // single factors below this keep the fixed tiles of a batch (their records then do not depend on how they are batched)
 
+// largest |coordinate| over a cloud's finite points, as the bits of a non-negative float (ordered like the unsigned integers they read as)
+__global__ void __launch_bounds__(256) source_extent_kernel(const float* __restrict__ points, long long count /* 3 n */, unsigned* __restrict__ out) {
+  float m = 0.f;
+  for (long long i = blockIdx.x * 256ll + threadIdx.x; i < count; i += 256ll * gridDim.x) {
+    const float v = fabsf(points[i]);
+    if (v <= 3.402823466e38f) m = fmaxf(m, v);  // (NaN and infinity: no)
+  }
+  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_down(m, o));
+  if ((threadIdx.x & 63) == 0) atomicMax(out, __float_as_uint(m));
+}
+
+// the extents of the batch's sources, for the far-pose rule (takes_rigid_path): one launch per factor whose source arrays changed, one wait for all of them -- here, where
+// a table upload synchronises anyway
+int measure_extents(gp_vgicp_batch* b) {
+  const int F = (int)b->factors.size();
+  std::vector<int> todo;
+  for (int i = 0; i < F; i++) {
+    gp_vgicp_factor* f = b->factors[i];
+    if (f->extent_generation == f->generation) continue;
+    if (f->n > 0) todo.push_back(i);
+    else f->extent = 0.0, f->extent_generation = f->generation;
+  }
+  if (todo.empty()) return GP_OK;
+  gp::DeviceArray d_ext;
+  GP_TRY(d_ext.alloc(sizeof(unsigned) * todo.size()));
+  GP_HIP(hipMemsetAsync(d_ext.ptr, 0, sizeof(unsigned) * todo.size(), b->stream));
+  for (size_t k = 0; k < todo.size(); k++) {
+    const gp_vgicp_factor* f = b->factors[todo[k]];
+    const long long count = 3ll * f->n;
+    const int wgs = (int)std::min<long long>(1024, (count + 255) / 256);
+    hipLaunchKernelGGL(source_extent_kernel, dim3(wgs), dim3(256), 0, b->stream, f->points, count, d_ext.as<unsigned>() + k);
+  }
+  GP_HIP(hipGetLastError());
+  std::vector<unsigned> h(todo.size());
+  GP_HIP(hipMemcpyAsync(h.data(), d_ext.ptr, sizeof(unsigned) * todo.size(), hipMemcpyDeviceToHost, b->stream));
+  GP_HIP(hipStreamSynchronize(b->stream));
+  for (size_t k = 0; k < todo.size(); k++) {
+    gp_vgicp_factor* f = b->factors[todo[k]];
+    float v;
+    memcpy(&v, &h[k], sizeof(v));
+    f->extent = (double)v;
+    f->extent_generation = f->generation;
+  }
+  return GP_OK;
+}
+
 int build_table(gp_vgicp_batch* b) {
   const int F = (int)b->factors.size();
   std::vector<gp::FactorDesc> descs((size_t)F);
@@ -808,6 +857,7 @@ int build_table(gp_vgicp_batch* b) {
   // the table upload is synchronous (pageable source); it happens once per factor-set change, not per linearise
   if (F) GP_HIP(hipMemcpy(b->d_factors.ptr, descs.data(), sizeof(gp::FactorDesc) * (size_t)F, hipMemcpyHostToDevice));
   if (b->num_tiles) GP_HIP(hipMemcpy(b->d_tiles.ptr, tiles.data(), sizeof(gp::TileDesc) * (size_t)b->num_tiles, hipMemcpyHostToDevice));
+  GP_TRY(measure_extents(b));
   b->seen.resize((size_t)F);
   for (int i = 0; i < F; i++) b->seen[i] = b->factors[i]->generation + b->factors[i]->target->generation;
   b->table_dirty = false;
@@ -848,6 +898,25 @@ bool poses_are_rigid(const double* poses_host, size_t F) {
   if (!poses_host) return false;
   for (size_t i = 0; i < F; i++)
     if (!gp::pose_is_rigid(poses_host + 16 * i)) return false;
+  return true;
+}
+
+// does the batch (table built) take the 29-sum kernels + adjoint expansion at these poses?  Every 3x3 block orthonormal, and no pose FAR: the 29 sums are formed
+// in f32 from q = R p + t, so H_t carries rounding of size |q|^2 M, and the expansion H_s = Ad^T H_t Ad (of size |p|^2 M) cancels about (|t| / |p|)^2 of it -- a
+// scan registered against a map whose origin is kilometres away.  A pose with |t| > far_pose_ratio x the source's extent (largest |coordinate|) therefore takes the
+// explicit-J_s sums like a non-orthonormal one (all f64, summed from p: nothing cancels).  Per call and per batch, like the orthonormality test.
+bool takes_rigid_path(const gp_vgicp_batch* b, const double* poses_host) {
+  const size_t F = b->factors.size();
+  if (!poses_are_rigid(poses_host, F)) return false;
+  const double ratio = (double)b->tuning.far_pose_ratio;
+  if (ratio <= 0.0) return true;
+  for (size_t i = 0; i < F; i++) {
+    const gp_vgicp_factor* f = b->factors[i];
+    if (f->n <= 0) continue;
+    const double* t = poses_host + 16 * i + 12;
+    const double lim = ratio * f->extent;
+    if (t[0] * t[0] + t[1] * t[1] + t[2] * t[2] > lim * lim) return false;
+  }
   return true;
 }
 
@@ -1085,6 +1154,10 @@ static int apply_tuning(gp_vgicp_tuning* t, int key, int value) {
       if (value < 0 || value > 2) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "GP_TUNE_EXPERIMENT: 0 (off), 1 (block-grid warm-up), 2 (f32 covariance rotation: breaks parity, timing only)");
       t->experiment = value;
       return GP_OK;
+    case GP_TUNE_FAR_POSE_RATIO:
+      if (value < 0 || value > 1000000) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "GP_TUNE_FAR_POSE_RATIO: 0 (no pose counts as far) .. 1000000 (x the source cloud's extent)");
+      t->far_pose_ratio = value;
+      return GP_OK;
     case GP_TUNE_BALANCE:
       if (value < -1 || value > 600) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "GP_TUNE_BALANCE: -1 (automatic), 0 (flat) .. 600 (per mille of the mean share per dispatch round)");
       t->balance = value;
@@ -1134,6 +1207,7 @@ int gp_vgicp_batch_get_tuning(const gp_vgicp_batch_t* b, int key, int* value) {
     case GP_TUNE_EFFECTIVE_KERNEL: *value = b->table_dirty ? -1 : b->family; return GP_OK;  // what the last table build resolved GP_TUNE_KERNEL to
     case GP_TUNE_SOURCE_MIRROR: *value = b->tuning.source_mirror; return GP_OK;
     case GP_TUNE_EXPERIMENT: *value = b->tuning.experiment; return GP_OK;
+    case GP_TUNE_FAR_POSE_RATIO: *value = b->tuning.far_pose_ratio; return GP_OK;
     case GP_TUNE_EFFECTIVE_MIRROR: *value = b->table_dirty ? -1 : (b->packed ? 1 : 0); return GP_OK;  // does the built table stream the packed mirrors?
     default: return gp::fail(GP_ERROR_INVALID_ARGUMENT, "unknown GP_TUNE_* key");
   }
@@ -1266,7 +1340,7 @@ int gp_vgicp_factor_issue_linearize(gp_vgicp_factor_t* f, const double* pose_hos
   } else {
     ps.d_lin = pose_dev;
   }
-  return launch_linearize(f->self_batch, ps, out_dev, poses_are_rigid(pose_host, 1));
+  return launch_linearize(f->self_batch, ps, out_dev, takes_rigid_path(f->self_batch, pose_host));
 }
 
 int gp_vgicp_factor_issue_compute_error(gp_vgicp_factor_t* f, const double* pose_lin_host, const double* pose_eval_host, const double* pose_lin_dev,
@@ -1408,7 +1482,23 @@ int gp_vgicp_batch_issue_linearize(gp_vgicp_batch_t* b, const double* poses_host
   if (b->factors.empty()) return GP_OK;
   PoseSource ps;
   GP_TRY(stage_poses(b, poses_host, nullptr, &ps));
-  return launch_linearize(b, ps, out_dev, poses_are_rigid(poses_host, b->factors.size()));
+  return launch_linearize(b, ps, out_dev, takes_rigid_path(b, poses_host));
+}
+
+// which kernels the host-pose entry points run at these poses: 1 = the 29 sums + adjoint expansion (every 3x3 block orthonormal to 1e-9, no pose far from its
+// source cloud: takes_rigid_path), 0 = the explicit-J_s sums.  What a caller of gp_vgicp_batch_issue_linearize_dev passes as `rigid` to choose the same.
+int gp_vgicp_batch_takes_rigid_path(gp_vgicp_batch_t* b, const double* poses_host, int* out) {
+  if (!b || !poses_host || !out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_vgicp_batch_takes_rigid_path: null");
+  if (table_is_stale(b)) GP_TRY(build_table(b));
+  *out = takes_rigid_path(b, poses_host) ? 1 : 0;
+  return GP_OK;
+}
+
+int gp_vgicp_factor_takes_rigid_path(gp_vgicp_factor_t* f, const double pose[16], int* out) {
+  if (!f || !pose || !out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_vgicp_factor_takes_rigid_path: null");
+  GP_TRY(ensure_self_batch(f));
+  *out = takes_rigid_path(f->self_batch, pose) ? 1 : 0;
+  return GP_OK;
 }
 
 int gp_vgicp_batch_issue_compute_error(gp_vgicp_batch_t* b, const double* poses_lin_host, const double* poses_eval_host, double* out_dev) {
@@ -1672,7 +1762,7 @@ static int batch_linearize_sync(gp_vgicp_batch_t* b, const double* poses_host, g
   PoseSource ps;
   GP_TRY(stage_poses(b, poses_host, nullptr, &ps, true));
   const gp::DoneFlags done{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq, b->trace ? b->trace + 2047 * 16 : nullptr};
-  const bool rigid = poses_are_rigid(poses_host, F);
+  const bool rigid = takes_rigid_path(b, poses_host);
   const int parts = (F == 1 && rigid && b->num_tiles >= kFinalizeSplitTiles) ? finalize_parts() : 1;
   constexpr bool host_expand = true;  // the parts deliver their 32 sums, the host expands once (the parts expanding: measured slower, round 2)
   const bool sums_only = parts > 1 && host_expand;
@@ -1912,14 +2002,14 @@ int gp_vgicp_batch_time_linearize(gp_vgicp_batch_t* b, const double* poses_host,
   const size_t F = b->factors.size();
   if (F == 0) return GP_OK;
   // the device work of the SYNCHRONOUS call (gp_vgicp_batch_linearize), incl. its split finalize for a single large factor
-  const int parts = (F == 1 && poses_are_rigid(poses_host, F) && b->num_tiles >= kFinalizeSplitTiles) ? finalize_parts() : 1;
+  const int parts = (F == 1 && takes_rigid_path(b, poses_host) && b->num_tiles >= kFinalizeSplitTiles) ? finalize_parts() : 1;
   gp::DeviceArray d_out;
   GP_TRY(d_out.alloc(sizeof(gp_linearized6) * F * (size_t)parts));
   PoseSource ps;
   GP_TRY(stage_poses(b, poses_host, nullptr, &ps));
   double* partials = nullptr;
   GP_TRY(partials_ptr(b, &partials));
-  const bool rigid = poses_are_rigid(poses_host, F);
+  const bool rigid = takes_rigid_path(b, poses_host);
   hipEvent_t e0, e1, e2;
   GP_HIP(hipEventCreate(&e0));
   GP_HIP(hipEventCreate(&e1));

@@ -298,6 +298,13 @@ int gp_vgicp_batch_sync(gp_vgicp_batch_t* batch);
  * nothing is staged or copied, the host has nothing to wait for.  Same kernels, same records.  rigid != 0: the caller vouches that every 3x3 block is orthonormal to
  * 1e-9 -- the test the host-pose entry points make themselves to choose between the 29-sum kernel + adjoint expansion and the 92-sum kernel that is exact for any block */
 int gp_vgicp_batch_issue_linearize_dev(gp_vgicp_batch_t* batch, const double* poses_dev, int rigid, gp_linearized6* out_dev);
+/* Which kernels the host-pose entry points run at these poses (double[F][16] / double[16], column-major): *out = 1, the 29 sums + adjoint expansion -- every 3x3
+ * block orthonormal to 1e-9 and no pose FAR, i.e. |t| <= GP_TUNE_FAR_POSE_RATIO x the largest |coordinate| of the factor's source cloud; *out = 0, the explicit-J_s
+ * sums (all f64, from the source point itself).  The expansion H_s = Ad^T H_t Ad cancels about (|t| / |p|)^2 of the f32 rounding in H_t, so a scan registered against
+ * a map whose origin is kilometres away takes the explicit sums.  One far or non-orthonormal pose decides for the whole batch.  Pass the answer as `rigid` to
+ * gp_vgicp_batch_issue_linearize_dev to get what the host-pose entry points would run (gp_lm_graph_set_values does). */
+int gp_vgicp_batch_takes_rigid_path(gp_vgicp_batch_t* batch, const double* poses_host, int* out);
+int gp_vgicp_factor_takes_rigid_path(gp_vgicp_factor_t* factor, const double pose[16], int* out);
 int gp_vgicp_batch_issue_compute_error_dev(gp_vgicp_batch_t* batch, const double* poses_lin_dev, const double* poses_eval_dev, double* out_dev);
 /* ... and the error evaluation as a synchronous call that POLLS the finalize kernel's completion words (pinned) instead of synchronising the stream: on return everything
  * queued in front of it on the batch's stream is complete, work queued behind it meanwhile is not waited for.  _begin / _end: the same in two halves (one begin at a time). */
@@ -722,6 +729,7 @@ int gp_debug_sparse_work_lists(int num_slots, const int* factor_slots, int num_f
  *                        surface validation inside the ring.  Default.
  * (The A/B switches of rounds 2-3 -- poses by copy engine, finalize parts / width / host expansion, the fused GICP kernel -- were measured, decided and removed:
  *  profiles/r02_*, r03_*, DESIGN.md.) */
+#define GP_FAR_POSE_RATIO_DEFAULT 2
 enum {
   GP_KERNEL_REFERENCE = 0,
   GP_KERNEL_HASHED = 2,
@@ -760,6 +768,10 @@ enum {
   GP_TUNE_TIMING = 7,           /* measurement: 1 = gp_vgicp_batch_linearize brackets its two kernels with HIP events (gp_vgicp_batch_last_kernel_ms) */
   GP_TUNE_MAP_BUILD = 16,       /* gp_voxelmap: 1 = reference-shaped hashed build (atomicCAS claims + atomic sums; also the fallback of clouds whose
                                    bounding box is too large for the block grid), 0 = binned deterministic build (default) */
+  GP_TUNE_FAR_POSE_RATIO = 25,  /* VGICP factors / batches: a rigid pose whose translation exceeds `value` x the source cloud's extent (largest |coordinate|) takes the explicit-J_s
+                                   sums instead of the 29 f32 sums + adjoint expansion (gp_vgicp_batch_takes_rigid_path); 0 = no pose counts as far (measurement: the rigid
+                                   sums at any distance).  Default GP_FAR_POSE_RATIO_DEFAULT: half the largest ratio at which the rigid sums were measured inside 1e-6 of
+                                   the f64 reference */
   GP_TUNE_BUCKET_LOAD = 24,     /* gp_voxelmap (binned build): load factor in per cent (5 .. 90, default 33) at which the reference-visible bucket table enters the reference's doubling
                                    sequence (gaussian_voxelmap_gpu.cu:269-291).  At 50 .. 67 % some probe chain among 10^5 voxels exceeds max_bucket_scan_count almost surely and the failed
                                    attempt costs a fill + an insertion pass + a wait; 33 % means up to twice the entries (16 B each) of a table sized at 67 % */
