@@ -23,27 +23,44 @@
 
 namespace gp {
 
-__device__ __forceinline__ void point_coord(const float* __restrict__ points, int i, double inv_leaf, int& cx, int& cy, int& cz) {
-  cx = fast_floor((double)points[3 * (size_t)i] * inv_leaf);
-  cy = fast_floor((double)points[3 * (size_t)i + 1] * inv_leaf);
-  cz = fast_floor((double)points[3 * (size_t)i + 2] * inv_leaf);
+// A point belongs to a voxel iff all three |p / leaf| < 1e9: the binned build's rule (gp_binning.hip, point_cell), false for NaN / inf.  Both builds apply it:
+// on the device (int)NaN is 0, i.e. voxel (0, 0, 0), and an infinite coordinate saturates into a voxel of its own.
+__device__ __forceinline__ bool voxel_of(double px, double py, double pz, double inv_leaf, int& cx, int& cy, int& cz) {
+  const double ux = px * inv_leaf, uy = py * inv_leaf, uz = pz * inv_leaf;
+  const bool ok = fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9;
+  cx = ok ? fast_floor(ux) : 0;
+  cy = ok ? fast_floor(uy) : 0;
+  cz = ok ? fast_floor(uz) : 0;
+  return ok;
 }
+__device__ __forceinline__ bool point_coord(const float* __restrict__ points, int i, double inv_leaf, int& cx, int& cy, int& cz) {
+  return voxel_of((double)points[3 * (size_t)i], (double)points[3 * (size_t)i + 1], (double)points[3 * (size_t)i + 2], inv_leaf, cx, cy, cz);
+}
+
+// Voxel intensity, ONE rule for both builds: the CPU map's std::max from 0.0 (gaussian_voxelmap_cpu.cpp:34-35), `cur < x ? x : cur` -- a negative value, -0.0 and a
+// NaN leave +0.0.  (The reference's GPU map takes atomicMax of the bit patterns from 0, :138-139, which is the same for x >= +0 and lets every negative value, -0.0
+// and NaN win otherwise.)
+__device__ __forceinline__ float intensity_max(float cur, float x) { return cur < x ? x : cur; }
 
 // voxel_bucket_assignment_kernel (gaussian_voxelmap_gpu.cu:37-75): claim a bucket per distinct voxel coordinate.
 // rep[b] = index of the first point that claimed bucket b, or -1.
 __global__ void __launch_bounds__(256) claim_buckets_kernel(const float* __restrict__ points, int n, int* __restrict__ rep, uint32_t num_buckets,
-                                                            uint32_t mask, int max_scan, double inv_leaf, int* __restrict__ failures) {
+                                                            uint32_t mask, int max_scan, double inv_leaf, int* __restrict__ invalid,
+                                                            int* __restrict__ failures) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   int cx, cy, cz;
-  point_coord(points, i, inv_leaf, cx, cy, cz);
+  if (!point_coord(points, i, inv_leaf, cx, cy, cz)) {  // neither a member nor a failure: counted apart, so that the drop rate is over the valid points
+    atomicAdd(invalid, 1);
+    return;
+  }
   const uint64_t hash = coord_hash(cx, cy, cz);
   for (int j = 0; j < max_scan; j++) {
     const uint32_t b = bucket_index(hash, j, num_buckets, mask);
     const int old = atomicCAS(&rep[b], -1, i);
     if (old < 0) return;  // claimed an empty bucket
     int ox, oy, oz;
-    point_coord(points, old, inv_leaf, ox, oy, oz);
+    point_coord(points, old, inv_leaf, ox, oy, oz);  // (a representative is a valid point: only those claim)
     if (ox == cx && oy == cy && oz == cz) return;  // voxel already present
   }
   atomicAdd(failures, 1);  // probe chain exhausted: this point is dropped (gaussian_voxelmap_gpu.cu:67)
@@ -76,7 +93,8 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const double px = (double)points[3 * (size_t)i], py = (double)points[3 * (size_t)i + 1], pz = (double)points[3 * (size_t)i + 2];
-  const int cx = fast_floor(px * map.inv_leaf), cy = fast_floor(py * map.inv_leaf), cz = fast_floor(pz * map.inv_leaf);
+  int cx, cy, cz;
+  if (!voxel_of(px, py, pz, map.inv_leaf, cx, cy, cz)) return;  // NaN / inf / out of range: in no voxel
   const int v = lookup_voxel(map, cx, cy, cz);
   if (v < 0) return;  // dropped at table build
   double ox, oy, oz;
@@ -93,7 +111,12 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict
   unsafeAtomicAdd(s + 7, 0.5 * ((double)c[7] + (double)c[5]));  // yz
   unsafeAtomicAdd(s + 8, (double)c[8]);  // zz
   atomicAdd(counts + v, 1);
-  if (intensities) atomicMax(intensity_bits + v, __float_as_uint(intensities[i]));  // max intensity (:138-139)
+  if (intensities) {
+    // intensity_max over the voxel, from +0.0: only x > 0 can change it, and among positive floats (inf included) the order of the bit patterns is the order of
+    // the values -- atomicMax on the bits (:138-139) of those alone
+    const float x = intensities[i];
+    if (x > 0.0f) atomicMax(intensity_bits + v, __float_as_uint(x));
+  }
 }
 
 // finalize_voxels_kernel (:154-172): divide by the count; emit the gather record and the reference-visible arrays
@@ -236,7 +259,7 @@ __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __res
   int cx = 0, cy = 0, cz = 0;
   double ox = 0.0, oy = 0.0, oz = 0.0;  // the voxel's centre, from its first point -- taken from the batch that holds it (two dependent loads less in front of the gather)
   double acc[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  float imax = 0.0f;  // max intensity (:138-139): intensities are non-negative upstream (atomicMax on the float bits), 0 when absent
+  float imax = 0.0f;  // intensity_max from +0.0; 0 when the cloud has no intensities
   for (int batch = p0; batch < p1; batch += kStatsBatch) {
     const int cnt = min(kStatsBatch, p1 - batch);
     float row[kStatsBatch / 256][12];
@@ -281,7 +304,7 @@ __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __res
       acc[6] += (double)c[7];
       acc[7] += 0.5 * ((double)c[10] + (double)c[8]);
       acc[8] += (double)c[11];
-      imax = fmaxf(imax, inten[j - batch]);
+      imax = intensity_max(imax, inten[j - batch]);
     }
     __syncthreads();
   }
@@ -291,7 +314,7 @@ __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __res
     for (int off = kGroup / 2; off > 0; off >>= 1) acc[k] += __shfl_xor(acc[k], off, kGroup);
   }
 #pragma unroll
-  for (int off = kGroup / 2; off > 0; off >>= 1) imax = fmaxf(imax, __shfl_xor(imax, off, kGroup));
+  for (int off = kGroup / 2; off > 0; off >>= 1) imax = intensity_max(imax, __shfl_xor(imax, off, kGroup));
   if (!live) return;
   if (lane != 0) return;
   const int n = e - b;
@@ -664,13 +687,15 @@ int gp_voxelmap_insert(gp_voxelmap_t* map, const float* points_dev, const float*
     const uint32_t mask = ((num_buckets & (num_buckets - 1)) == 0) ? (uint32_t)(num_buckets - 1) : 0u;
     if (n > 0) {
       hipLaunchKernelGGL(gp::claim_buckets_kernel, dim3(grid_for(n)), dim3(kBlock), 0, s, points_dev, n, rep.as<int>(), (uint32_t)num_buckets, mask,
-                         m->info.max_bucket_scan_count, inv_leaf, counters.as<int>() + 1);
+                         m->info.max_bucket_scan_count, inv_leaf, counters.as<int>(), counters.as<int>() + 1);
       GP_HIP(hipGetLastError());
     }
     GP_HIP(hipMemcpyAsync(h_counters, counters.ptr, sizeof(int) * 2, hipMemcpyDeviceToHost, s));
     GP_HIP(hipStreamSynchronize(s));
-    if (h_counters[1] == 0 || (double)h_counters[1] / (double)n <= m->target_points_drop_rate) break;  // :288
+    // :288, over the VALID points (h_counters[0] = points in no voxel: NaN / inf / out of range -- neither failures nor members)
+    if (h_counters[1] == 0 || (double)h_counters[1] / (double)std::max(n - h_counters[0], 1) <= m->target_points_drop_rate) break;
   }
+  GP_HIP(hipMemsetAsync(counters.ptr, 0, sizeof(int), s));  // counters[0] becomes the voxel count
   m->info.num_buckets = (int)num_buckets;
   GP_TRY(m->buckets.alloc(sizeof(gp_voxel_bucket) * (size_t)num_buckets));
   // upper bound of the voxel count = number of claimed buckets <= min(n, num_buckets)
@@ -917,7 +942,12 @@ int gp_voxelmap_save_compact(const gp_voxelmap_t* map, const char* path) {
   if (!ofs) return gp::fail(GP_ERROR_IO, std::string("error: failed to open ") + path);
   // header of gaussian_voxelmap_gpu.cu:358-366
   ofs << "compact " << 1 << std::endl;
-  ofs << "resolution " << map->resolution << std::endl;
+  {  // every digit of the double: load rebuilds mean_local and every later floor(p / resolution) from this value (the stream's default is 6 significant digits)
+    std::ostringstream res;
+    res.precision(std::numeric_limits<double>::max_digits10);
+    res << map->resolution;
+    ofs << "resolution " << res.str() << std::endl;
+  }
   ofs << "lru_count " << 0 << std::endl;
   ofs << "lru_cycle " << 1 << std::endl;
   ofs << "lru_thresh " << 1 << std::endl;

@@ -129,3 +129,28 @@ def rigid(values):
         u, _, vt = np.linalg.svd(T[:3, :3])
         T[:3, :3] = u @ vt
     return out
+
+
+def reference_bucket_lookup(buckets, info, coord):
+    """lookup_voxel of cuda/kernels/vector3_hash.cuh:53-76 restated on the downloaded bucket table (rows of x, y, z, voxel index): linear probing over at most
+    max_bucket_scan_count buckets, stop at an empty one"""
+    M, mask = 0xC6A4A7935BD1E995, (1 << 64) - 1
+
+    def combine(h, k):
+        k = (k * M) & mask
+        k ^= k >> 47
+        k = (k * M) & mask
+        h ^= k
+        h = (h * M) & mask
+        return (h + 0xE6546B64) & mask
+
+    h = 0
+    for c in coord:
+        h = combine(h, int(c) & mask)
+    for i in range(info.max_bucket_scan_count):
+        b = buckets[((h + i) & mask) % info.num_buckets]
+        if b[3] < 0:
+            return -1
+        if tuple(b[:3]) == tuple(int(c) for c in coord):
+            return int(b[3])
+    return -1

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import expmap
+from helpers import expmap, reference_bucket_lookup
 
 pytestmark = pytest.mark.gpu
 
@@ -20,28 +20,7 @@ def _maps(gpu, points, covs, res, intensities=None, **kw):
     return cloud, vm, om
 
 
-def _reference_lookup(buckets, info, coord):
-    """lookup_voxel of cuda/kernels/vector3_hash.cuh:53-76 restated on the downloaded table"""
-    M, mask = 0xC6A4A7935BD1E995, (1 << 64) - 1
-
-    def combine(h, k):
-        k = (k * M) & mask
-        k ^= k >> 47
-        k = (k * M) & mask
-        h ^= k
-        h = (h * M) & mask
-        return (h + 0xE6546B64) & mask
-
-    h = 0
-    for c in coord:
-        h = combine(h, int(c) & mask)
-    for i in range(info.max_bucket_scan_count):
-        b = buckets[((h + i) & mask) % info.num_buckets]
-        if b[3] < 0:
-            return -1
-        if tuple(b[:3]) == tuple(int(c) for c in coord):
-            return int(b[3])
-    return -1
+_reference_lookup = reference_bucket_lookup  # (shared with tests/test_voxelmap_edges_gpu.py)
 
 
 @pytest.mark.parametrize("res", [0.5, 1.0, 0.3])
