@@ -19,6 +19,7 @@ from .factors import (  # noqa: F401
     pose_inverse,
 )
 from .features import (  # noqa: F401
+    CorrespondenceFactorBatchGPU,
     IntegratedGICPFactorGPU,
     IntegratedICPFactorGPU,
     IntegratedPointToPlaneICPFactorGPU,
@@ -54,6 +55,7 @@ __all__ = [
     "GaussianVoxelMapGPU",
     "HessianFactor",
     "IntegratedGICPFactorGPU",
+    "CorrespondenceFactorBatchGPU",
     "IntegratedICPFactorGPU",
     "IntegratedPointToPlaneICPFactorGPU",
     "IntegratedVGICPFactorGPU",

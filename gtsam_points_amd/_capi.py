@@ -197,6 +197,16 @@ _SIGNATURES = {
     "gp_icp_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gp_icp_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "gp_icp_factor_num_correspondences": (C.c_int, [C.c_void_p]),
+    # a batch of GICP / ICP factors with device-resident poses (gp_corr_batch.hip)
+    "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_corr_batch_destroy": (C.c_int, [C.c_void_p]),
+    "gp_corr_batch_size": (C.c_int, [C.c_void_p]),
+    "gp_corr_batch_stream": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_corr_batch_sync": (C.c_int, [C.c_void_p]),
+    "gp_corr_batch_issue_linearize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "gp_corr_batch_issue_compute_error_dev": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "gp_corr_batch_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
+    "gp_corr_batch_compute_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     # voxelgrid_sampling / randomgrid_sampling / sample on the device (gp_sampling.hip)
     "gp_voxelgrid_plan_create": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_voxelgrid_plan_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
@@ -270,6 +280,7 @@ _SIGNATURES = {
     "gp_lm_graph_optimize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_lm_graph_records": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "gp_lm_graph_create_with_pose_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_lm_graph_create_with_factors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_pose_factors_create": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_pose_factors_destroy": (C.c_int, [C.c_void_p]),
     "gp_pose_factors_size": (C.c_int, [C.c_void_p]),

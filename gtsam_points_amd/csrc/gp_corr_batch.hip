@@ -1,0 +1,297 @@
+// gp_corr_batch.hip -- a batch of matching-cost factors on 1-NN correspondences (GICP, point-to-point and point-to-plane ICP: gp_corr_factors.hip) whose relative
+// poses live in DEVICE memory: what gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor, and what the device-resident LM graph
+// (gp_lm.hip) queues for these factors.
+//
+// A single factor's linearise is three launches and a wait with its pose in the kernel arguments (gp_{gicp,icp}_factor_linearize); F of them are 3 F launches and F
+// waits, and every pose goes through the host.  Here the launch count does not depend on F:
+//   linearise       one search launch (gp_knn.hip: nearest_correspond_batch_kernel -- search structure, cloud, cut-off and pose of each factor from tables in device
+//                   memory), one tile launch per factor KIND present (the kernels are instantiated per term: GICP, ICP point, ICP plane), one finalize launch
+//   error           the tile launches (MODE_ERR) on the STORED correspondences -- the reference's error() does not search (integrated_gicp_factor_impl.hpp:183-185) --
+//                   and one finalize launch
+// The per-point terms, the 1024-point tiles dealt to 256 lanes, the reduction of a tile's sums (gp_corr_factors.hpp) and the finalize kernels (gp_vgicp.hip, one
+// workgroup per factor over the factor's contiguous rows) are the single-factor call's own, on the same operands in the same order: a batch record has the bits of
+// the single-factor call at the same pose.  A tile never straddles two factors (the flat tile list is built once, at create).
+//
+// Correspondences are kept in TWO sets.  The LM graph queues a speculative linearise at a trial's values behind the trial's error evaluation; were there one set, a
+// REJECTED trial would leave the next trial evaluating on the correspondences of the rejected point instead of those of the linearisation point.  A linearise names
+// the set it searches into, an error evaluation the set it reads; the partial rows of the two passes are separate buffers.
+// Not thread-safe per handle, re-entrant across handles, like the rest of the library.
+#include <type_traits>
+#include <vector>
+
+#include "gp_corr_factors.hpp"
+
+namespace gp {
+
+// what the tile kernels read of factor t.factor (every kind's pointers in one record; a kind reads its own)
+struct CorrBatchDesc {
+  const float* points;          // [n][3] source
+  const float* covs;            // [n][9] source (GICP)
+  const float* target_points;   // [num_target][3]
+  const float* target_covs;     // [num_target][9] (GICP)
+  const float* target_normals;  // [num_target][3] (ICP point-to-plane)
+  const int* corr[2];           // [n] the two correspondence sets
+};
+
+template <class TERM>
+__device__ __forceinline__ TERM batch_term(const CorrBatchDesc& d) {
+  if constexpr (std::is_same<TERM, GicpTerm>::value) {
+    return GicpTerm{d.points, d.covs, d.target_points, d.target_covs};
+  } else {
+    return TERM{IcpDesc{d.points, d.target_points, d.target_normals}};
+  }
+}
+
+// corr_tile_kernel (gp_corr_factors.hip) with the tile, the factor and the poses looked up: workgroup b takes tile tiles[b], lane t of 256 its points t, t + 256, ...
+template <int MODE, class TERM>
+__global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const CorrBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
+                                                               const double* __restrict__ poses_eval, const int set, double* __restrict__ partials) {
+  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
+  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
+  const CorrTile t = tiles[blockIdx.x];
+  const CorrBatchDesc d = descs[t.factor];
+  const TERM f = batch_term<TERM>(d);
+  const Pose Tl = load_pose(poses_lin + 16 * (size_t)t.factor);
+  const Pose Te = MODE == MODE_ERR ? load_pose(poses_eval + 16 * (size_t)t.factor) : Tl;
+  double acc[NREG];
+#pragma unroll
+  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
+  const int* __restrict__ corr = d.corr[set];
+  const int end = t.begin + t.count;
+  for (int i = t.begin + threadIdx.x; i < end; i += 256) {
+    const int c = corr[i];
+    if (c < 0) continue;
+    f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
+  }
+  store_tile_sums_row<MODE>(acc, partials + (size_t)t.row * STRIDE);
+}
+
+}  // namespace gp
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------
+
+struct gp_corr_batch {
+  enum Kind { GICP = 0, ICP_POINT = 1, ICP_PLANE = 2 };
+  hipStream_t stream = nullptr;
+  int F = 0;
+  int num_tiles = 0;            // = rows of the partial sums
+  long total_points = 0;
+  int kind_begin[3] = {0, 0, 0}, kind_count[3] = {0, 0, 0};  // the tile list is ordered by kind: one tile launch per kind present
+  gp::DeviceArray d_search, d_descs, d_tiles, d_rows;         // search descriptors | CorrBatchDesc[F] | CorrTile[num_tiles] | FactorDesc[F] (tile_begin / tile_count: the finalize's)
+  gp::DeviceArray d_corr[2];                                  // int[total_points] each: factor f's correspondences at its point offset
+  gp::DeviceArray d_partials_lin, d_partials_err;             // [num_tiles][ACCG_STRIDE] | [num_tiles][ACC_STRIDE]
+  bool set_valid[2] = {false, false};
+  // the synchronous host-pose forms and the LM graph's error evaluation: pose staging, results and completion words in host-mapped pinned memory
+  gp::PinnedArray h_poses, h_out, h_done;
+  void *h_out_dev = nullptr, *h_done_dev = nullptr;
+  gp::DeviceArray d_poses[2];
+  unsigned long long seq = 0;
+
+  long spin_us() const { return 200 + total_points / 500; }  // (the search is ~1 ns per point; the wait falls back to the stream behind it)
+
+  template <int MODE>
+  int launch_tiles(const double* lin, const double* eval, int set, double* partials) {
+    const gp::CorrBatchDesc* descs = d_descs.as<gp::CorrBatchDesc>();
+    const gp::CorrTile* tiles = d_tiles.as<gp::CorrTile>();
+    if (kind_count[GICP] > 0)
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::GicpTerm>), dim3(kind_count[GICP]), dim3(256), 0, stream, descs, tiles + kind_begin[GICP], lin, eval, set, partials);
+    if (kind_count[ICP_POINT] > 0)
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<false>>), dim3(kind_count[ICP_POINT]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_POINT], lin, eval, set, partials);
+    if (kind_count[ICP_PLANE] > 0)
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<true>>), dim3(kind_count[ICP_PLANE]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_PLANE], lin, eval, set, partials);
+    GP_HIP(hipGetLastError());
+    return GP_OK;
+  }
+
+  int issue_linearize(const double* poses_dev, bool rigid, int set, gp_linearized6* out, gp::DoneFlags done) {
+    if (num_tiles > 0) {
+      GP_TRY(gp::launch_nearest_correspondences_batch(d_search.ptr, d_tiles.as<gp::CorrTile>(), num_tiles, poses_dev, set, stream));
+      if (rigid) GP_TRY(launch_tiles<gp::MODE_LIN>(poses_dev, poses_dev, set, d_partials_lin.as<double>()));
+      else GP_TRY(launch_tiles<gp::MODE_LIN_GENERAL>(poses_dev, poses_dev, set, d_partials_lin.as<double>()));
+    }
+    set_valid[set] = true;
+    return gp::launch_finalize_table(stream, d_rows.as<gp::FactorDesc>(), F, poses_dev, d_partials_lin.as<double>(), out, !rigid, done);
+  }
+
+  int issue_error(int set, const double* lin, const double* eval, double* out, gp::DoneFlags done) {
+    if (num_tiles > 0) GP_TRY(launch_tiles<gp::MODE_ERR>(lin, eval, set, d_partials_err.as<double>()));
+    return gp::launch_finalize_error_table(stream, d_rows.as<gp::FactorDesc>(), F, d_partials_err.as<double>(), out, done);
+  }
+
+  // host poses [F][16] -> d_poses[k] (through the pinned staging block; in stream order in front of the kernels that read them)
+  int stage_poses(const double* poses_host, int k) {
+    const size_t bytes = sizeof(double) * 16 * (size_t)F;
+    char* h = static_cast<char*>(h_poses.ptr) + bytes * (size_t)k;
+    memcpy(h, poses_host, bytes);
+    GP_HIP(hipMemcpyAsync(d_poses[k].ptr, h, bytes, hipMemcpyHostToDevice, stream));
+    return GP_OK;
+  }
+};
+
+namespace gp {
+
+int corr_batch_error_begin(gp_corr_batch* b, int set, const double* poses_lin_dev, const double* poses_eval_dev) {
+  if (!b || !poses_lin_dev || !poses_eval_dev || (set != 0 && set != 1)) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch: error evaluation: null / set must be 0 or 1");
+  if (!b->set_valid[set]) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch: error evaluation on a correspondence set that was never linearised");
+  const DoneFlags done{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq};
+  return b->issue_error(set, poses_lin_dev, poses_eval_dev, static_cast<double*>(b->h_out_dev), done);
+}
+
+int corr_batch_error_end(gp_corr_batch* b, double* out_host, long extra_spin_us) {
+  GP_TRY(wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), (size_t)b->F, b->seq, b->stream, b->spin_us() + extra_spin_us));
+  memcpy(out_host, b->h_out.ptr, sizeof(double) * (size_t)b->F);
+  return GP_OK;
+}
+
+}  // namespace gp
+
+extern "C" {
+
+int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out) {
+  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null out");
+  *out = nullptr;
+  if (num_gicp < 0 || num_icp < 0 || (num_gicp > 0 && !gicp) || (num_icp > 0 && !icp)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: bad arguments");
+  if (num_gicp + num_icp == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
+  const int F = num_gicp + num_icp;
+  std::vector<const gp_corr_factor_core*> cores((size_t)F);
+  std::vector<int> kinds((size_t)F);
+  for (int i = 0; i < num_gicp; i++) {
+    if (!gicp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null GICP factor");
+    cores[(size_t)i] = gicp[i], kinds[(size_t)i] = gp_corr_batch::GICP;
+  }
+  for (int i = 0; i < num_icp; i++) {
+    if (!icp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null ICP factor");
+    // the keep-or-search decision of the update tolerances is host logic on a host pose: in a batch every linearise searches (the reference's default)
+    if (icp[i]->tol_rot != 0.0 || icp[i]->tol_trans != 0.0)
+      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an ICP factor with non-zero correspondence-update tolerances cannot join a batch");
+    cores[(size_t)(num_gicp + i)] = icp[i], kinds[(size_t)(num_gicp + i)] = icp[i]->plane ? gp_corr_batch::ICP_PLANE : gp_corr_batch::ICP_POINT;
+  }
+  for (const auto* c : cores)
+    if (c->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
+
+  auto b = std::make_unique<gp_corr_batch>();
+  b->stream = (hipStream_t)stream;
+  b->F = F;
+  // rows (= tiles) in record order, a factor's rows contiguous; the tile LIST ordered by kind
+  std::vector<gp::FactorDesc> rows((size_t)F);
+  std::vector<long> point_offset((size_t)F);
+  std::vector<gp::CorrTile> by_kind[3];
+  int row = 0;
+  for (int f = 0; f < F; f++) {
+    const int n = cores[(size_t)f]->n;
+    point_offset[(size_t)f] = b->total_points;
+    b->total_points += n;
+    rows[(size_t)f] = gp::FactorDesc{};
+    rows[(size_t)f].n = n;
+    rows[(size_t)f].tile_begin = row;
+    for (int begin = 0; begin < n; begin += gp::kTilePoints) by_kind[kinds[(size_t)f]].push_back(gp::CorrTile{f, begin, std::min(gp::kTilePoints, n - begin), row++});
+    rows[(size_t)f].tile_count = row - rows[(size_t)f].tile_begin;
+  }
+  b->num_tiles = row;
+  std::vector<gp::CorrTile> tiles;
+  for (int k = 0; k < 3; k++) {
+    b->kind_begin[k] = (int)tiles.size();
+    b->kind_count[k] = (int)by_kind[k].size();
+    tiles.insert(tiles.end(), by_kind[k].begin(), by_kind[k].end());
+  }
+  if (b->total_points > 0x7fffffffl) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: more than 2^31 - 1 source points in one batch");
+
+  for (int k = 0; k < 2; k++) GP_TRY(b->d_corr[k].alloc(sizeof(int) * (size_t)std::max(b->total_points, 1l)));
+  GP_TRY(b->d_partials_lin.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(b->num_tiles, 1)));
+  GP_TRY(b->d_partials_err.alloc(sizeof(double) * gp::ACC_STRIDE * (size_t)std::max(b->num_tiles, 1)));
+  std::vector<char> search(gp::corr_search_desc_bytes() * (size_t)F);
+  std::vector<gp::CorrBatchDesc> descs((size_t)F);
+  for (int f = 0; f < F; f++) {
+    const gp_corr_factor_core* c = cores[(size_t)f];
+    int* c0 = b->d_corr[0].as<int>() + point_offset[(size_t)f];
+    int* c1 = b->d_corr[1].as<int>() + point_offset[(size_t)f];
+    gp::fill_corr_search_desc(search.data(), f, c->grid, c->points, c->n, c->max_sq_dist, c0, c1);
+    gp::CorrBatchDesc& d = descs[(size_t)f];
+    d = gp::CorrBatchDesc{};
+    if (f < num_gicp) {
+      const gp::GicpTerm& t = gicp[f]->term;
+      d.points = t.points, d.covs = t.covs, d.target_points = t.target_points, d.target_covs = t.target_covs;
+    } else {
+      const gp::IcpDesc& t = icp[f - num_gicp]->desc;
+      d.points = t.points, d.target_points = t.target_points, d.target_normals = t.target_normals;
+    }
+    d.corr[0] = c0, d.corr[1] = c1;
+  }
+  GP_TRY(b->d_search.alloc(search.size()));
+  GP_TRY(b->d_descs.alloc(sizeof(gp::CorrBatchDesc) * (size_t)F));
+  GP_TRY(b->d_tiles.alloc(sizeof(gp::CorrTile) * std::max(tiles.size(), (size_t)1)));
+  GP_TRY(b->d_rows.alloc(sizeof(gp::FactorDesc) * (size_t)F));
+  GP_HIP(hipMemcpy(b->d_search.ptr, search.data(), search.size(), hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_descs.ptr, descs.data(), sizeof(gp::CorrBatchDesc) * (size_t)F, hipMemcpyHostToDevice));
+  if (!tiles.empty()) GP_HIP(hipMemcpy(b->d_tiles.ptr, tiles.data(), sizeof(gp::CorrTile) * tiles.size(), hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_rows.ptr, rows.data(), sizeof(gp::FactorDesc) * (size_t)F, hipMemcpyHostToDevice));
+
+  const size_t pb = sizeof(double) * 16 * (size_t)F;
+  for (int k = 0; k < 2; k++) GP_TRY(b->d_poses[k].alloc(pb));
+  GP_TRY(b->h_poses.ensure(2 * pb));
+  GP_TRY(b->h_out.ensure(sizeof(gp_linearized6) * (size_t)F));
+  GP_HIP(hipHostGetDevicePointer(&b->h_out_dev, b->h_out.ptr, 0));
+  GP_TRY(b->h_done.ensure(sizeof(unsigned long long) * (size_t)F));
+  memset(b->h_done.ptr, 0, b->h_done.bytes);
+  GP_HIP(hipHostGetDevicePointer(&b->h_done_dev, b->h_done.ptr, 0));
+  *out = b.release();
+  return GP_OK;
+}
+
+int gp_corr_batch_destroy(gp_corr_batch_t* b) {
+  if (!b) return GP_OK;
+  (void)hipStreamSynchronize(b->stream);
+  delete b;  // (the factors are the caller's)
+  return GP_OK;
+}
+
+int gp_corr_batch_size(const gp_corr_batch_t* b) { return b ? b->F : 0; }
+
+int gp_corr_batch_stream(const gp_corr_batch_t* b, gp_stream_t* out) {
+  if (!b || !out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_stream: null");
+  *out = (gp_stream_t)b->stream;
+  return GP_OK;
+}
+
+int gp_corr_batch_sync(gp_corr_batch_t* b) {
+  if (!b) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_sync: null batch");
+  GP_HIP(hipStreamSynchronize(b->stream));
+  return GP_OK;
+}
+
+int gp_corr_batch_issue_linearize_dev(gp_corr_batch_t* b, const double* poses_dev, int rigid, int set, gp_linearized6* out_dev) {
+  if (!b || !poses_dev || !out_dev || (set != 0 && set != 1)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_issue_linearize_dev: null / set must be 0 or 1");
+  return b->issue_linearize(poses_dev, rigid != 0, set, out_dev, {});
+}
+
+int gp_corr_batch_issue_compute_error_dev(gp_corr_batch_t* b, int set, const double* poses_lin_dev, const double* poses_eval_dev, double* out, unsigned long long* done_flags,
+                                          unsigned long long done_seq) {
+  if (!b || !poses_lin_dev || !poses_eval_dev || !out || (set != 0 && set != 1))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_issue_compute_error_dev: null / set must be 0 or 1");
+  if (!b->set_valid[set]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_issue_compute_error_dev: this correspondence set was never linearised");
+  return b->issue_error(set, poses_lin_dev, poses_eval_dev, out, gp::DoneFlags{done_flags, done_seq});
+}
+
+// the synchronous host-pose forms (tests and callers outside the LM graph): set 0
+int gp_corr_batch_linearize(gp_corr_batch_t* b, const double* poses_host, int rigid, gp_linearized6* out_host) {
+  if (!b || !poses_host || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_linearize: null");
+  GP_TRY(b->stage_poses(poses_host, 0));
+  const gp::DoneFlags done{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq};
+  GP_TRY(b->issue_linearize(b->d_poses[0].as<double>(), rigid != 0, 0, static_cast<gp_linearized6*>(b->h_out_dev), done));
+  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), (size_t)b->F, done.seq, b->stream, b->spin_us()));
+  memcpy(out_host, b->h_out.ptr, sizeof(gp_linearized6) * (size_t)b->F);
+  return GP_OK;
+}
+
+int gp_corr_batch_compute_error(gp_corr_batch_t* b, const double* poses_lin_host, const double* poses_eval_host, double* out_host) {
+  if (!b || !poses_lin_host || !poses_eval_host || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_compute_error: null");
+  if (!b->set_valid[0]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_compute_error: correspondence set 0 was never linearised");
+  GP_TRY(b->stage_poses(poses_lin_host, 0));
+  GP_TRY(b->stage_poses(poses_eval_host, 1));
+  GP_TRY(gp::corr_batch_error_begin(b, 0, b->d_poses[0].as<double>(), b->d_poses[1].as<double>()));
+  return gp::corr_batch_error_end(b, out_host, 0);
+}
+
+}  // extern "C"

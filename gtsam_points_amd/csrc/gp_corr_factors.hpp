@@ -1,0 +1,232 @@
+// gp_corr_factors.hpp -- what the single-factor entry points of the matching-cost factors (gp_corr_factors.hip) share with their batch (gp_corr_batch.hip): the
+// per-point terms of GICP and ICP, the reduction of a tile's sums into its partial row, and the factor handles the batch borrows.
+#pragma once
+#include <cmath>
+#include <cstring>
+#include <memory>
+
+#include "gp_host.hpp"
+#include "gp_vgicp_tile.hpp"
+
+namespace gp {
+
+// the poses ride in the kernel arguments (no H2D copy in front of the launch)
+struct CorrPoses {
+  double lin[16], eval[16];
+};
+
+// ---- the per-point terms: a descriptor of device arrays + "given source point i, its target point j, Tl and Te, accumulate into acc" ----
+
+// GICP: the same H/b algebra as VGICP (integrated_gicp_factor_impl.hpp:199-296)
+struct GicpTerm {
+  const float* points;
+  const float* covs;
+  const float* target_points;
+  const float* target_covs;
+  static constexpr int kErrRegs = 32;  // accumulate_terms_mu<MODE_ERR> is handed the 32-register array of the linearise
+
+  template <int MODE>
+  __device__ __forceinline__ void accumulate(int i, size_t j, const Pose& Tl, const Pose& Te, double* acc) const {
+    const GicpTerm& f = *this;
+    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+    const double lx = Tl.r00 * px + Tl.r01 * py + Tl.r02 * pz + Tl.tx;
+    const double ly = Tl.r10 * px + Tl.r11 * py + Tl.r12 * pz + Tl.ty;
+    const double lz = Tl.r20 * px + Tl.r21 * py + Tl.r22 * pz + Tl.tz;
+    const float* cp = f.covs + 9 * (size_t)i;
+    const float* cq = f.target_covs + 9 * j;
+    // reuse the VGICP per-point algebra: the "voxel" is the matched target point (mu_B, C_B)
+    const double mux = (double)f.target_points[3 * j], muy = (double)f.target_points[3 * j + 1], muz = (double)f.target_points[3 * j + 2];
+    // symmetric parts of both column-major 3x3 covariances (exactly the inputs when they are symmetric)
+    const double cb[6] = {(double)cq[0], 0.5 * ((double)cq[3] + (double)cq[1]), 0.5 * ((double)cq[6] + (double)cq[2]),
+                          (double)cq[4], 0.5 * ((double)cq[7] + (double)cq[5]), (double)cq[8]};
+    if constexpr (MODE == MODE_LIN_GENERAL) {
+      const double ca[6] = {(double)cp[0], 0.5 * ((double)cp[3] + (double)cp[1]), 0.5 * ((double)cp[6] + (double)cp[2]),
+                            (double)cp[4], 0.5 * ((double)cp[7] + (double)cp[5]), (double)cp[8]};
+      double m[6];
+      fused_mahalanobis(Tl, ca, cb, m);
+      accumulate_sums<MODE_LIN_GENERAL>(Tl, m, px, py, pz, lx, ly, lz, mux - lx, muy - ly, muz - lz, acc);
+    } else {
+      const v2d c01 = {cb[0], cb[1]}, c23 = {cb[2], cb[3]}, c45 = {cb[4], cb[5]};
+      accumulate_terms_mu<MODE, double>(Tl, Te, (float)px, (float)py, (float)pz, cp, mux, muy, muz, c01, c23, c45, acc);
+    }
+  }
+};
+
+// The per-point body of IntegratedICPFactor_::evaluate (integrated_icp_factor_impl.hpp:199-240):
+//   q = T p, d = mu_B - q, r = n_B o d (element-wise, :212; point-to-point: r = d), error += r^T r (:215, no 1/2),
+//   J_t = diag(n_B) [-[q]x, I], J_s = diag(n_B) [R [p]x, -R] (:220-232), H += J^T J, b += J^T r (:234-238).
+// That is the GICP algebra with M = diag(n_B o n_B) (or I) in place of the fused Mahalanobis matrix, so the sums go into the SAME
+// partial-row layout and through the same finalize kernels: b_t = [q x w; w] with w = n_B o r = M d,
+// K = M [q]x and TL = -[q]x K written out for a diagonal M (the off-diagonal slots of ACC_M and the diagonal of K stay zero).
+// A matched point costs 4 B (index) + 12 B (source point) + 12 B (target point) [+ 12 B (normal)]; no covariance is read and nothing is
+// inverted.  A non-orthonormal 3x3 block takes the 92 explicit sums of accumulate_sums<MODE_LIN_GENERAL>, J_s from the block AS GIVEN.
+struct IcpDesc {
+  const float* points;          // [n][3] source
+  const float* target_points;   // [num_target][3]
+  const float* target_normals;  // [num_target][3]; read by the point-to-plane kernels only
+};
+template <bool PLANE>
+struct IcpTerm {
+  IcpDesc f;
+  static constexpr int kErrRegs = 2;
+
+  template <int MODE>
+  __device__ __forceinline__ void accumulate(int i, size_t j, const Pose& Tl, const Pose& Te, double* acc) const {
+    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+    const double mux = (double)f.target_points[3 * j], muy = (double)f.target_points[3 * j + 1], muz = (double)f.target_points[3 * j + 2];
+    double nx = 1.0, ny = 1.0, nz = 1.0;
+    if constexpr (PLANE) {
+      nx = (double)f.target_normals[3 * j];
+      ny = (double)f.target_normals[3 * j + 1];
+      nz = (double)f.target_normals[3 * j + 2];
+    }
+    const double qx = Te.r00 * px + Te.r01 * py + Te.r02 * pz + Te.tx;
+    const double qy = Te.r10 * px + Te.r11 * py + Te.r12 * pz + Te.ty;
+    const double qz = Te.r20 * px + Te.r21 * py + Te.r22 * pz + Te.tz;
+    const double dx = mux - qx, dy = muy - qy, dz = muz - qz;
+    if constexpr (MODE == MODE_LIN_GENERAL) {
+      const double m[6] = {nx * nx, 0.0, 0.0, ny * ny, 0.0, nz * nz};
+      accumulate_sums<MODE_LIN_GENERAL>(Tl, m, px, py, pz, qx, qy, qz, dx, dy, dz, acc);
+    } else {
+      const double rx = PLANE ? nx * dx : dx, ry = PLANE ? ny * dy : dy, rz = PLANE ? nz * dz : dz;  // r = n_B o d
+      acc[ACC_COUNT] += 1.0;
+      acc[ACC_ERR] += rx * rx + ry * ry + rz * rz;
+      if constexpr (MODE == MODE_LIN) {
+        const double m0 = PLANE ? nx * nx : 1.0, m3 = PLANE ? ny * ny : 1.0, m5 = PLANE ? nz * nz : 1.0;  // M = diag(n_B o n_B)
+        const double wx = PLANE ? nx * rx : rx, wy = PLANE ? ny * ry : ry, wz = PLANE ? nz * rz : rz;     // w = n_B o r
+        acc[ACC_M + 0] += m0;
+        acc[ACC_M + 3] += m3;
+        acc[ACC_M + 5] += m5;
+        // K = M [q]x, row-major
+        const double k01 = -m0 * qz, k02 = m0 * qy, k10 = m3 * qz, k12 = -m3 * qx, k20 = -m5 * qy, k21 = m5 * qx;
+        acc[ACC_K + 1] += k01;
+        acc[ACC_K + 2] += k02;
+        acc[ACC_K + 3] += k10;
+        acc[ACC_K + 5] += k12;
+        acc[ACC_K + 6] += k20;
+        acc[ACC_K + 7] += k21;
+        // TL = -[q]x K (= [q]x^T M [q]x), upper triangle
+        acc[ACC_TL + 0] += qz * k10 - qy * k20;
+        acc[ACC_TL + 1] += -qy * k21;
+        acc[ACC_TL + 2] += qz * k12;
+        acc[ACC_TL + 3] += qx * k21 - qz * k01;
+        acc[ACC_TL + 4] += -qz * k02;
+        acc[ACC_TL + 5] += qy * k02 - qx * k12;
+        // b_t = [q x w; w]
+        acc[ACC_QXMR + 0] += qy * wz - qz * wy;
+        acc[ACC_QXMR + 1] += qz * wx - qx * wz;
+        acc[ACC_QXMR + 2] += qx * wy - qy * wx;
+        acc[ACC_MR + 0] += wx;
+        acc[ACC_MR + 1] += wy;
+        acc[ACC_MR + 2] += wz;
+      }
+    }
+  }
+};
+
+// the lanes meet in the butterfly / shuffle tree and the four waves in wave order: a fixed order, two passes over the same correspondences are bit-identical
+// (row: where the workgroup's sums go -- the single-factor kernels' row is their blockIdx.x, a batch's tile carries its own)
+template <int MODE>
+__device__ __forceinline__ void store_tile_sums_row(double* acc, double* __restrict__ row) {
+  constexpr int NACC = MODE == MODE_ERR ? 2 : (MODE == MODE_LIN ? ACC_SIZE : ACCG_SIZE);
+  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __shared__ double lds[4][STRIDE];
+  if constexpr (MODE == MODE_LIN) {
+    const double s = butterfly_reduce32(acc, lane);
+    if ((lane & 1) == 0) lds[wave][butterfly_component(lane)] = s;
+  } else {
+#pragma unroll
+    for (int k = 0; k < NACC; k++) {
+      double v = acc[k];
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      if (lane == 0) lds[wave][k] = v;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < STRIDE) {
+    double s = 0.0;
+    if (threadIdx.x < NACC) s = (lds[0][threadIdx.x] + lds[1][threadIdx.x]) + (lds[2][threadIdx.x] + lds[3][threadIdx.x]);
+    row[threadIdx.x] = s;
+  }
+}
+template <int MODE>
+__device__ __forceinline__ void store_tile_sums(double* acc, double* __restrict__ partials) {
+  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
+  store_tile_sums_row<MODE>(acc, partials + (size_t)blockIdx.x * STRIDE);
+}
+
+}  // namespace gp
+
+// ---------------------------------------------------------------------------------------------------------------
+// host side: the factor handles
+// ---------------------------------------------------------------------------------------------------------------
+
+// what both factors keep: the search's inputs, the stored correspondences and the pose they belong to, the tile geometry and where a pass leaves its result
+struct gp_corr_factor_core {
+  const gp_point_grid* grid = nullptr;  // the search structure over the target (the cut-off ends every search, whatever cell size it was built with)
+  const float* points = nullptr;        // [n][3] source
+  int n = 0;
+  double max_sq_dist = 0.0;
+  hipStream_t stream = nullptr;
+  int tile_points = 1024;
+  int num_tiles = 0;
+  gp::DeviceArray partials, corr;  // corr: [n] correspondences of the last correspondence pass
+  gp::PinnedArray h_out;
+  void* h_out_dev = nullptr;
+  gp::PinnedArray h_done;  // completion word of the synchronous calls (gp_vgicp_shared.hpp: DoneFlags)
+  void* h_done_dev = nullptr;
+  unsigned long long seq = 0;
+  double corr_pose[16] = {0};  // last_correspondence_point: the pose the stored correspondences were searched at
+  bool corr_valid = false;
+
+  int prepare(const gp_point_grid* grid_, const float* points_dev, int n_, double max_sq_dist_, hipStream_t stream_) {
+    grid = grid_;
+    points = points_dev;
+    n = n_;
+    max_sq_dist = max_sq_dist_;
+    stream = stream_;
+    num_tiles = (n + tile_points - 1) / tile_points;
+    GP_TRY(partials.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(num_tiles, 1)));
+    GP_TRY(corr.alloc(sizeof(int) * (size_t)std::max(n, 1)));
+    GP_TRY(h_out.ensure(sizeof(gp_linearized6)));
+    GP_HIP(hipHostGetDevicePointer(&h_out_dev, h_out.ptr, 0));
+    GP_TRY(h_done.ensure(sizeof(unsigned long long)));
+    memset(h_done.ptr, 0, h_done.bytes);
+    GP_HIP(hipHostGetDevicePointer(&h_done_dev, h_done.ptr, 0));
+    return GP_OK;
+  }
+
+  bool searched_at(const double* pose) const { return corr_valid && memcmp(corr_pose, pose, sizeof(double) * 16) == 0; }
+
+  // the correspondence pass at pose_lin (n > 0)
+  int search(const double* pose_lin) {
+    GP_TRY(gp::launch_nearest_correspondences(grid, points, n, pose_lin, max_sq_dist, corr.as<int>(), stream));
+    memcpy(corr_pose, pose_lin, sizeof(double) * 16);
+    corr_valid = true;
+    return GP_OK;
+  }
+
+  // One synchronous pass over the stored correspondences (gp_corr_factors.hip, which alone instantiates it).
+  template <class TERM>
+  int run_pass(const TERM& term, const double* pose_lin, const double* pose_eval, void* out_host);
+};
+
+struct gp_gicp_factor : gp_corr_factor_core {
+  gp_point_grid* own_grid = nullptr;  // OWNED: the factor's target 1-NN structure
+  gp::GicpTerm term{};
+  ~gp_gicp_factor() {
+    if (own_grid) gp_point_grid_destroy(own_grid);
+  }
+};
+
+struct gp_icp_factor : gp_corr_factor_core {  // (the grid is BORROWED: the reference's target_tree, shared between factors)
+  gp::IcpDesc desc{};
+  bool plane = false;
+  double lin_pose[16] = {0};  // the pose of the last linearise (which may have kept older correspondences: the update tolerances)
+  bool lin_valid = false;
+  double tol_rot = 0.0, tol_trans = 0.0;  // correspondence_update_tolerance_rot / _trans (:32-33)
+  int num_correspondences = 0;
+  int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_corr_factors.hip)
+};

@@ -1942,6 +1942,35 @@ __global__ void __launch_bounds__(256) nearest_correspond_kernel(NearestDesc f, 
   corr[i] = top.found ? top.idx[0] : -1;
 }
 
+// The same pass for a batch of factors (gp_corr_batch.hip) in ONE launch: the search structure, cloud and cut-off of factor t.factor come from a descriptor table and
+// its pose from a pose table, both in device memory (the device-resident LM graph writes the poses there itself).  Four workgroups per tile of <= 1024 points, one
+// query per lane as above; the query and the walk are the single launch's, so the correspondences are the same.
+struct NearestBatchDesc {
+  const float* points;
+  SearchView grid;
+  int* corr[2];  // the two correspondence sets
+  int n;
+  double max_sq_dist;
+};
+
+__global__ void __launch_bounds__(256) nearest_correspond_batch_kernel(const NearestBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles,
+                                                                       const double* __restrict__ poses, const int set) {
+  const CorrTile t = tiles[blockIdx.x >> 2];
+  const int k = (int)(blockIdx.x & 3) * 256 + (int)threadIdx.x;
+  if (k >= t.count) return;
+  const NearestBatchDesc& f = descs[t.factor];
+  const int i = t.begin + k;
+  const Pose Tl = load_pose(poses + 16 * (size_t)t.factor);
+  const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+  const double lx = Tl.r00 * px + Tl.r01 * py + Tl.r02 * pz + Tl.tx;
+  const double ly = Tl.r10 * px + Tl.r11 * py + Tl.r12 * pz + Tl.ty;
+  const double lz = Tl.r20 * px + Tl.r21 * py + Tl.r22 * pz + Tl.tz;
+  TopK<1> top;
+  top.init(1, f.max_sq_dist);
+  knn_query_any<1>(f.grid, lx, ly, lz, 1, top);
+  f.corr[set][i] = top.found ? top.idx[0] : -1;
+}
+
 }  // namespace gp
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -2035,6 +2064,24 @@ int launch_nearest_correspondences(const gp_point_grid* grid, const float* point
   f.max_sq_dist = max_sq_dist;
   memcpy(f.pose, pose_lin, sizeof(double) * 16);
   hipLaunchKernelGGL(nearest_correspond_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, f, corr);
+  GP_HIP(hipGetLastError());
+  return GP_OK;
+}
+
+size_t corr_search_desc_bytes() { return sizeof(NearestBatchDesc); }
+
+void fill_corr_search_desc(void* table_host, int index, const gp_point_grid* grid, const float* points, int n, double max_sq_dist, int* corr0, int* corr1) {
+  NearestBatchDesc d{};
+  d.points = points;
+  d.grid = grid->view();
+  d.corr[0] = corr0, d.corr[1] = corr1;
+  d.n = n;
+  d.max_sq_dist = max_sq_dist;
+  memcpy(static_cast<char*>(table_host) + sizeof(NearestBatchDesc) * (size_t)index, &d, sizeof(d));
+}
+
+int launch_nearest_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream) {
+  hipLaunchKernelGGL(nearest_correspond_batch_kernel, dim3(4 * (unsigned)num_tiles), dim3(256), 0, stream, static_cast<const NearestBatchDesc*>(table_dev), tiles_dev, poses_dev, set);
   GP_HIP(hipGetLastError());
   return GP_OK;
 }

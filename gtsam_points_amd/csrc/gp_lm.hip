@@ -18,6 +18,10 @@
 //   gp_lm_graph_optimize     the reference's cadence over those three (tryLambda's tests :262-292, decreaseLambda / increaseLambda with the GTSAM defaults)
 // Pose arithmetic on the device = the formulas of gtsam::Pose3 (Expmap with the closed-form V, compose, inverse() * other) in f64; the host-side harness
 // (bench_lm.py) computes the same with numpy, and the two agree to rounding (tests/test_lm_gpu.py).
+// GICP / ICP factors (gp_corr_batch.hip) are a second group of pairwise factors beside the VGICP batch: their relative poses go into delta tables of their own (written by
+// the same retract), their records follow the VGICP ones, and their correspondences live in the batch's two SETS -- set `rec` goes with record buffer `rec`, the
+// speculative linearise at a trial's values searches into set 1 - rec, so a rejected trial leaves the correspondences of the linearisation point where the next
+// trial's error evaluation reads them.
 // Device: the graph is created on the device that is current (the batch's: gp_set_device first in a multi-device process), like the batch and the systems it builds.
 // Not thread-safe per handle, re-entrant across handles, like the rest of the library.
 #include <cmath>
@@ -39,12 +43,16 @@ __global__ void __launch_bounds__(256) lm_poses_kernel(const LmPoseView v) {
 }  // namespace gp
 
 struct gp_lm_graph {
-  gp_vgicp_batch_t* batch = nullptr;  // not owned; null = a pure pose graph
+  gp_vgicp_batch_t* batch = nullptr;  // not owned; null = no VGICP factors
+  gp_corr_batch_t* corr = nullptr;    // not owned; null = no GICP / ICP factors.  Records [F, F + G); correspondence set k goes with d_records[k]
+  int G = 0;
+  gp::DeviceArray d_corr_pairs, d_corr_deltas[2];  // as d_pairs / d_deltas
+  std::vector<double> corr_errors;
   gp_sparse_system_t* sparse = nullptr;
   gp_dense_system_t* dense = nullptr;
   hipStream_t stream = nullptr;
   int F = 0, N = 0, slots = 0;
-  // pose factors (gp_pose_factors.hpp): records [F, F + P) of both record buffers; their errors at a trial's values reach the host through h_pose_errors, written by
+  // pose factors (gp_pose_factors.hpp): records [F + G, F + G + P) of both record buffers; their errors at a trial's values reach the host through h_pose_errors, written by
   // the launch that also writes their records at those values (speculation) -- queued in front of the batch's error evaluation, so its completion words cover them
   int P = 0;
   gp::DeviceArray d_pose_factors;
@@ -79,12 +87,15 @@ gp::LmPoseView pose_view(gp_lm_graph* g, int from, int to, bool step) {
   v.values_host = step ? g->h_values[to].as<double>() : nullptr;
   v.deltas_out = g->d_deltas[to].as<double>();
   v.F = g->F, v.N = g->N;
+  v.corr_pairs = g->d_corr_pairs.as<int>();
+  v.corr_deltas_out = g->d_corr_deltas[to].as<double>();
+  v.G = g->G;
   return v;
 }
 
 int launch_poses(gp_lm_graph* g, int from, int to, bool step) {
   const gp::LmPoseView v = pose_view(g, from, to, step);
-  const int n = std::max(g->F, g->N);
+  const int n = v.threads();
   hipLaunchKernelGGL(gp::lm_poses_kernel, dim3((n + 255) / 256), dim3(256), 0, g->stream, v);
   GP_HIP(hipGetLastError());
   return GP_OK;
@@ -103,34 +114,48 @@ int gp_lm_graph_destroy(gp_lm_graph_t* g) {
   return GP_OK;
 }
 
-// gp_lm_graph_create (P = 0: the same graph, the same launches) and gp_lm_graph_create_with_pose_factors; the arguments are checked by the callers
-static int create_graph(gp_vgicp_batch_t* batch, int F, const int* pose_pairs, const gp_pose_factor* pose_factors, int P, int num_poses, const unsigned char* pose_fixed,
-                        int ordering, gp_stream_t stream, gp_lm_graph_t** out) {
+// gp_lm_graph_create (G = P = 0: the same graph, the same launches), gp_lm_graph_create_with_pose_factors (G = 0) and gp_lm_graph_create_with_factors; the arguments
+// are checked by the callers
+static int create_graph(gp_vgicp_batch_t* batch, int F, const int* pose_pairs, gp_corr_batch_t* corr, int G, const int* corr_pairs, const gp_pose_factor* pose_factors, int P,
+                        int num_poses, const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out) {
   auto* g = new gp_lm_graph;
   g->batch = batch, g->F = F, g->N = num_poses, g->P = P;
+  g->corr = corr, g->G = G;
   g->slot.assign((size_t)num_poses, -1);
   for (int i = 0; i < num_poses; i++)
     if (!pose_fixed || !pose_fixed[i]) g->slot[i] = g->slots++;
-  std::vector<int> factor_slots(2 * ((size_t)F + P));
+  std::vector<int> factor_slots(2 * ((size_t)F + G + P));
   int rc = GP_OK;
   for (int f = 0; f < F && rc == GP_OK; f++) {
     const int t = pose_pairs[2 * f], s = pose_pairs[2 * f + 1];
     if (t < 0 || t >= num_poses || s < 0 || s >= num_poses || t == s) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: pose_pairs entries must be two different poses in [0, num_poses)");
     else factor_slots[2 * f] = g->slot[t], factor_slots[2 * f + 1] = g->slot[s];
   }
+  for (int f = 0; f < G && rc == GP_OK; f++) {
+    const int t = corr_pairs[2 * f], s = corr_pairs[2 * f + 1];
+    if (t < 0 || t >= num_poses || s < 0 || s >= num_poses || t == s) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: corr_pairs entries must be two different poses in [0, num_poses)");
+    else factor_slots[2 * ((size_t)F + f)] = g->slot[t], factor_slots[2 * ((size_t)F + f) + 1] = g->slot[s];
+  }
   for (int p = 0; p < P; p++) {  // between: (slot[a], slot[b]); prior: a unary record (-1, slot[a])
     const gp_pose_factor& pf = pose_factors[p];
     const bool between = pf.kind == GP_POSE_FACTOR_BETWEEN;
-    factor_slots[2 * ((size_t)F + p)] = between ? g->slot[pf.pose_a] : -1;
-    factor_slots[2 * ((size_t)F + p) + 1] = between ? g->slot[pf.pose_b] : g->slot[pf.pose_a];
+    factor_slots[2 * ((size_t)F + G + p)] = between ? g->slot[pf.pose_a] : -1;
+    factor_slots[2 * ((size_t)F + G + p) + 1] = between ? g->slot[pf.pose_b] : g->slot[pf.pose_a];
   }
   if (rc == GP_OK && g->slots == 0) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: every pose is held");
   gp_stream_t st = stream;
   if (rc == GP_OK && batch) rc = gp_vgicp_batch_stream(batch, &st);
   if (rc == GP_OK && batch && stream && stream != st) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: stream must be NULL or the batch's own");
+  if (rc == GP_OK && corr) {
+    gp_stream_t cs = nullptr;
+    rc = gp_corr_batch_stream(corr, &cs);
+    if (rc == GP_OK && batch && cs != st) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: the two batches must share one stream");
+    if (rc == GP_OK && !batch && stream && stream != cs) rc = gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: stream must be NULL or the batches' own");
+    if (rc == GP_OK && !batch) st = cs;
+  }
   g->stream = (hipStream_t)st;
   // one free pose: the dense step (a 6 x 6 system); else the block-sparse one
-  const int R = F + P;
+  const int R = F + G + P;
   if (rc == GP_OK) rc = g->slots == 1 ? gp_dense_system_create(1, factor_slots.data(), R, st, &g->dense) : gp_sparse_system_create(g->slots, factor_slots.data(), R, ordering, st, &g->sparse);
   if (rc == GP_OK) rc = g->sparse ? gp_sparse_system_device_solution(g->sparse, &g->x_dev, &g->status_dev) : gp_dense_system_device_solution(g->dense, &g->x_dev, &g->status_dev);
   const size_t vb = sizeof(double) * 16 * (size_t)num_poses, db = sizeof(double) * 16 * (size_t)F;
@@ -138,6 +163,11 @@ static int create_graph(gp_vgicp_batch_t* batch, int F, const int* pose_pairs, c
     if ((rc = g->d_values[k].alloc(vb)) || (rc = g->d_deltas[k].alloc(db)) || (rc = g->h_values[k].ensure(vb))) break;
   }
   if (rc == GP_OK) rc = g->d_pairs.alloc(sizeof(int) * 2 * (size_t)F);
+  for (int k = 0; k < 2 && rc == GP_OK; k++) rc = g->d_corr_deltas[k].alloc(sizeof(double) * 16 * (size_t)G);
+  if (rc == GP_OK) rc = g->d_corr_pairs.alloc(sizeof(int) * 2 * (size_t)G);
+  if (rc == GP_OK && G > 0 && hipMemcpy(g->d_corr_pairs.ptr, corr_pairs, sizeof(int) * 2 * (size_t)G, hipMemcpyHostToDevice) != hipSuccess)
+    rc = gp::fail(GP_ERROR_HIP, "gp_lm_graph_create_with_factors: upload of the corr pairs");
+  g->corr_errors.assign((size_t)G, 0.0);
   if (rc == GP_OK) rc = g->d_slot.alloc(sizeof(int) * (size_t)num_poses);
   for (int k = 0; k < 2 && rc == GP_OK; k++) rc = g->d_records[k].alloc(sizeof(gp_linearized6) * (size_t)R);
   if (rc == GP_OK && P > 0) rc = g->d_pose_factors.alloc(sizeof(gp_pose_factor) * (size_t)P);
@@ -161,7 +191,7 @@ int gp_lm_graph_create(gp_vgicp_batch_t* batch, const int* pose_pairs, int num_p
   *out = nullptr;
   const int F = batch ? gp_vgicp_batch_size(batch) : 0;
   if (!batch || F <= 0 || !pose_pairs || num_poses < 2) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create: a batch of >= 1 factors, pose_pairs [F][2], >= 2 poses");
-  return create_graph(batch, F, pose_pairs, nullptr, 0, num_poses, pose_fixed, ordering, nullptr, out);
+  return create_graph(batch, F, pose_pairs, nullptr, 0, nullptr, nullptr, 0, num_poses, pose_fixed, ordering, nullptr, out);
 }
 
 int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pose_pairs, const gp_pose_factor* pose_factors, int num_pose_factors, int num_poses,
@@ -172,7 +202,19 @@ int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pos
   if (F < 0 || (F > 0 && !pose_pairs)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: pose_pairs [F][2]");
   GP_TRY(gp::check_pose_factors(pose_factors, num_pose_factors, num_poses, "gp_lm_graph_create_with_pose_factors"));
   if (F + num_pose_factors == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_pose_factors: a graph without factors");
-  return create_graph(batch, F, pose_pairs, pose_factors, num_pose_factors, num_poses, pose_fixed, ordering, stream, out);
+  return create_graph(batch, F, pose_pairs, nullptr, 0, nullptr, pose_factors, num_pose_factors, num_poses, pose_fixed, ordering, stream, out);
+}
+
+int gp_lm_graph_create_with_factors(gp_vgicp_batch_t* batch, const int* vgicp_pairs, gp_corr_batch_t* corr, const int* corr_pairs, const gp_pose_factor* pose_factors,
+                                    int num_pose_factors, int num_poses, const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out) {
+  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: null out");
+  *out = nullptr;
+  if (!corr) return gp_lm_graph_create_with_pose_factors(batch, vgicp_pairs, pose_factors, num_pose_factors, num_poses, pose_fixed, ordering, stream, out);
+  const int F = batch ? gp_vgicp_batch_size(batch) : 0, G = gp_corr_batch_size(corr);
+  if (F < 0 || (F > 0 && !vgicp_pairs)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: vgicp_pairs [F][2]");
+  if (G <= 0 || !corr_pairs || num_poses < 2) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_create_with_factors: corr_pairs [G][2], >= 2 poses");
+  GP_TRY(gp::check_pose_factors(pose_factors, num_pose_factors, num_poses, "gp_lm_graph_create_with_factors"));
+  return create_graph(batch, F, vgicp_pairs, corr, G, corr_pairs, pose_factors, num_pose_factors, num_poses, pose_fixed, ordering, stream, out);
 }
 
 // 0: no linearise is queued ahead of the host's decision (measurement / A-B; results are the same bits either way).  Returns the previous setting.
@@ -232,7 +274,8 @@ int gp_lm_graph_linearize(gp_lm_graph_t* g) {
   if (!g || !g->have_values) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_lm_graph_linearize: set the values first");
   if (!g->spec_valid) {  // (else: queued behind the accepted trial's error evaluation)
     if (g->batch) GP_TRY(gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[g->cur].as<double>(), g->rigid ? 1 : 0, g->d_records[g->rec].as<gp_linearized6>()));
-    GP_TRY(gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[g->cur].as<double>(), g->d_records[g->rec].as<gp_linearized6>() + g->F, nullptr, g->stream));
+    if (g->corr) GP_TRY(gp_corr_batch_issue_linearize_dev(g->corr, g->d_corr_deltas[g->cur].as<double>(), g->rigid ? 1 : 0, g->rec, g->d_records[g->rec].as<gp_linearized6>() + g->F));
+    GP_TRY(gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[g->cur].as<double>(), g->d_records[g->rec].as<gp_linearized6>() + g->F + g->G, nullptr, g->stream));
   }
   g->spec_valid = false;
   g->linearized = true, g->tried = false;
@@ -261,8 +304,10 @@ int gp_lm_graph_try_lambda(gp_lm_graph_t* g, double lambda, int diagonal_damping
   // the pose factors at the trial values the retract has just written (an indeterminate step leaves them = the current values): their errors, and with speculation
   // their records for the next linearisation, in one launch -- in front of the batch's error evaluation, whose completion words therefore cover them
   if (rc == GP_OK)
-    rc = gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[to].as<double>(), g->speculate ? g->d_records[1 - g->rec].as<gp_linearized6>() + g->F : nullptr,
+    rc = gp::launch_pose_factors(g->d_pose_factors.as<gp_pose_factor>(), g->P, g->d_values[to].as<double>(), g->speculate ? g->d_records[1 - g->rec].as<gp_linearized6>() + g->F + g->G : nullptr,
                                  g->h_pose_errors.as<double>(), g->stream);
+  // the GICP / ICP factors' errors at the trial deltas, on the correspondences of the linearisation point (set rec): in front of the VGICP batch's evaluation
+  if (rc == GP_OK && g->corr) rc = gp::corr_batch_error_begin(g->corr, g->rec, g->d_corr_deltas[g->cur].as<double>(), g->d_corr_deltas[to].as<double>());
   if (rc == GP_OK && g->batch) rc = gp_vgicp_batch_issue_compute_error_dev_begin(g->batch, g->d_deltas[g->cur].as<double>(), g->d_deltas[to].as<double>());
   if (rc != GP_OK) {  // the step went out: collect it (its own wait) before the error is reported
     if (g->sparse) (void)gp_sparse_system_finish_step(g->sparse, nullptr, nullptr, nullptr);
@@ -271,12 +316,18 @@ int gp_lm_graph_try_lambda(gp_lm_graph_t* g, double lambda, int diagonal_damping
   }
   bool spec = false;
   if (g->speculate) spec = !g->batch || gp_vgicp_batch_issue_linearize_dev(g->batch, g->d_deltas[to].as<double>(), g->rigid ? 1 : 0, g->d_records[1 - g->rec].as<gp_linearized6>()) == GP_OK;
+  // (into the OTHER correspondence set: a rejected trial must leave set rec as the linearisation point's.  As for the VGICP batch above, a speculative launch that
+  //  fails is swallowed on purpose: spec = false, and the next gp_lm_graph_linearize issues the linearise itself and reports its error)
+  if (g->speculate && spec && g->corr)
+    spec = gp_corr_batch_issue_linearize_dev(g->corr, g->d_corr_deltas[to].as<double>(), g->rigid ? 1 : 0, 1 - g->rec, g->d_records[1 - g->rec].as<gp_linearized6>() + g->F) == GP_OK;
   // the call's ONE wait: the completion words of the error evaluation (everything in front of it on the stream -- the step, the trial values, the pose factors -- is
   // then complete and its pinned results are readable; the speculative linearise behind it is not waited for).  Without a batch: the step's own finish, behind the
   // pose factors' launch.
   int rs;
-  if (g->batch) {
-    rc = gp_vgicp_batch_compute_error_dev_end(g->batch, g->errors.data());
+  if (g->batch || g->corr) {
+    // (with both: the VGICP words are behind the corr batch's on the stream, so those have arrived and their poll returns at once)
+    if (g->batch) rc = gp_vgicp_batch_compute_error_dev_end(g->batch, g->errors.data());
+    if (rc == GP_OK && g->corr) rc = gp::corr_batch_error_end(g->corr, g->corr_errors.data(), 400);  // (+ the damped step queued in front of it)
     rs = g->sparse ? (rc == GP_OK ? gp_sparse_system_collect_step(g->sparse, x_host, b_host, c_host) : gp_sparse_system_finish_step(g->sparse, x_host, b_host, c_host))
                    : (rc == GP_OK ? gp_dense_system_collect_step(g->dense, x_host, b_host, c_host) : gp_dense_system_finish_step(g->dense, x_host, b_host, c_host));
   } else {
@@ -289,6 +340,7 @@ int gp_lm_graph_try_lambda(gp_lm_graph_t* g, double lambda, int diagonal_damping
   if (new_error) {
     double e = 0.0;
     for (int f = 0; f < g->F; f++) e += g->errors[(size_t)f];
+    for (int f = 0; f < g->G; f++) e += g->corr_errors[(size_t)f];
     const double* pe = g->h_pose_errors.as<double>();
     for (int p = 0; p < g->P; p++) e += pe[p];
     *new_error = e;

@@ -80,9 +80,14 @@ struct LmPoseView {
   double* values_host;    // [N][16] pinned, may be null
   double* deltas_out;     // [F][16]
   int F, N;
+  // a second group of pairwise factors with a delta table of its own (the GICP / ICP batch, gp_corr_batch.hip): G = 0 without one
+  const int* corr_pairs;      // [G][2] (target pose, source pose)
+  double* corr_deltas_out;    // [G][16]
+  int G;
+  __host__ __device__ int threads() const { return F > N ? (F > G ? F : G) : (N > G ? N : G); }  // what a caller of lm_poses_thread covers: max(F, G, N)
 };
 
-// thread i of n >= max(F, N): factor i's relative pose at the (retracted) values, and pose i's (retracted) value.  x: the step in slot order (null: no step -- the relative
+// thread i of n >= v.threads() = max(F, G, N): factor i's relative pose at the (retracted) values, and pose i's (retracted) value.  x: the step in slot order (null: no step -- the relative
 // poses of `values` themselves); failed: the step was indeterminate (the trial is the current values).  A pose shared by several factors is retracted by each of
 // them from the same operands with the same instructions: the same bits everywhere.
 __device__ __forceinline__ void lm_poses_thread(const LmPoseView& v, const int i, const double* __restrict__ x, const bool failed) {
@@ -95,6 +100,10 @@ __device__ __forceinline__ void lm_poses_thread(const LmPoseView& v, const int i
   if (i < v.F) {
     const Rigid D = between_rigid(value(v.pairs[2 * i]), value(v.pairs[2 * i + 1]));
     store_rigid(D, v.deltas_out + 16 * (size_t)i);
+  }
+  if (i < v.G) {
+    const Rigid D = between_rigid(value(v.corr_pairs[2 * i]), value(v.corr_pairs[2 * i + 1]));
+    store_rigid(D, v.corr_deltas_out + 16 * (size_t)i);
   }
   if (i < v.N && (v.values_out || v.values_host)) {
     const Rigid T = value(i);

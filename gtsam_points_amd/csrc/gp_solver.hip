@@ -272,7 +272,7 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
     out_host[13] = (double)st;
   }
   if (has_epi) {  // the device-resident LM trial's poses (gp_lm_poses.hpp) while x is at hand: one launch less behind the step
-    const int n = max(epi.F, epi.N);
+    const int n = epi.threads();
     for (int i = t; i < n; i += 64) lm_poses_thread(epi, i, xx, st != 0);
   }
 }

@@ -1743,7 +1743,7 @@ __global__ void __launch_bounds__(kSmallThreads) sparse_small_step_kernel(const 
   if (V.has_epi) {
     // the trial's poses (gp_lm.hip: lm_poses_kernel's work) while this workgroup still has x at hand: one launch less behind the step
     __syncthreads();
-    const int n = max(V.epi.F, V.epi.N);
+    const int n = V.epi.threads();
     for (int i = t; i < n; i += kSmallThreads) lm_poses_thread(V.epi, i, ys, bad != 0);
   }
   if (t == 0) {

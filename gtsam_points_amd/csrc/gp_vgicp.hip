@@ -431,6 +431,26 @@ int launch_finalize_error_single(hipStream_t stream, const double* partials, int
   return e == hipSuccess ? GP_OK : hip_fail(e, "vgicp_finalize_error_kernel", __FILE__, __LINE__);
 }
 
+// the same kernels as the two launchers above, one workgroup per factor of a table: rows [tile_begin, tile_begin + tile_count) of factor f, its pose at poses_dev + 16 f,
+// its record at out_dev + f (its completion word at done.flags + f).  Same order of sums as the single-factor forms: the same bits.
+int launch_finalize_table(hipStream_t stream, const FactorDesc* factors_dev, int num_factors, const double* poses_dev, const double* partials, gp_linearized6* out_dev,
+                          bool general, DoneFlags done) {
+  InlinePoses inl{};
+  inl.use = 0;
+  if (general)
+    hipLaunchKernelGGL(vgicp_finalize_kernel<true>, dim3(num_factors), dim3(kFinalizeThreads), 0, stream, factors_dev, poses_dev, inl, partials, out_dev, done);
+  else
+    hipLaunchKernelGGL(vgicp_finalize_rigid_kernel<kFinalizeThreads>, dim3(num_factors), dim3(kFinalizeThreads), 0, stream, factors_dev, poses_dev, inl, partials, out_dev, done, 1);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GP_OK : hip_fail(e, "vgicp_finalize_kernel", __FILE__, __LINE__);
+}
+
+int launch_finalize_error_table(hipStream_t stream, const FactorDesc* factors_dev, int num_factors, const double* partials, double* out_dev, DoneFlags done) {
+  hipLaunchKernelGGL(vgicp_finalize_error_kernel, dim3(num_factors), dim3(kBlockThreads), 0, stream, factors_dev, partials, out_dev, -1, done);
+  hipError_t e = hipGetLastError();
+  return e == hipSuccess ? GP_OK : hip_fail(e, "vgicp_finalize_error_kernel", __FILE__, __LINE__);
+}
+
 }  // namespace gp
 
 // ---------------------------------------------------------------------------------------------------------------

@@ -233,5 +233,9 @@ inline bool pose_is_rigid(const double* m) {
   return det > 0.0;
 }
 int launch_finalize_error_single(hipStream_t stream, const double* partials, int num_tiles, double* out_dev, DoneFlags done = {});
+// ... and for a table of factors in device memory (gp_corr_batch.hip): only tile_begin / tile_count of a FactorDesc are read; poses_dev [num_factors][16]
+int launch_finalize_table(hipStream_t stream, const FactorDesc* factors_dev, int num_factors, const double* poses_dev, const double* partials, gp_linearized6* out_dev,
+                          bool general, DoneFlags done = {});
+int launch_finalize_error_table(hipStream_t stream, const FactorDesc* factors_dev, int num_factors, const double* partials, double* out_dev, DoneFlags done = {});
 
 }  // namespace gp

@@ -5,6 +5,7 @@
   estimate_normals_gpu      <- features/normal_estimation.hpp:estimate_normals(points, k=10); estimate_normals_covariances_gpu: both from one search
   IntegratedGICPFactorGPU   <- factors/integrated_gicp_factor.hpp (CPU-only upstream), same calc_delta / HessianFactor protocol
   IntegratedICPFactorGPU    <- factors/integrated_icp_factor.hpp (point-to-point / point-to-plane; CPU-only upstream), on a shared KdTreeGPU
+  CorrespondenceFactorBatchGPU  any number of the two factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
 """
 import ctypes as C
 
@@ -143,6 +144,7 @@ class IntegratedGICPFactorGPU:
             "gp_gicp_factor_create_ex",
         )
         self._h = h
+        self.stream = stream
         self.linearization_point = np.eye(4)
         self._num_inliers = 0
 
@@ -218,6 +220,7 @@ class IntegratedICPFactorGPU:
             "gp_icp_factor_create",
         )
         self._h = h
+        self.stream = stream
         self.linearization_point = np.eye(4)
         self._num_inliers = 0
 
@@ -271,3 +274,99 @@ def IntegratedPointToPlaneICPFactorGPU(target_key, source_key, target, source, t
     """IntegratedPointToPlaneICPFactor_ (factors/integrated_icp_factor.hpp): the ICP factor with use_point_to_plane = true"""
     return IntegratedICPFactorGPU(target_key, source_key, target, source, target_tree=target_tree, use_point_to_plane=True,
                                   max_correspondence_distance=max_correspondence_distance, stream=stream, _fixed_target_pose=_fixed_target_pose)
+
+
+def _poses16(deltas, count):
+    d = np.asarray(deltas, dtype=np.float64)
+    if d.shape != (count, 4, 4):
+        raise ValueError(f"poses must be [{count}, 4, 4]")
+    return np.ascontiguousarray(d.transpose(0, 2, 1)).reshape(count, 16)
+
+
+class CorrespondenceFactorBatchGPU:
+    """IntegratedGICPFactorGPU / IntegratedICPFactorGPU objects linearised and evaluated TOGETHER (gp_corr_batch_*, csrc/gp_corr_batch.hip): one search launch, one tile
+    launch per factor kind, one finalize launch, whatever their number, with the relative poses read from device memory.  Record order: the GICP factors in the
+    order given, then the ICP factors in the order given (`order`: positions in `factors`; the results below are returned in the order of `factors`).
+    The batch borrows the factors (kept alive here) and keeps correspondences of its own, in two sets: a linearise searches into the set it names (default 0), an
+    error evaluation reads the set it names and never searches.  A record / an error has the bits of the factor's own linearize_delta / error at the same pose(s).
+    ICP factors with non-zero correspondence-update tolerances are refused."""
+
+    def __init__(self, factors, stream=None):
+        self._lib = _capi.load()
+        self.factors = list(factors)
+        gicp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedGICPFactorGPU)]
+        icp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedICPFactorGPU)]
+        if len(gicp) + len(icp) != len(self.factors):
+            raise TypeError("CorrespondenceFactorBatchGPU takes IntegratedGICPFactorGPU / IntegratedICPFactorGPU objects")
+        self.order = gicp + icp  # record r is factors[order[r]]
+        if stream is None and self.factors:
+            stream = self.factors[0].stream  # the stream the factors were created on (the library refuses a batch whose factors live on different streams)
+        self._slot = np.argsort(np.asarray(self.order, dtype=np.int64)) if self.factors else np.zeros(0, np.int64)  # factors[i] is record _slot[i]
+        self.stream = stream
+        ga = (C.c_void_p * max(len(gicp), 1))(*[self.factors[i]._h.value for i in gicp])
+        ia = (C.c_void_p * max(len(icp), 1))(*[self.factors[i]._h.value for i in icp])
+        h = C.c_void_p()
+        _capi.check(self._lib.gp_corr_batch_create(ga, len(gicp), ia, len(icp), stream, C.byref(h)), "gp_corr_batch_create")
+        self._h = h
+        self._dev = None
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_corr_batch_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def __len__(self):
+        return len(self.factors)
+
+    def _records_order(self, poses):
+        return np.ascontiguousarray(_poses16(poses, len(self.factors))[self.order])
+
+    def _upload(self, p16):
+        import torch
+
+        t = torch.from_numpy(p16).to("cuda")
+        torch.cuda.synchronize()
+        return t
+
+    def linearize_deltas(self, deltas, rigid=True, corr_set=None):
+        """deltas [F, 4, 4] in the order of `factors` -> [LinearizedSystem6] in that order.  rigid: every 3x3 block is orthonormal to 1e-9 (the 29-sum kernels, what
+        the factors' own calls choose for such poses); False: the general kernels.  corr_set: None = the synchronous host-pose call (set 0); 0 / 1 = the device-pose
+        entry point into that correspondence set."""
+        F = len(self.factors)
+        p16 = self._records_order(deltas)
+        out = np.zeros((F, _capi.LINEARIZED6_DOUBLES))
+        if corr_set is None:
+            _capi.check(self._lib.gp_corr_batch_linearize(self._h, p16.ctypes.data, int(bool(rigid)), out.ctypes.data), "gp_corr_batch_linearize")
+        else:
+            import torch
+
+            poses = self._upload(p16)
+            rec = torch.zeros((F, _capi.LINEARIZED6_DOUBLES), dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            _capi.check(self._lib.gp_corr_batch_issue_linearize_dev(self._h, C.c_void_p(poses.data_ptr()), int(bool(rigid)), int(corr_set), C.c_void_p(rec.data_ptr())),
+                        "gp_corr_batch_issue_linearize_dev")
+            _capi.check(self._lib.gp_corr_batch_sync(self._h), "gp_corr_batch_sync")
+            out = rec.cpu().numpy()
+        return [LinearizedSystem6.from_doubles(out[self._slot[i]]) for i in range(F)]
+
+    def errors(self, deltas_lin, deltas_eval, corr_set=None):
+        """the factors' errors at deltas_eval on the stored correspondences of set `corr_set` (None: the synchronous host-pose call on set 0), deltas_lin being the poses that
+        set was linearised at -> float64 [F] in the order of `factors`"""
+        F = len(self.factors)
+        pl, pe = self._records_order(deltas_lin), self._records_order(deltas_eval)
+        out = np.zeros(F)
+        if corr_set is None:
+            _capi.check(self._lib.gp_corr_batch_compute_error(self._h, pl.ctypes.data, pe.ctypes.data, out.ctypes.data), "gp_corr_batch_compute_error")
+        else:
+            import torch
+
+            dl, de = self._upload(pl), self._upload(pe)
+            err = torch.zeros(F, dtype=torch.float64, device="cuda")
+            torch.cuda.synchronize()
+            _capi.check(self._lib.gp_corr_batch_issue_compute_error_dev(self._h, int(corr_set), C.c_void_p(dl.data_ptr()), C.c_void_p(de.data_ptr()), C.c_void_p(err.data_ptr()),
+                                                                        None, 0), "gp_corr_batch_issue_compute_error_dev")
+            _capi.check(self._lib.gp_corr_batch_sync(self._h), "gp_corr_batch_sync")
+            out = err.cpu().numpy()
+        return out[self._slot].copy()

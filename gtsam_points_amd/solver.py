@@ -314,12 +314,19 @@ class LevenbergMarquardtGraphGPU:
 
     factors: IntegratedVGICPFactorGPU objects; pairs[i] = (target pose, source pose) of factor i, poses 0..num_poses-1; fixed: indices of held poses.
     pose_factors: BetweenFactorPose3 / PriorFactorPose3 objects over the same poses (gp_lm_graph_create_with_pose_factors): their records follow the VGICP ones,
-    `factors` may then be empty (a pose graph) and `fixed` may be () (the priors fix the gauge).  values are [num_poses, 4, 4] float64 arrays (rigid)."""
+    `factors` may then be empty (a pose graph) and `fixed` may be () (the priors fix the gauge).  values are [num_poses, 4, 4] float64 arrays (rigid).
+    corr_factors: IntegratedGICPFactorGPU / IntegratedICPFactorGPU objects, corr_pairs[i] = (target pose, source pose) of corr_factors[i]
+    (gp_lm_graph_create_with_factors): the graph builds and owns a CorrespondenceFactorBatchGPU over them; their records lie between the VGICP ones and the pose
+    factors', in the batch's record order (GICP factors first, then ICP, each in the order given: `corr_order`).  The trials evaluate them on the correspondences
+    of the linearisation point, whether or not a linearise at a trial's values was queued ahead (two correspondence sets)."""
 
-    def __init__(self, factors, pairs, num_poses, fixed=(0,), ordering="auto", stream=None, pose_factors=()):
+    def __init__(self, factors, pairs, num_poses, fixed=(0,), ordering="auto", stream=None, pose_factors=(), corr_factors=(), corr_pairs=()):
         self._lib = _capi.load()
         self.factors = list(factors)  # (kept alive: the batch holds their handles)
         self.pose_factors = list(pose_factors)
+        self.corr_factors = list(corr_factors)
+        self._corr = None
+        self.corr_order = []
         self._stream = stream
         F = len(self.factors)
         self.pairs = np.ascontiguousarray(np.asarray(pairs, dtype=np.int32).reshape(-1, 2))
@@ -329,13 +336,27 @@ class LevenbergMarquardtGraphGPU:
         held = np.zeros(self.num_poses, dtype=np.uint8)
         held[list(fixed)] = 1
         self._batch, self._h = C.c_void_p(), C.c_void_p()
-        if F > 0 or not self.pose_factors:
+        cp = np.ascontiguousarray(np.asarray(corr_pairs, dtype=np.int32).reshape(-1, 2))
+        if len(cp) != len(self.corr_factors):
+            raise ValueError(f"{len(self.corr_factors)} correspondence factors, {len(cp)} pose pairs")
+        if self.corr_factors:
+            from .features import CorrespondenceFactorBatchGPU
+
+            self._corr = CorrespondenceFactorBatchGPU(self.corr_factors, stream=stream)
+            self.corr_order = list(self._corr.order)
+            self.corr_pairs = np.ascontiguousarray(cp[self.corr_order])  # in record order
+        if F > 0 or not (self.pose_factors or self.corr_factors):
             arr = (C.c_void_p * F)(*[f._h.value for f in self.factors])
             _capi.check(self._lib.gp_vgicp_batch_create(arr, F, stream, C.byref(self._batch)), "gp_vgicp_batch_create")
         else:
             self._batch = None
         try:
-            if self.pose_factors:
+            if self.corr_factors:
+                _capi.check(self._lib.gp_lm_graph_create_with_factors(self._batch, self.pairs.ctypes.data, self._corr._h, self.corr_pairs.ctypes.data,
+                                                                     _pose_factor_array(self.pose_factors) if self.pose_factors else None, len(self.pose_factors),
+                                                                     self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
+                            "gp_lm_graph_create_with_factors")
+            elif self.pose_factors:
                 _capi.check(self._lib.gp_lm_graph_create_with_pose_factors(self._batch, self.pairs.ctypes.data, _pose_factor_array(self.pose_factors), len(self.pose_factors),
                                                                           self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
                             "gp_lm_graph_create_with_pose_factors")
@@ -345,6 +366,8 @@ class LevenbergMarquardtGraphGPU:
             if self._batch:
                 self._lib.gp_vgicp_batch_destroy(self._batch)
             self._batch = None
+            if self._corr is not None:
+                self._corr.close()
             raise
         self.n = self._lib.gp_lm_graph_num_variables(self._h)
         self._x, self._b, self._c, self._e = np.zeros(self.n), np.zeros(self.n), np.zeros(1), np.zeros(1)
@@ -357,6 +380,9 @@ class LevenbergMarquardtGraphGPU:
         if getattr(self, "_batch", None):
             self._lib.gp_vgicp_batch_destroy(self._batch)
             self._batch = None
+        if getattr(self, "_corr", None) is not None:
+            self._corr.close()
+            self._corr = None
 
     __del__ = close
 
@@ -382,17 +408,20 @@ class LevenbergMarquardtGraphGPU:
     def sync(self):
         if self._batch:
             _capi.check(self._lib.gp_vgicp_batch_sync(self._batch), "gp_vgicp_batch_sync")
+        elif self._corr is not None:
+            _capi.check(self._lib.gp_corr_batch_sync(self._corr._h), "gp_corr_batch_sync")
         else:
             _capi.check(self._lib.gp_stream_synchronize(self._stream), "gp_stream_synchronize")
 
     def records(self):
-        """-> [F + P, 122] float64 CUDA tensor: a copy of the records of the last linearise (the VGICP factors', then the pose factors')"""
+        """-> [F + G + P, 122] float64 CUDA tensor: a copy of the records of the last linearise (the VGICP factors', then the correspondence factors' in the
+        batch's record order -- corr_factors[corr_order[r]] --, then the pose factors')"""
         import torch
 
         p = C.c_void_p()
         _capi.check(self._lib.gp_lm_graph_records(self._h, C.byref(p), None), "gp_lm_graph_records")
         self.sync()
-        n = (len(self.factors) + len(self.pose_factors)) * _capi.LINEARIZED6_DOUBLES
+        n = (len(self.factors) + len(self.corr_factors) + len(self.pose_factors)) * _capi.LINEARIZED6_DOUBLES
         out = torch.zeros(n, dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
         _capi.check(self._lib.gp_memcpy_d2d(C.c_void_p(out.data_ptr()), p, 8 * n, None), "gp_memcpy_d2d")

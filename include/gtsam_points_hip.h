@@ -469,6 +469,39 @@ int gp_icp_factor_set_correspondence_update_tolerance(gp_icp_factor_t* f, double
 /* source points that had a correspondence in the last linearise (= its record's num_inliers); 0 before one */
 int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f);
 
+/* ---- a batch of GICP / ICP factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
+ * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of
+ * launches that does not depend on their count -- one search launch, one tile launch per factor kind present (GICP, ICP point-to-point, ICP point-to-plane), one
+ * finalize launch --, the poses read from a table double[F][16] (column-major) in device memory.  The batch BORROWS the factor handles (the caller keeps them and
+ * their clouds alive) and keeps correspondences of its own: a batch pass does not touch what the factors' own calls store, and the other way round.
+ *   record order  the GICP factors in the order given, then the ICP factors in the order given: pose f, record f and error f belong to member f.
+ *   create        GP_ERROR_INVALID_ARGUMENT for: a NULL handle, a factor created on another stream than `stream`, an empty batch (num_gicp + num_icp = 0), an ICP factor
+ *                 whose correspondence-update tolerances are not both zero (that keep-or-search decision is host logic on a host pose; in a batch every linearise
+ *                 searches: the reference's default for both factor types).
+ *   sets          the batch holds TWO sets of correspondences, set 0 and set 1.  A linearise searches every member's correspondences at its pose INTO the set it names
+ *                 and sums on them; an error evaluation reads the set it names and never searches -- the reference's error(), which evaluates on the correspondences
+ *                 of the last linearise.  So a caller that linearises ahead (gp_lm_graph_*: at a trial's values, into the other set) still evaluates further trials on
+ *                 the correspondences of its linearisation point.  Evaluating a set that was never linearised: GP_ERROR_INVALID_ARGUMENT.
+ *   rigid         as gp_vgicp_batch_issue_linearize_dev: 1 = the caller vouches that every 3x3 block is orthonormal to 1e-9 (29 sums + adjoint expansion, what the
+ *                 factors' own calls choose for such a pose), 0 = the 92 explicit sums with J_s from the block as given.
+ *   bits          a record / an error equals, bit for bit, that of the member's own gp_*_factor_linearize / _compute_error at the same pose(s) (same terms, same
+ *                 1024-point tiles, same order of sums).  A member without points, or none of whose points has a target within the cut-off: an all-zero record, error 0.
+ * The issue_ forms are asynchronous on the batch's stream.  issue_compute_error_dev: out [F] may be device or host-mapped memory; done_flags (may be NULL) = F words of
+ * host-mapped memory, word f receives done_seq behind error f (for a caller that polls instead of synchronising the stream).
+ * gp_corr_batch_linearize / _compute_error: the synchronous host-pose forms on set 0 (poses up, wait, results down); compute_error evaluates on the correspondences of
+ * the last linearise into set 0, with poses_lin the poses of that linearise (GICP's fused covariances are taken at them). */
+typedef struct gp_corr_batch gp_corr_batch_t;
+int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out);
+int gp_corr_batch_destroy(gp_corr_batch_t* batch); /* synchronises the batch's stream; leaves the factors alone */
+int gp_corr_batch_size(const gp_corr_batch_t* batch);
+int gp_corr_batch_stream(const gp_corr_batch_t* batch, gp_stream_t* out);
+int gp_corr_batch_sync(gp_corr_batch_t* batch);
+int gp_corr_batch_issue_linearize_dev(gp_corr_batch_t* batch, const double* poses_dev, int rigid, int set, gp_linearized6* out_dev);
+int gp_corr_batch_issue_compute_error_dev(gp_corr_batch_t* batch, int set, const double* poses_lin_dev, const double* poses_eval_dev, double* out,
+                                          unsigned long long* done_flags, unsigned long long done_seq);
+int gp_corr_batch_linearize(gp_corr_batch_t* batch, const double* poses_host, int rigid, gp_linearized6* out_host);
+int gp_corr_batch_compute_error(gp_corr_batch_t* batch, const double* poses_lin_host, const double* poses_eval_host, double* out_host);
+
 /* ---- the step after the path: damped normal equations assembled and solved on the device ----
  * DenseLinearSystemBuilder (optimizers/linear_system_builder.cpp:39-48): A = sum of the Hessian blocks scattered by key,
  *   b = sum of g (= -b_target / -b_source, integrated_matching_cost_factor.cpp:49), c = sum of the errors;
@@ -600,7 +633,8 @@ int gp_lm_graph_set_speculation(gp_lm_graph_t* graph, int enable);
  * its own behind it; default 1: the one-launch step where the system qualifies, the retract as its epilogue).  Same bits. */
 int gp_lm_graph_set_one_launch(gp_lm_graph_t* graph, int enable);
 int gp_lm_graph_optimize(gp_lm_graph_t* graph, const gp_lm_params* params, gp_lm_summary* summary);
-/* for checkers: the records of the last linearise (F, then the pose factors' P: gp_lm_graph_create_with_pose_factors) and the relative poses of the current values, where
+/* for checkers: the records of the last linearise (the VGICP batch's F, then the corr batch's G: gp_lm_graph_create_with_factors, then the pose factors' P:
+ * gp_lm_graph_create_with_pose_factors) and the relative poses of the current values (the VGICP members'), where
  * they lie in device memory (valid until the graph is destroyed; contents as of the work queued so far on the graph's stream) */
 int gp_lm_graph_records(gp_lm_graph_t* graph, const gp_linearized6** records_dev, const double** relative_poses_dev);
 
@@ -639,6 +673,17 @@ int gp_pose_factors_compute_error(gp_pose_factors_t* pf, const double* poses_hos
  * refuses values that are not orthonormal to 1e-9 (GP_ERROR_INVALID_ARGUMENT).  Refusals as gp_pose_factors_create, and a graph with no factor at all. */
 int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pose_pairs, const gp_pose_factor* pose_factors, int num_pose_factors, int num_poses,
                                          const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out);
+/* ... and with a batch of GICP / ICP factors (gp_corr_batch_*) as a third group: corr member i is the pairwise factor between poses corr_pairs[2 i] (target) and
+ * corr_pairs[2 i + 1] (source), evaluated at target^-1 source like a VGICP member.  Any of the three groups may be absent (batch NULL, corr NULL, num_pose_factors 0),
+ * not all of them.  Records (gp_lm_graph_records), and the order of the host's sum for new_error: the VGICP batch's at [0, F), the corr batch's at [F, F + G), the
+ * pose factors' at [F + G, F + G + P); the damped system covers all of them.  The graph borrows both batches; they share one stream (`stream`: NULL or that stream
+ * when a batch is given).
+ * Sets and speculation: linearize searches the corr members' correspondences into the set that goes with the current record buffer; try_lambda evaluates their errors
+ * on THAT set at the trial values (queued in front of the VGICP batch's evaluation, whose completion words then cover it; without a VGICP batch the corr batch's own
+ * words are polled: one wait either way); the speculative linearise at the trial values searches into the OTHER set, and accept swaps set and record buffer together.
+ * A rejected trial therefore leaves the correspondences of the linearisation point in place for the next lambda.  The graph's rigid flag (set_values) is passed on. */
+int gp_lm_graph_create_with_factors(gp_vgicp_batch_t* batch, const int* vgicp_pairs, gp_corr_batch_t* corr, const int* corr_pairs, const gp_pose_factor* pose_factors,
+                                    int num_pose_factors, int num_poses, const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out);
 
 /* ---- voxelgrid_sampling / randomgrid_sampling / sample on the device (gp_sampling.hip) ----
  * Device counterparts of types/point_cloud_cpu.hpp:110-156 (point_cloud_cpu_funcs.cpp:27-75, 119-295, 298-456; CPU-only upstream).
