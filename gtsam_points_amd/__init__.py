@@ -22,6 +22,9 @@ from .features import (  # noqa: F401
     CorrespondenceFactorBatchGPU,
     IntegratedGICPFactorGPU,
     IntegratedICPFactorGPU,
+    IntegratedLOAMFactorGPU,
+    IntegratedPointToEdgeFactorGPU,
+    IntegratedPointToPlaneFactorGPU,
     IntegratedPointToPlaneICPFactorGPU,
     KdTreeGPU,
     estimate_covariances_gpu,
@@ -58,6 +61,9 @@ __all__ = [
     "CorrespondenceFactorBatchGPU",
     "IntegratedICPFactorGPU",
     "IntegratedPointToPlaneICPFactorGPU",
+    "IntegratedLOAMFactorGPU",
+    "IntegratedPointToEdgeFactorGPU",
+    "IntegratedPointToPlaneFactorGPU",
     "IntegratedVGICPFactorGPU",
     "KdTreeGPU",
     "estimate_covariances_gpu",

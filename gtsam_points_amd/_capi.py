@@ -197,7 +197,17 @@ _SIGNATURES = {
     "gp_icp_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gp_icp_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "gp_icp_factor_num_correspondences": (C.c_int, [C.c_void_p]),
-    # a batch of GICP / ICP factors with device-resident poses (gp_corr_batch.hip)
+    # LOAM point-to-edge / point-to-plane / combined factor (gp_corr_factors.hip)
+    "gp_loam_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_loam_factor_destroy": (C.c_int, [C.c_void_p]),
+    "gp_loam_factor_set_max_correspondence_distance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "gp_loam_factor_set_enable_correspondence_validation": (C.c_int, [C.c_void_p, C.c_int]),
+    "gp_loam_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "gp_loam_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(Linearized6)]),
+    "gp_loam_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gp_loam_factor_num_correspondences": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    # a batch of GICP / ICP / LOAM factors with device-resident poses (gp_corr_batch.hip)
+    "gp_corr_batch_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_destroy": (C.c_int, [C.c_void_p]),
     "gp_corr_batch_size": (C.c_int, [C.c_void_p]),

@@ -1,5 +1,5 @@
-// gp_corr_batch.hip -- a batch of matching-cost factors on 1-NN correspondences (GICP, point-to-point and point-to-plane ICP: gp_corr_factors.hip) whose relative
-// poses live in DEVICE memory: what gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor, and what the device-resident LM graph
+// gp_corr_batch.hip -- a batch of matching-cost factors on nearest-neighbour correspondences (GICP, point-to-point and point-to-plane ICP, LOAM edge / plane /
+// combined: gp_corr_factors.hip) whose relative poses live in DEVICE memory: what gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor, and what the device-resident LM graph
 // (gp_lm.hip) queues for these factors.
 //
 // A single factor's linearise is three launches and a wait with its pose in the kernel arguments (gp_{gicp,icp}_factor_linearize); F of them are 3 F launches and F
@@ -15,6 +15,13 @@
 // Correspondences are kept in TWO sets.  The LM graph queues a speculative linearise at a trial's values behind the trial's error evaluation; were there one set, a
 // REJECTED trial would leave the next trial evaluating on the correspondences of the rejected point instead of those of the linearisation point.  A linearise names
 // the set it searches into, an error evaluation the set it reads; the partial rows of the two passes are separate buffers.
+//
+// LOAM members.  Internally the batch is a list of PARTS: a GICP or ICP member is one part, a LOAM member its edge part, its plane part, or both in that order.  Tiles,
+// rows, search descriptors and the finalize kernels' table are per part.  With a two-part member present the parts outnumber the members, and two small launches
+// frame a pass: one hands every part its member's pose, one adds a member's part records (errors) in part order in f64 into the member's record -- the sum
+// gp_loam_factor_linearize forms on the host, so the bits agree.  Without one, part p IS member p and neither launch exists: a batch of GICP / ICP members runs
+// exactly the launches it ran before.  The LOAM parts add one search launch (K = 2 and 3 together, gp_knn.hip: nearest_k_correspond_batch_kernel), one tile launch
+// per term kind present, and the validation launch when a member enables it; none of these counts depends on the number of members.
 // Not thread-safe per handle, re-entrant across handles, like the rest of the library.
 #include <type_traits>
 #include <vector>
@@ -66,6 +73,68 @@ __global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const CorrBatchDe
   store_tile_sums_row<MODE>(acc, partials + (size_t)t.row * STRIDE);
 }
 
+// what the LOAM tile kernels and the validation read of part t.factor (a table of its own beside CorrBatchDesc, which the GICP / ICP kernels keep as it is)
+struct LoamBatchDesc {
+  const float* points;         // [n][3] source
+  const float* target_points;  // [num_target][3]
+  int* corr[2];                // int[K][n] each: the two correspondence sets
+  int n;
+  int k;         // 2: edge part, 3: plane part
+  int validate;  // the member's enable_correspondence_validation
+  int pad_;
+};
+
+// corr_batch_tiles_kernel for the LOAM terms: the same tile, lanes and reduction; a term is handed corr + i and the stride n (gp_corr_factors.hpp)
+template <int MODE, class TERM>
+__global__ void __launch_bounds__(256) loam_batch_tiles_kernel(const LoamBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
+                                                               const double* __restrict__ poses_eval, const int set, double* __restrict__ partials) {
+  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
+  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
+  const CorrTile t = tiles[blockIdx.x];
+  const LoamBatchDesc d = descs[t.factor];
+  const TERM f{LoamDesc{d.points, d.target_points}};
+  const Pose Tl = load_pose(poses_lin + 16 * (size_t)t.factor);
+  const Pose Te = MODE == MODE_ERR ? load_pose(poses_eval + 16 * (size_t)t.factor) : Tl;
+  double acc[NREG];
+#pragma unroll
+  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
+  const int* __restrict__ corr = d.corr[set];
+  const int end = t.begin + t.count;
+  for (int i = t.begin + threadIdx.x; i < end; i += 256) {
+    if (corr[i] < 0) continue;
+    f.template accumulate<MODE>(i, corr + i, (size_t)d.n, Tl, Te, acc);
+  }
+  store_tile_sums_row<MODE>(acc, partials + (size_t)t.row * STRIDE);
+}
+
+// validate_correspondences over the LOAM tiles of a batch, into the set just searched; a tile of a member that did not enable it returns at once
+__global__ void __launch_bounds__(256) loam_batch_validate_kernel(const LoamBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles, const int set) {
+  const CorrTile t = tiles[blockIdx.x];
+  const LoamBatchDesc d = descs[t.factor];
+  if (!d.validate) return;
+  const int end = t.begin + t.count;
+  for (int i = t.begin + threadIdx.x; i < end; i += 256) loam_validate_point(d.target_points, d.corr[set] + i, (size_t)d.n, d.k);
+}
+
+// part p takes the pose of its member
+__global__ void corr_batch_part_poses_kernel(const int* __restrict__ part_member, int num_parts, const double* __restrict__ poses, double* __restrict__ part_poses) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < 16 * num_parts) part_poses[i] = poses[16 * (size_t)part_member[i >> 4] + (i & 15)];
+}
+
+// member f's result = its part results added in part order (edge, then plane), `width` doubles each; one workgroup per member, completion word f behind it
+__global__ void __launch_bounds__(128) corr_batch_combine_kernel(const int2* __restrict__ member_parts, const double* __restrict__ part_results, int width, double* __restrict__ out,
+                                                                 const DoneFlags done) {
+  const int2 m = member_parts[blockIdx.x];  // first part, number of parts (1 or 2)
+  const int k = threadIdx.x;
+  const bool mine = k < width;
+  if (mine) {
+    const double a = part_results[(size_t)m.x * width + k];
+    out[(size_t)blockIdx.x * width + k] = m.y == 2 ? a + part_results[(size_t)(m.x + 1) * width + k] : a;
+  }
+  signal_done(done, blockIdx.x, mine);
+}
+
 }  // namespace gp
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -73,14 +142,22 @@ __global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const CorrBatchDe
 // ---------------------------------------------------------------------------------------------------------------
 
 struct gp_corr_batch {
-  enum Kind { GICP = 0, ICP_POINT = 1, ICP_PLANE = 2 };
+  enum Kind { GICP = 0, ICP_POINT = 1, ICP_PLANE = 2, LOAM_EDGE = 3, LOAM_PLANE = 4, NUM_KINDS = 5 };
+  static constexpr int kRecordDoubles = (int)(sizeof(gp_linearized6) / sizeof(double));
   hipStream_t stream = nullptr;
-  int F = 0;
+  int F = 0;                    // members = records
+  int P = 0;                    // parts (>= F): what the tables below are indexed by
+  bool combine = false;         // P > F: part poses in front of a pass, part results added behind it
+  bool validate = false;        // a LOAM member enables the correspondence validation
   int num_tiles = 0;            // = rows of the partial sums
   long total_points = 0;
-  int kind_begin[3] = {0, 0, 0}, kind_count[3] = {0, 0, 0};  // the tile list is ordered by kind: one tile launch per kind present
-  gp::DeviceArray d_search, d_descs, d_tiles, d_rows;         // search descriptors | CorrBatchDesc[F] | CorrTile[num_tiles] | FactorDesc[F] (tile_begin / tile_count: the finalize's)
-  gp::DeviceArray d_corr[2];                                  // int[total_points] each: factor f's correspondences at its point offset
+  int kind_begin[NUM_KINDS] = {0, 0, 0, 0, 0}, kind_count[NUM_KINDS] = {0, 0, 0, 0, 0};  // the tile list is ordered by kind: one tile launch per kind present
+  int tiles_1nn = 0, tiles_knn = 0;                           // the tiles of the 1-NN kinds come first, those of the LOAM kinds behind them
+  gp::DeviceArray d_search, d_descs, d_tiles, d_rows;         // search descriptors | CorrBatchDesc[P] | CorrTile[num_tiles] | FactorDesc[P] (tile_begin / tile_count: the finalize's)
+  gp::DeviceArray d_loam_descs;                               // LoamBatchDesc[P] (the LOAM parts' entries)
+  gp::DeviceArray d_part_member, d_member_parts;              // int[P] | int2[F]
+  gp::DeviceArray d_part_poses[2], d_part_records, d_part_errors;  // combine: [P][16] lin | eval, gp_linearized6[P], double[P]
+  gp::DeviceArray d_corr[2];                                  // int each: part p's correspondences (K rows of n) at its offset
   gp::DeviceArray d_partials_lin, d_partials_err;             // [num_tiles][ACCG_STRIDE] | [num_tiles][ACC_STRIDE]
   bool set_valid[2] = {false, false};
   // the synchronous host-pose forms and the LM graph's error evaluation: pose staging, results and completion words in host-mapped pinned memory
@@ -101,23 +178,60 @@ struct gp_corr_batch {
       hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<false>>), dim3(kind_count[ICP_POINT]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_POINT], lin, eval, set, partials);
     if (kind_count[ICP_PLANE] > 0)
       hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<true>>), dim3(kind_count[ICP_PLANE]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_PLANE], lin, eval, set, partials);
+    const gp::LoamBatchDesc* ldescs = d_loam_descs.as<gp::LoamBatchDesc>();
+    if (kind_count[LOAM_EDGE] > 0)
+      hipLaunchKernelGGL((gp::loam_batch_tiles_kernel<MODE, gp::LoamEdgeTerm>), dim3(kind_count[LOAM_EDGE]), dim3(256), 0, stream, ldescs, tiles + kind_begin[LOAM_EDGE], lin, eval, set, partials);
+    if (kind_count[LOAM_PLANE] > 0)
+      hipLaunchKernelGGL((gp::loam_batch_tiles_kernel<MODE, gp::LoamPlaneTerm>), dim3(kind_count[LOAM_PLANE]), dim3(256), 0, stream, ldescs, tiles + kind_begin[LOAM_PLANE], lin, eval, set, partials);
+    GP_HIP(hipGetLastError());
+    return GP_OK;
+  }
+
+  // the members' poses [F][16] as the parts read them: the table itself when part p is member p, else gathered into d_part_poses[slot]
+  int part_poses(const double* poses_dev, int slot, const double** out) {
+    *out = poses_dev;
+    if (!combine) return GP_OK;
+    double* pp = d_part_poses[slot].as<double>();
+    hipLaunchKernelGGL(gp::corr_batch_part_poses_kernel, dim3((16 * P + 255) / 256), dim3(256), 0, stream, d_part_member.as<int>(), P, poses_dev, pp);
+    GP_HIP(hipGetLastError());
+    *out = pp;
+    return GP_OK;
+  }
+
+  int combine_parts(const double* part_results, int width, double* out, gp::DoneFlags done) {
+    hipLaunchKernelGGL(gp::corr_batch_combine_kernel, dim3(F), dim3(128), 0, stream, d_member_parts.as<int2>(), part_results, width, out, done);
     GP_HIP(hipGetLastError());
     return GP_OK;
   }
 
   int issue_linearize(const double* poses_dev, bool rigid, int set, gp_linearized6* out, gp::DoneFlags done) {
+    const double* pp = nullptr;
+    GP_TRY(part_poses(poses_dev, 0, &pp));
     if (num_tiles > 0) {
-      GP_TRY(gp::launch_nearest_correspondences_batch(d_search.ptr, d_tiles.as<gp::CorrTile>(), num_tiles, poses_dev, set, stream));
-      if (rigid) GP_TRY(launch_tiles<gp::MODE_LIN>(poses_dev, poses_dev, set, d_partials_lin.as<double>()));
-      else GP_TRY(launch_tiles<gp::MODE_LIN_GENERAL>(poses_dev, poses_dev, set, d_partials_lin.as<double>()));
+      const gp::CorrTile* tiles = d_tiles.as<gp::CorrTile>();
+      if (tiles_1nn > 0) GP_TRY(gp::launch_nearest_correspondences_batch(d_search.ptr, tiles, tiles_1nn, pp, set, stream));
+      if (tiles_knn > 0) GP_TRY(gp::launch_nearest_k_correspondences_batch(d_search.ptr, tiles + tiles_1nn, tiles_knn, pp, set, stream));
+      if (validate) {
+        hipLaunchKernelGGL(gp::loam_batch_validate_kernel, dim3(tiles_knn), dim3(256), 0, stream, d_loam_descs.as<gp::LoamBatchDesc>(), tiles + tiles_1nn, set);
+        GP_HIP(hipGetLastError());
+      }
+      if (rigid) GP_TRY(launch_tiles<gp::MODE_LIN>(pp, pp, set, d_partials_lin.as<double>()));
+      else GP_TRY(launch_tiles<gp::MODE_LIN_GENERAL>(pp, pp, set, d_partials_lin.as<double>()));
     }
     set_valid[set] = true;
-    return gp::launch_finalize_table(stream, d_rows.as<gp::FactorDesc>(), F, poses_dev, d_partials_lin.as<double>(), out, !rigid, done);
+    if (!combine) return gp::launch_finalize_table(stream, d_rows.as<gp::FactorDesc>(), P, pp, d_partials_lin.as<double>(), out, !rigid, done);
+    GP_TRY(gp::launch_finalize_table(stream, d_rows.as<gp::FactorDesc>(), P, pp, d_partials_lin.as<double>(), d_part_records.as<gp_linearized6>(), !rigid, {}));
+    return combine_parts(d_part_records.as<double>(), kRecordDoubles, reinterpret_cast<double*>(out), done);
   }
 
   int issue_error(int set, const double* lin, const double* eval, double* out, gp::DoneFlags done) {
-    if (num_tiles > 0) GP_TRY(launch_tiles<gp::MODE_ERR>(lin, eval, set, d_partials_err.as<double>()));
-    return gp::launch_finalize_error_table(stream, d_rows.as<gp::FactorDesc>(), F, d_partials_err.as<double>(), out, done);
+    const double *pl = nullptr, *pe = nullptr;
+    GP_TRY(part_poses(lin, 0, &pl));
+    GP_TRY(part_poses(eval, 1, &pe));
+    if (num_tiles > 0) GP_TRY(launch_tiles<gp::MODE_ERR>(pl, pe, set, d_partials_err.as<double>()));
+    if (!combine) return gp::launch_finalize_error_table(stream, d_rows.as<gp::FactorDesc>(), P, d_partials_err.as<double>(), out, done);
+    GP_TRY(gp::launch_finalize_error_table(stream, d_rows.as<gp::FactorDesc>(), P, d_partials_err.as<double>(), d_part_errors.as<double>(), {}));
+    return combine_parts(d_part_errors.as<double>(), 1, out, done);
   }
 
   // host poses [F][16] -> d_poses[k] (through the pinned staging block; in stream order in front of the kernels that read them)
@@ -150,83 +264,137 @@ int corr_batch_error_end(gp_corr_batch* b, double* out_host, long extra_spin_us)
 extern "C" {
 
 int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out) {
+  return gp_corr_batch_create_ex(gicp, num_gicp, icp, num_icp, nullptr, 0, stream, out);
+}
+
+int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
+                            gp_stream_t stream, gp_corr_batch_t** out) {
   if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null out");
   *out = nullptr;
-  if (num_gicp < 0 || num_icp < 0 || (num_gicp > 0 && !gicp) || (num_icp > 0 && !icp)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: bad arguments");
-  if (num_gicp + num_icp == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
-  const int F = num_gicp + num_icp;
-  std::vector<const gp_corr_factor_core*> cores((size_t)F);
-  std::vector<int> kinds((size_t)F);
+  if (num_gicp < 0 || num_icp < 0 || num_loam < 0 || (num_gicp > 0 && !gicp) || (num_icp > 0 && !icp) || (num_loam > 0 && !loam))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: bad arguments");
+  if (num_gicp + num_icp + num_loam == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
+  const int F = num_gicp + num_icp + num_loam;
+  // the parts in record order: a GICP / ICP member is one, a LOAM member its edge part and / or its plane part, in that order
+  struct Part {
+    const gp_corr_factor_core* core;
+    int kind, member, k;
+    const gp_loam_factor* loam;
+  };
+  std::vector<Part> parts;
+  std::vector<int2> member_parts((size_t)F);
   for (int i = 0; i < num_gicp; i++) {
     if (!gicp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null GICP factor");
-    cores[(size_t)i] = gicp[i], kinds[(size_t)i] = gp_corr_batch::GICP;
+    member_parts[(size_t)i] = make_int2((int)parts.size(), 1);
+    parts.push_back({gicp[i], gp_corr_batch::GICP, i, 1, nullptr});
   }
   for (int i = 0; i < num_icp; i++) {
     if (!icp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null ICP factor");
     // the keep-or-search decision of the update tolerances is host logic on a host pose: in a batch every linearise searches (the reference's default)
     if (icp[i]->tol_rot != 0.0 || icp[i]->tol_trans != 0.0)
       return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an ICP factor with non-zero correspondence-update tolerances cannot join a batch");
-    cores[(size_t)(num_gicp + i)] = icp[i], kinds[(size_t)(num_gicp + i)] = icp[i]->plane ? gp_corr_batch::ICP_PLANE : gp_corr_batch::ICP_POINT;
+    member_parts[(size_t)(num_gicp + i)] = make_int2((int)parts.size(), 1);
+    parts.push_back({icp[i], icp[i]->plane ? gp_corr_batch::ICP_PLANE : gp_corr_batch::ICP_POINT, num_gicp + i, 1, nullptr});
   }
-  for (const auto* c : cores)
-    if (c->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
+  bool validate = false;
+  for (int i = 0; i < num_loam; i++) {
+    const gp_loam_factor* l = loam[i];
+    if (!l) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null LOAM factor");
+    if (l->tol_rot != 0.0 || l->tol_trans != 0.0)
+      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: a LOAM factor with non-zero correspondence-update tolerances cannot join a batch");
+    const int m = num_gicp + num_icp + i;
+    member_parts[(size_t)m] = make_int2((int)parts.size(), (l->edge ? 1 : 0) + (l->plane ? 1 : 0));
+    if (l->edge) parts.push_back({l->edge.get(), gp_corr_batch::LOAM_EDGE, m, 2, l});
+    if (l->plane) parts.push_back({l->plane.get(), gp_corr_batch::LOAM_PLANE, m, 3, l});
+    validate = validate || l->validation;
+  }
+  for (const Part& p : parts)
+    if (p.core->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
+  const int P = (int)parts.size();
 
   auto b = std::make_unique<gp_corr_batch>();
   b->stream = (hipStream_t)stream;
   b->F = F;
-  // rows (= tiles) in record order, a factor's rows contiguous; the tile LIST ordered by kind
-  std::vector<gp::FactorDesc> rows((size_t)F);
-  std::vector<long> point_offset((size_t)F);
-  std::vector<gp::CorrTile> by_kind[3];
+  b->P = P;
+  b->combine = P != F;
+  b->validate = validate;
+  // rows (= tiles) in part order, a part's rows contiguous; the tile LIST ordered by kind
+  std::vector<gp::FactorDesc> rows((size_t)P);
+  std::vector<long> corr_offset((size_t)P);
+  std::vector<int> part_member((size_t)P);
+  std::vector<gp::CorrTile> by_kind[gp_corr_batch::NUM_KINDS];
+  long total_corr = 0;
   int row = 0;
-  for (int f = 0; f < F; f++) {
-    const int n = cores[(size_t)f]->n;
-    point_offset[(size_t)f] = b->total_points;
+  for (int p = 0; p < P; p++) {
+    const int n = parts[(size_t)p].core->n;
+    part_member[(size_t)p] = parts[(size_t)p].member;
+    corr_offset[(size_t)p] = total_corr;
+    total_corr += (long)parts[(size_t)p].k * n;
     b->total_points += n;
-    rows[(size_t)f] = gp::FactorDesc{};
-    rows[(size_t)f].n = n;
-    rows[(size_t)f].tile_begin = row;
-    for (int begin = 0; begin < n; begin += gp::kTilePoints) by_kind[kinds[(size_t)f]].push_back(gp::CorrTile{f, begin, std::min(gp::kTilePoints, n - begin), row++});
-    rows[(size_t)f].tile_count = row - rows[(size_t)f].tile_begin;
+    rows[(size_t)p] = gp::FactorDesc{};
+    rows[(size_t)p].n = n;
+    rows[(size_t)p].tile_begin = row;
+    for (int begin = 0; begin < n; begin += gp::kTilePoints) by_kind[parts[(size_t)p].kind].push_back(gp::CorrTile{p, begin, std::min(gp::kTilePoints, n - begin), row++});
+    rows[(size_t)p].tile_count = row - rows[(size_t)p].tile_begin;
   }
   b->num_tiles = row;
   std::vector<gp::CorrTile> tiles;
-  for (int k = 0; k < 3; k++) {
+  for (int k = 0; k < gp_corr_batch::NUM_KINDS; k++) {
     b->kind_begin[k] = (int)tiles.size();
     b->kind_count[k] = (int)by_kind[k].size();
     tiles.insert(tiles.end(), by_kind[k].begin(), by_kind[k].end());
   }
-  if (b->total_points > 0x7fffffffl) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: more than 2^31 - 1 source points in one batch");
+  b->tiles_1nn = b->kind_begin[gp_corr_batch::LOAM_EDGE];
+  b->tiles_knn = (int)tiles.size() - b->tiles_1nn;
+  if (b->tiles_knn == 0) b->validate = false;
+  if (total_corr > 0x7fffffffl) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: more than 2^31 - 1 correspondences in one batch");
 
-  for (int k = 0; k < 2; k++) GP_TRY(b->d_corr[k].alloc(sizeof(int) * (size_t)std::max(b->total_points, 1l)));
+  for (int k = 0; k < 2; k++) GP_TRY(b->d_corr[k].alloc(sizeof(int) * (size_t)std::max(total_corr, 1l)));
   GP_TRY(b->d_partials_lin.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(b->num_tiles, 1)));
   GP_TRY(b->d_partials_err.alloc(sizeof(double) * gp::ACC_STRIDE * (size_t)std::max(b->num_tiles, 1)));
-  std::vector<char> search(gp::corr_search_desc_bytes() * (size_t)F);
-  std::vector<gp::CorrBatchDesc> descs((size_t)F);
-  for (int f = 0; f < F; f++) {
-    const gp_corr_factor_core* c = cores[(size_t)f];
-    int* c0 = b->d_corr[0].as<int>() + point_offset[(size_t)f];
-    int* c1 = b->d_corr[1].as<int>() + point_offset[(size_t)f];
-    gp::fill_corr_search_desc(search.data(), f, c->grid, c->points, c->n, c->max_sq_dist, c0, c1);
-    gp::CorrBatchDesc& d = descs[(size_t)f];
+  std::vector<char> search(gp::corr_search_desc_bytes() * (size_t)P);
+  std::vector<gp::CorrBatchDesc> descs((size_t)P);
+  std::vector<gp::LoamBatchDesc> ldescs((size_t)P);
+  for (int p = 0; p < P; p++) {
+    const Part& part = parts[(size_t)p];
+    const gp_corr_factor_core* c = part.core;
+    int* c0 = b->d_corr[0].as<int>() + corr_offset[(size_t)p];
+    int* c1 = b->d_corr[1].as<int>() + corr_offset[(size_t)p];
+    gp::fill_corr_search_desc(search.data(), p, c->grid, c->points, c->n, c->max_sq_dist, c0, c1, part.k);
+    gp::CorrBatchDesc& d = descs[(size_t)p];
     d = gp::CorrBatchDesc{};
-    if (f < num_gicp) {
-      const gp::GicpTerm& t = gicp[f]->term;
+    ldescs[(size_t)p] = gp::LoamBatchDesc{};
+    if (part.kind == gp_corr_batch::GICP) {
+      const gp::GicpTerm& t = static_cast<const gp_gicp_factor*>(c)->term;
       d.points = t.points, d.covs = t.covs, d.target_points = t.target_points, d.target_covs = t.target_covs;
+    } else if (part.loam) {
+      const gp::LoamDesc& t = static_cast<const gp_loam_part*>(c)->desc;
+      ldescs[(size_t)p] = gp::LoamBatchDesc{t.points, t.target_points, {c0, c1}, c->n, part.k, part.loam->validation ? 1 : 0, 0};
     } else {
-      const gp::IcpDesc& t = icp[f - num_gicp]->desc;
+      const gp::IcpDesc& t = static_cast<const gp_icp_factor*>(c)->desc;
       d.points = t.points, d.target_points = t.target_points, d.target_normals = t.target_normals;
     }
     d.corr[0] = c0, d.corr[1] = c1;
   }
   GP_TRY(b->d_search.alloc(search.size()));
-  GP_TRY(b->d_descs.alloc(sizeof(gp::CorrBatchDesc) * (size_t)F));
+  GP_TRY(b->d_descs.alloc(sizeof(gp::CorrBatchDesc) * (size_t)P));
+  GP_TRY(b->d_loam_descs.alloc(sizeof(gp::LoamBatchDesc) * (size_t)P));
   GP_TRY(b->d_tiles.alloc(sizeof(gp::CorrTile) * std::max(tiles.size(), (size_t)1)));
-  GP_TRY(b->d_rows.alloc(sizeof(gp::FactorDesc) * (size_t)F));
+  GP_TRY(b->d_rows.alloc(sizeof(gp::FactorDesc) * (size_t)P));
+  GP_TRY(b->d_part_member.alloc(sizeof(int) * (size_t)P));
+  GP_TRY(b->d_member_parts.alloc(sizeof(int2) * (size_t)F));
   GP_HIP(hipMemcpy(b->d_search.ptr, search.data(), search.size(), hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_descs.ptr, descs.data(), sizeof(gp::CorrBatchDesc) * (size_t)F, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_descs.ptr, descs.data(), sizeof(gp::CorrBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_loam_descs.ptr, ldescs.data(), sizeof(gp::LoamBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
   if (!tiles.empty()) GP_HIP(hipMemcpy(b->d_tiles.ptr, tiles.data(), sizeof(gp::CorrTile) * tiles.size(), hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_rows.ptr, rows.data(), sizeof(gp::FactorDesc) * (size_t)F, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_rows.ptr, rows.data(), sizeof(gp::FactorDesc) * (size_t)P, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_part_member.ptr, part_member.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_member_parts.ptr, member_parts.data(), sizeof(int2) * (size_t)F, hipMemcpyHostToDevice));
+  if (b->combine) {
+    for (int k = 0; k < 2; k++) GP_TRY(b->d_part_poses[k].alloc(sizeof(double) * 16 * (size_t)P));
+    GP_TRY(b->d_part_records.alloc(sizeof(gp_linearized6) * (size_t)P));
+    GP_TRY(b->d_part_errors.alloc(sizeof(double) * (size_t)P));
+  }
 
   const size_t pb = sizeof(double) * 16 * (size_t)F;
   for (int k = 0; k < 2; k++) GP_TRY(b->d_poses[k].alloc(pb));

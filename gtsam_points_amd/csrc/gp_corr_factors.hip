@@ -1,8 +1,10 @@
-// gp_corr_factors.hip -- the matching-cost factors on 1-NN correspondences: GICP and ICP (point-to-point and point-to-plane).
+// gp_corr_factors.hip -- the matching-cost factors on nearest-neighbour correspondences: GICP and ICP (point-to-point and point-to-plane) on the nearest target point,
+// the LOAM point-to-edge and point-to-plane factors on the 2 and 3 nearest.
 //
 // Replaces (reference, CPU only -- there is no GPU counterpart upstream):
 //   factors/impl/integrated_gicp_factor_impl.hpp:132-296              GICP correspondences+H/b  -> gp_gicp_factor_*
 //   factors/impl/integrated_icp_factor_impl.hpp:128-157,180-248       ICP correspondences+H/b   -> gp_icp_factor_*
+//   factors/impl/integrated_loam_factor_impl.hpp:80-194,235-365,444-529   LOAM edge / plane / combined -> gp_loam_factor_*
 //
 // Nothing of the search lives here: gp::launch_nearest_correspondences (gp_knn.hip) writes, for the source points transformed by the linearisation pose, the index
 // of the nearest target point within the cut-off into corr[]; a tile kernel then sums the factor's terms over those correspondences into the partial-row layout of
@@ -28,9 +30,18 @@ __global__ void __launch_bounds__(256) corr_tile_kernel(TERM f, const CorrPoses 
   for (int i = begin + threadIdx.x; i < end; i += 256) {
     const int c = corr[i];
     if (c < 0) continue;
-    f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
+    if constexpr (TERM::kNeighbours == 1)
+      f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
+    else  // (the LOAM terms: corr is int[K][n], slot 0 the anchor)
+      f.template accumulate<MODE>(i, corr + i, (size_t)n, Tl, Te, acc);
   }
   store_tile_sums<MODE>(acc, partials);
+}
+
+// validate_correspondences of the LOAM factor over the stored correspondences of one part (gp_corr_factors.hpp: loam_validate_point), one point per lane
+__global__ void __launch_bounds__(256) loam_validate_kernel(const float* __restrict__ target_points, int* __restrict__ corr, int n, int K) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) loam_validate_point(target_points, corr + i, (size_t)n, K);
 }
 
 }  // namespace gp
@@ -74,11 +85,22 @@ int gp_icp_factor::run_pass(const double* pose_lin, const double* pose_eval, voi
   return gp_corr_factor_core::run_pass(gp::IcpTerm<false>{desc}, pose_lin, pose_eval, out_host);
 }
 
-// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137) on two column-major 4x4 poses: diff = delta^-1 * last (the
-// isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
-static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta) {
-  if (!f->corr_valid || !(f->tol_trans > 0.0 || f->tol_rot > 0.0)) return false;
-  const double* last = f->corr_pose;
+int gp_loam_part::run_pass(const double* pose_lin, const double* pose_eval, void* out_host) {
+  if (k == 2) return gp_corr_factor_core::run_pass(gp::LoamEdgeTerm{desc}, pose_lin, pose_eval, out_host);
+  return gp_corr_factor_core::run_pass(gp::LoamPlaneTerm{desc}, pose_lin, pose_eval, out_host);
+}
+
+int gp_loam_part::validate() {
+  if (n <= 0) return GP_OK;
+  hipLaunchKernelGGL(gp::loam_validate_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, desc.target_points, corr.as<int>(), n, k);
+  GP_HIP(hipGetLastError());
+  return GP_OK;
+}
+
+// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137, integrated_loam_factor_impl.hpp:81-88, :236-243) on two column-major 4x4 poses:
+// diff = delta^-1 * last (the isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
+static bool keep_correspondences(bool corr_valid, const double* last, double tol_rot, double tol_trans, const double* delta) {
+  if (!corr_valid || !(tol_trans > 0.0 || tol_rot > 0.0)) return false;
   double D[3][3], t[3];
   for (int r = 0; r < 3; r++) {
     for (int c = 0; c < 3; c++) D[r][c] = delta[4 * r] * last[4 * c] + delta[4 * r + 1] * last[4 * c + 1] + delta[4 * r + 2] * last[4 * c + 2];
@@ -88,7 +110,26 @@ static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta
   const double sx = 0.5 * (D[2][1] - D[1][2]), sy = 0.5 * (D[0][2] - D[2][0]), sz = 0.5 * (D[1][0] - D[0][1]);
   const double diff_rot = std::atan2(std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0));
   const double diff_trans = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  return diff_rot < f->tol_rot && diff_trans < f->tol_trans;
+  return diff_rot < tol_rot && diff_trans < tol_trans;
+}
+static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta) { return keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, delta); }
+
+// ---- LOAM factor: what the entry points share ----
+
+// the searches of both parts at `pose`, with the validation behind them when it is enabled
+static int loam_search(gp_loam_factor* f, const double* pose) {
+  for (gp_loam_part* p : {f->edge.get(), f->plane.get()})
+    if (p && p->num_tiles > 0) GP_TRY(p->search_k(p->k, pose));
+  memcpy(f->corr_pose, pose, sizeof(double) * 16);
+  f->corr_valid = true;
+  return GP_OK;
+}
+
+static int loam_validate(gp_loam_factor* f) {
+  if (!f->validation) return GP_OK;
+  for (gp_loam_part* p : {f->edge.get(), f->plane.get()})
+    if (p) GP_TRY(p->validate());
+  return GP_OK;
 }
 
 extern "C" {
@@ -186,6 +227,110 @@ int gp_icp_factor_compute_error(gp_icp_factor_t* f, const double pose_lin[16], c
     f->lin_valid = false;
   }
   return f->run_pass(pose_lin, pose_eval, out_host);
+}
+
+// ---- LOAM factor ----------------------------------------------------------------------------------------------------
+
+static int loam_make_part(int k, const gp_point_grid_t* grid, const float* target_dev, const float* source_dev, int n, hipStream_t stream, std::unique_ptr<gp_loam_part>* out) {
+  auto p = std::make_unique<gp_loam_part>();
+  p->k = k;
+  p->desc = {source_dev, target_dev};
+  GP_TRY(p->prepare(grid, source_dev, n, 1.0, stream));  // max_correspondence_distance_sq(1.0), :27, :205
+  GP_TRY(p->corr.alloc(sizeof(int) * (size_t)k * (size_t)std::max(n, 1)));
+  *out = std::move(p);
+  return GP_OK;
+}
+
+int gp_loam_factor_create(const gp_point_grid_t* edge_grid, const float* target_edges_dev, int num_target_edges, const float* source_edges_dev, int num_source_edges,
+                          const gp_point_grid_t* plane_grid, const float* target_planes_dev, int num_target_planes, const float* source_planes_dev, int num_source_planes,
+                          gp_stream_t stream, gp_loam_factor_t** out) {
+  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_create: null out");
+  *out = nullptr;
+  const bool no_edge = !edge_grid && num_target_edges == 0 && num_source_edges == 0, no_plane = !plane_grid && num_target_planes == 0 && num_source_planes == 0;
+  if (no_edge && no_plane) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_create: neither an edge part nor a plane part");
+  if (!no_edge && (!edge_grid || !target_edges_dev || !source_edges_dev || num_target_edges < 0 || num_source_edges < 0))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_create: the edge part needs its grid, target points and source points");
+  if (!no_plane && (!plane_grid || !target_planes_dev || !source_planes_dev || num_target_planes < 0 || num_source_planes < 0))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_create: the plane part needs its grid, target points and source points");
+  auto f = std::make_unique<gp_loam_factor>();
+  f->stream = (hipStream_t)stream;
+  if (!no_edge) GP_TRY(loam_make_part(2, edge_grid, target_edges_dev, source_edges_dev, num_source_edges, f->stream, &f->edge));
+  if (!no_plane) GP_TRY(loam_make_part(3, plane_grid, target_planes_dev, source_planes_dev, num_source_planes, f->stream, &f->plane));
+  *out = f.release();
+  return GP_OK;
+}
+
+int gp_loam_factor_destroy(gp_loam_factor_t* f) {
+  if (!f) return GP_OK;
+  (void)hipStreamSynchronize(f->stream);
+  delete f;  // (the grids are the caller's)
+  return GP_OK;
+}
+
+int gp_loam_factor_set_max_correspondence_distance(gp_loam_factor_t* f, double dist_edge, double dist_plane) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_max_correspondence_distance: null");
+  if (!(dist_edge > 0.0) || !(dist_plane > 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_max_correspondence_distance: distances must be positive");
+  if (f->edge) f->edge->max_sq_dist = dist_edge * dist_edge;
+  if (f->plane) f->plane->max_sq_dist = dist_plane * dist_plane;
+  return GP_OK;
+}
+
+int gp_loam_factor_set_enable_correspondence_validation(gp_loam_factor_t* f, int on) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_enable_correspondence_validation: null");
+  f->validation = on != 0;
+  return GP_OK;
+}
+
+int gp_loam_factor_set_correspondence_update_tolerance(gp_loam_factor_t* f, double angle, double trans) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_correspondence_update_tolerance: null");
+  f->tol_rot = angle;
+  f->tol_trans = trans;
+  return GP_OK;
+}
+
+int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, int* planes) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_num_correspondences: null");
+  if (edges) *edges = f->num_edges;
+  if (planes) *planes = f->num_planes;
+  return GP_OK;
+}
+
+// the record of a combined factor: the edge part's finalised record plus the plane part's, added in that order in f64 as IntegratedLOAMFactor_::evaluate does
+// (:461-472); a factor of one part hands that part's record on
+static void loam_add(const double* edge, const double* plane, double* out, size_t count) {
+  for (size_t k = 0; k < count; k++) out[k] = edge && plane ? edge[k] + plane[k] : (edge ? edge[k] : plane[k]);
+}
+
+int gp_loam_factor_linearize(gp_loam_factor_t* f, const double pose[16], gp_linearized6* out_host) {
+  if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_linearize: null");
+  if (!keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, pose)) GP_TRY(loam_search(f, pose));
+  GP_TRY(loam_validate(f));  // (also behind kept correspondences, as update_correspondences :444-449 does: it is idempotent)
+  memcpy(f->lin_pose, pose, sizeof(double) * 16);
+  f->lin_valid = true;
+  gp_linearized6 e{}, p{};
+  if (f->edge) GP_TRY(f->edge->run_pass(pose, nullptr, &e));
+  if (f->plane) GP_TRY(f->plane->run_pass(pose, nullptr, &p));
+  static_assert(sizeof(gp_linearized6) % sizeof(double) == 0, "a record is doubles only");
+  loam_add(f->edge ? reinterpret_cast<const double*>(&e) : nullptr, f->plane ? reinterpret_cast<const double*>(&p) : nullptr, reinterpret_cast<double*>(out_host),
+           sizeof(gp_linearized6) / sizeof(double));
+  f->num_edges = f->edge ? (int)e.num_inliers : 0;
+  f->num_planes = f->plane ? (int)p.num_inliers : 0;
+  return GP_OK;
+}
+
+int gp_loam_factor_compute_error(gp_loam_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
+  if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_compute_error: null");
+  const bool stored = f->corr_valid && ((f->lin_valid && memcmp(f->lin_pose, pose_lin, sizeof(double) * 16) == 0) || memcmp(f->corr_pose, pose_lin, sizeof(double) * 16) == 0);
+  if (!stored) {
+    GP_TRY(loam_search(f, pose_lin));
+    GP_TRY(loam_validate(f));
+    f->lin_valid = false;
+  }
+  double e = 0.0, p = 0.0;
+  if (f->edge) GP_TRY(f->edge->run_pass(pose_lin, pose_eval, &e));
+  if (f->plane) GP_TRY(f->plane->run_pass(pose_lin, pose_eval, &p));
+  loam_add(f->edge ? &e : nullptr, f->plane ? &p : nullptr, out_host, 1);
+  return GP_OK;
 }
 
 }  // extern "C"

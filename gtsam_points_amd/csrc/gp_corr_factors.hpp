@@ -24,6 +24,7 @@ struct GicpTerm {
   const float* target_points;
   const float* target_covs;
   static constexpr int kErrRegs = 32;  // accumulate_terms_mu<MODE_ERR> is handed the 32-register array of the linearise
+  static constexpr int kNeighbours = 1;
 
   template <int MODE>
   __device__ __forceinline__ void accumulate(int i, size_t j, const Pose& Tl, const Pose& Te, double* acc) const {
@@ -69,6 +70,7 @@ template <bool PLANE>
 struct IcpTerm {
   IcpDesc f;
   static constexpr int kErrRegs = 2;
+  static constexpr int kNeighbours = 1;
 
   template <int MODE>
   __device__ __forceinline__ void accumulate(int i, size_t j, const Pose& Tl, const Pose& Te, double* acc) const {
@@ -123,6 +125,82 @@ struct IcpTerm {
     }
   }
 };
+
+// ---- the LOAM terms (integrated_loam_factor_impl.hpp) on the K = 2 / 3 nearest target points of a source point, stored int[K][n]: a term is handed corr + i and the
+// stride n, slot 0 (>= 0, checked by the tile kernel) being the anchor x_j.  Both are the correspondence algebra above with another M, so they go through
+// accumulate_sums in every mode: error = d^T M d, H = sum J^T M J, b = sum J^T M d with d = x_j - q, q = T p, J_t = [-[q]x, I], J_s = [R [p]x, -R].
+// M is formed in f64 from the f32 target points.  Degenerate neighbours (x_j = x_l; a collinear triple) are not guarded, as in the reference: the division yields
+// non-finite values that flow into the sums.
+struct LoamDesc {
+  const float* points;         // [n][3] source
+  const float* target_points;  // [num_target][3]
+};
+
+// Point-to-edge (:300-365): v = x_j - x_l, c = 1 / |v|, r = c (q - x_j) x (q - x_l) = A d with A = c [v]x (J_e = [v]x, :350-353), so M = A^T A = c^2 [v]x^T [v]x
+// = c^2 (|v|^2 I - v v^T), a full symmetric matrix.
+struct LoamEdgeTerm {
+  LoamDesc f;
+  static constexpr int kErrRegs = 2;
+  static constexpr int kNeighbours = 2;
+
+  template <int MODE>
+  __device__ __forceinline__ void accumulate(int i, const int* __restrict__ c, size_t stride, const Pose& Tl, const Pose& Te, double* acc) const {
+    const size_t j = (size_t)c[0], l = (size_t)c[stride];
+    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+    const double jx = (double)f.target_points[3 * j], jy = (double)f.target_points[3 * j + 1], jz = (double)f.target_points[3 * j + 2];
+    const double vx = jx - (double)f.target_points[3 * l], vy = jy - (double)f.target_points[3 * l + 1], vz = jz - (double)f.target_points[3 * l + 2];
+    const double ci = 1.0 / sqrt(vx * vx + vy * vy + vz * vz);
+    const double c2 = ci * ci;
+    const double m[6] = {c2 * (vy * vy + vz * vz), -c2 * (vx * vy), -c2 * (vx * vz), c2 * (vx * vx + vz * vz), -c2 * (vy * vz), c2 * (vx * vx + vy * vy)};
+    const double qx = Te.r00 * px + Te.r01 * py + Te.r02 * pz + Te.tx;
+    const double qy = Te.r10 * px + Te.r11 * py + Te.r12 * pz + Te.ty;
+    const double qz = Te.r20 * px + Te.r21 * py + Te.r22 * pz + Te.tz;
+    accumulate_sums<MODE>(Tl, m, px, py, pz, qx, qy, qz, jx - qx, jy - qy, jz - qz, acc);
+  }
+};
+
+// Point-to-plane (:127-194): n = normalize((x_j - x_l) x (x_j - x_m)), r = n o (x_j - q) element-wise: the point-to-plane ICP term with the normal formed from
+// the three neighbours instead of read from the cloud, M = diag(n o n).
+struct LoamPlaneTerm {
+  LoamDesc f;
+  static constexpr int kErrRegs = 2;
+  static constexpr int kNeighbours = 3;
+
+  template <int MODE>
+  __device__ __forceinline__ void accumulate(int i, const int* __restrict__ c, size_t stride, const Pose& Tl, const Pose& Te, double* acc) const {
+    const size_t j = (size_t)c[0], l = (size_t)c[stride], mm = (size_t)c[2 * stride];
+    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+    const double jx = (double)f.target_points[3 * j], jy = (double)f.target_points[3 * j + 1], jz = (double)f.target_points[3 * j + 2];
+    const double ax = jx - (double)f.target_points[3 * l], ay = jy - (double)f.target_points[3 * l + 1], az = jz - (double)f.target_points[3 * l + 2];
+    const double bx = jx - (double)f.target_points[3 * mm], by = jy - (double)f.target_points[3 * mm + 1], bz = jz - (double)f.target_points[3 * mm + 2];
+    double nx = ay * bz - az * by, ny = az * bx - ax * bz, nz = ax * by - ay * bx;
+    const double norm = sqrt(nx * nx + ny * ny + nz * nz);
+    nx /= norm, ny /= norm, nz /= norm;
+    const double m[6] = {nx * nx, 0.0, 0.0, ny * ny, 0.0, nz * nz};
+    const double qx = Te.r00 * px + Te.r01 * py + Te.r02 * pz + Te.tx;
+    const double qy = Te.r10 * px + Te.r11 * py + Te.r12 * pz + Te.ty;
+    const double qz = Te.r20 * px + Te.r21 * py + Te.r22 * pz + Te.tz;
+    accumulate_sums<MODE>(Tl, m, px, py, pz, qx, qy, qz, jx - qx, jy - qy, jz - qz, acc);
+  }
+};
+
+// IntegratedLOAMFactor_::validate_correspondences (:487-529) on the stored correspondences of one source point (c = corr + i, int[K][n]): with
+// theta(p) = atan2(p.z, hypot(p.x, p.y)) in f64, an edge pair is rejected (every slot -1) when |theta_j - theta_l| < 0.1 pi / 180, a plane triple when that holds
+// and |theta_j - theta_m| < 0.1 * pi * 180.  The second bound is the reference's expression AS WRITTEN (about 56.5 rad: it always holds); parity is the target.
+// Idempotent: a rejected point is skipped.
+__device__ __forceinline__ void loam_validate_point(const float* __restrict__ target_points, int* __restrict__ c, size_t stride, int K) {
+  const int j = c[0];
+  if (j < 0) return;
+  auto theta = [&](int t) {
+    const double x = (double)target_points[3 * (size_t)t], y = (double)target_points[3 * (size_t)t + 1], z = (double)target_points[3 * (size_t)t + 2];
+    return atan2(z, hypot(x, y));
+  };
+  const double tj = theta(j);
+  bool reject = fabs(tj - theta(c[stride])) < 0.1 * M_PI / 180.0;
+  if (K == 3) reject = reject && fabs(tj - theta(c[2 * stride])) < 0.1 * M_PI * 180.0;
+  if (reject)
+    for (int k = 0; k < K; k++) c[(size_t)k * stride] = -1;
+}
 
 // the lanes meet in the butterfly / shuffle tree and the four waves in wave order: a fixed order, two passes over the same correspondences are bit-identical
 // (row: where the workgroup's sums go -- the single-factor kernels' row is their blockIdx.x, a batch's tile carries its own)
@@ -208,6 +286,9 @@ struct gp_corr_factor_core {
     return GP_OK;
   }
 
+  // the correspondence pass of the LOAM parts at pose_lin (n > 0): the k nearest into corr (int[k][n], allocated by the part); the pose is kept by the factor
+  int search_k(int k, const double* pose_lin) { return gp::launch_nearest_k_correspondences(grid, points, n, k, pose_lin, max_sq_dist, corr.as<int>(), stream); }
+
   // One synchronous pass over the stored correspondences (gp_corr_factors.hip, which alone instantiates it).
   template <class TERM>
   int run_pass(const TERM& term, const double* pose_lin, const double* pose_eval, void* out_host);
@@ -229,4 +310,24 @@ struct gp_icp_factor : gp_corr_factor_core {  // (the grid is BORROWED: the refe
   double tol_rot = 0.0, tol_trans = 0.0;  // correspondence_update_tolerance_rot / _trans (:32-33)
   int num_correspondences = 0;
   int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_corr_factors.hip)
+};
+
+// IntegratedPointToEdgeFactor_ (k = 2) / IntegratedPointToPlaneFactor_ (k = 3) as one part of a gp_loam_factor: the core with corr as int[k][n]
+struct gp_loam_part : gp_corr_factor_core {
+  int k = 0;
+  gp::LoamDesc desc{};
+  int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_corr_factors.hip)
+  int validate();                                                                 // (gp_corr_factors.hip) the validation kernel over corr, asynchronous
+};
+
+// IntegratedLOAMFactor_: an edge part and a plane part (either may be absent: the two single factors), both grids BORROWED.  What the two parts decide together --
+// the pose of the stored correspondences, the update tolerances, the validation -- is kept here.
+struct gp_loam_factor {
+  std::unique_ptr<gp_loam_part> edge, plane;
+  hipStream_t stream = nullptr;
+  bool validation = false;  // enable_correspondence_validation (off by default, :385)
+  double tol_rot = 0.0, tol_trans = 0.0;
+  double corr_pose[16] = {0}, lin_pose[16] = {0};
+  bool corr_valid = false, lin_valid = false;
+  int num_edges = 0, num_planes = 0;  // inliers of the last linearise, per part
 };

@@ -414,6 +414,9 @@ namespace gp {
 // gp_knn.hip, for the factors of gp_corr_factors.hip: corr[i] = index of the point of `grid` nearest to pose_lin * points[i] (column-major 4x4, f64 on the f32
 // inputs) with squared distance < max_sq_dist, or -1; n > 0.  Asynchronous on `stream`.
 int launch_nearest_correspondences(const gp_point_grid* grid, const float* points, int n, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream);
+// ... and the k = 2 or 3 nearest, for the LOAM factors: corr is int[k][n], corr[j * n + i] the j-th nearest of point i in ascending order of distance, every slot -1
+// when fewer than k lie within the cut-off
+int launch_nearest_k_correspondences(const gp_point_grid* grid, const float* points, int n, int k, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream);
 
 // ... and the same search for a BATCH of factors in one launch (gp_corr_batch.hip): what the single launch carries in its kernel arguments -- the search structure,
 // the cloud, the cut-off, the pose -- is read from tables in device memory instead.  A tile is up to 1024 consecutive source points of ONE factor (tiles never
@@ -426,9 +429,12 @@ struct CorrTile {
 };
 size_t corr_search_desc_bytes();  // one entry of the search's descriptor table (private to gp_knn.hip)
 // entry `index` of a HOST copy of that table: factor `index` searches `grid` for pose * points[i], i < n, and writes corr[set][i]
-void fill_corr_search_desc(void* table_host, int index, const gp_point_grid* grid, const float* points, int n, double max_sq_dist, int* corr0, int* corr1);
+// (k: neighbours kept per point, 1 for the 1-NN launch below; 2 or 3 for launch_nearest_k_correspondences_batch, whose sets are int[k][n])
+void fill_corr_search_desc(void* table_host, int index, const gp_point_grid* grid, const float* points, int n, double max_sq_dist, int* corr0, int* corr1, int k = 1);
 // poses_dev: [F][16] column-major; writes corr[set] of every factor that owns a tile.  Asynchronous on `stream`; num_tiles > 0.
 int launch_nearest_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream);
+// the same over tiles of table entries with k = 2 or 3
+int launch_nearest_k_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream);
 }  // namespace gp
 
 // the correspondence-factor batch as the LM graph drives it (gp_corr_batch.hip; gp_lm.hip): the error evaluation in two halves, like gp_vgicp_batch_issue_compute_error_dev_begin / _end

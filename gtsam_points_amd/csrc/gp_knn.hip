@@ -1950,6 +1950,7 @@ struct NearestBatchDesc {
   SearchView grid;
   int* corr[2];  // the two correspondence sets
   int n;
+  int k;  // neighbours kept per source point: 1 (GICP, ICP: nearest_correspond_batch_kernel) or 2 / 3 (LOAM edge / plane: nearest_k_correspond_batch_kernel)
   double max_sq_dist;
 };
 
@@ -1969,6 +1970,47 @@ __global__ void __launch_bounds__(256) nearest_correspond_batch_kernel(const Nea
   top.init(1, f.max_sq_dist);
   knn_query_any<1>(f.grid, lx, ly, lz, 1, top);
   f.corr[set][i] = top.found ? top.idx[0] : -1;
+}
+
+// update_correspondences of the LOAM factors (integrated_loam_factor_impl.hpp:80-124 plane, K = 3; :235-279 edge, K = 2): the K nearest target points of T p_i with
+// squared distance < max (the strict '<' of TopK::push) in ASCENDING order of distance -- index 0 is the anchor x_j of both residuals --, or -1 in every slot when
+// fewer than K lie within the cut-off.  Stored as int[K][n] (corr[k * n + i]): lane i of a wave writes consecutive words of each of the K rows.  The list is FULL
+// (k == KMAX): straight-line insertion, an entry is held iff its index is valid.  One query per lane and nothing else in the kernel, as above.
+template <int K>
+__device__ __forceinline__ void nearest_k_store(const SearchView& grid, const float* __restrict__ points, const Pose& Tl, double max_sq_dist, int i, int n,
+                                                int* __restrict__ corr) {
+  const double px = (double)points[3 * (size_t)i], py = (double)points[3 * (size_t)i + 1], pz = (double)points[3 * (size_t)i + 2];
+  const double lx = Tl.r00 * px + Tl.r01 * py + Tl.r02 * pz + Tl.tx;
+  const double ly = Tl.r10 * px + Tl.r11 * py + Tl.r12 * pz + Tl.ty;
+  const double lz = Tl.r20 * px + Tl.r21 * py + Tl.r22 * pz + Tl.tz;
+  TopK<K, true> top;
+  top.init(K, max_sq_dist);
+  knn_query_any<K, true>(grid, lx, ly, lz, K, top);
+  const bool all = top.idx[K - 1] >= 0;  // (the list is sorted: the last slot is filled last)
+#pragma unroll
+  for (int k = 0; k < K; k++) corr[(size_t)k * (size_t)n + (size_t)i] = all ? top.idx[k] : -1;
+}
+
+template <int K>
+__global__ void __launch_bounds__(256) nearest_k_correspond_kernel(NearestDesc f, int* __restrict__ corr) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= f.n) return;
+  nearest_k_store<K>(f.grid, f.points, load_pose(f.pose), f.max_sq_dist, i, f.n, corr);
+}
+
+// ... and for the K > 1 members of a batch, in ONE launch over their tiles: search structure, cloud, cut-off and K from the descriptor table, the pose from the pose
+// table, into the set it is given, as nearest_correspond_batch_kernel does for K = 1.  K is the same for the whole workgroup (a tile belongs to one factor).
+__global__ void __launch_bounds__(256) nearest_k_correspond_batch_kernel(const NearestBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles,
+                                                                         const double* __restrict__ poses, const int set) {
+  const CorrTile t = tiles[blockIdx.x >> 2];
+  const int k = (int)(blockIdx.x & 3) * 256 + (int)threadIdx.x;
+  if (k >= t.count) return;
+  const NearestBatchDesc& f = descs[t.factor];
+  const Pose Tl = load_pose(poses + 16 * (size_t)t.factor);
+  if (f.k == 2)
+    nearest_k_store<2>(f.grid, f.points, Tl, f.max_sq_dist, t.begin + k, f.n, f.corr[set]);
+  else
+    nearest_k_store<3>(f.grid, f.points, Tl, f.max_sq_dist, t.begin + k, f.n, f.corr[set]);
 }
 
 }  // namespace gp
@@ -2068,20 +2110,43 @@ int launch_nearest_correspondences(const gp_point_grid* grid, const float* point
   return GP_OK;
 }
 
+int launch_nearest_k_correspondences(const gp_point_grid* grid, const float* points, int n, int k, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream) {
+  if (k != 2 && k != 3) return fail(GP_ERROR_INVALID_ARGUMENT, "launch_nearest_k_correspondences: k must be 2 or 3");
+  NearestDesc f;
+  f.points = points;
+  f.grid = grid->view();
+  f.n = n;
+  f.max_sq_dist = max_sq_dist;
+  memcpy(f.pose, pose_lin, sizeof(double) * 16);
+  if (k == 2)
+    hipLaunchKernelGGL(nearest_k_correspond_kernel<2>, dim3((n + 255) / 256), dim3(256), 0, stream, f, corr);
+  else
+    hipLaunchKernelGGL(nearest_k_correspond_kernel<3>, dim3((n + 255) / 256), dim3(256), 0, stream, f, corr);
+  GP_HIP(hipGetLastError());
+  return GP_OK;
+}
+
 size_t corr_search_desc_bytes() { return sizeof(NearestBatchDesc); }
 
-void fill_corr_search_desc(void* table_host, int index, const gp_point_grid* grid, const float* points, int n, double max_sq_dist, int* corr0, int* corr1) {
+void fill_corr_search_desc(void* table_host, int index, const gp_point_grid* grid, const float* points, int n, double max_sq_dist, int* corr0, int* corr1, int k) {
   NearestBatchDesc d{};
   d.points = points;
   d.grid = grid->view();
   d.corr[0] = corr0, d.corr[1] = corr1;
   d.n = n;
+  d.k = k;
   d.max_sq_dist = max_sq_dist;
   memcpy(static_cast<char*>(table_host) + sizeof(NearestBatchDesc) * (size_t)index, &d, sizeof(d));
 }
 
 int launch_nearest_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream) {
   hipLaunchKernelGGL(nearest_correspond_batch_kernel, dim3(4 * (unsigned)num_tiles), dim3(256), 0, stream, static_cast<const NearestBatchDesc*>(table_dev), tiles_dev, poses_dev, set);
+  GP_HIP(hipGetLastError());
+  return GP_OK;
+}
+
+int launch_nearest_k_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream) {
+  hipLaunchKernelGGL(nearest_k_correspond_batch_kernel, dim3(4 * (unsigned)num_tiles), dim3(256), 0, stream, static_cast<const NearestBatchDesc*>(table_dev), tiles_dev, poses_dev, set);
   GP_HIP(hipGetLastError());
   return GP_OK;
 }

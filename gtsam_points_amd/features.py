@@ -5,7 +5,9 @@
   estimate_normals_gpu      <- features/normal_estimation.hpp:estimate_normals(points, k=10); estimate_normals_covariances_gpu: both from one search
   IntegratedGICPFactorGPU   <- factors/integrated_gicp_factor.hpp (CPU-only upstream), same calc_delta / HessianFactor protocol
   IntegratedICPFactorGPU    <- factors/integrated_icp_factor.hpp (point-to-point / point-to-plane; CPU-only upstream), on a shared KdTreeGPU
-  CorrespondenceFactorBatchGPU  any number of the two factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
+  IntegratedPointToEdgeFactorGPU / IntegratedPointToPlaneFactorGPU / IntegratedLOAMFactorGPU
+                            <- factors/integrated_loam_factor.hpp (CPU-only upstream), on the 2 / 3 nearest points of shared KdTreeGPUs
+  CorrespondenceFactorBatchGPU  any number of the factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
 """
 import ctypes as C
 
@@ -276,6 +278,125 @@ def IntegratedPointToPlaneICPFactorGPU(target_key, source_key, target, source, t
                                   max_correspondence_distance=max_correspondence_distance, stream=stream, _fixed_target_pose=_fixed_target_pose)
 
 
+class IntegratedLOAMFactorGPU:
+    """LOAM matching-cost factor on the GPU (IntegratedLOAMFactor_, impl/integrated_loam_factor_impl.hpp): a point-to-edge part on the 2 nearest edge points and a
+    point-to-plane part on the 3 nearest plane points within max_correspondence_distance (default 1 m each), their records added edge first.
+    target_edges_tree / target_planes_tree: KdTreeGPUs over the target clouds that many factors may share (held by reference); None builds one and holds it."""
+
+    _LOAM = "error: {} frame doesn't have required attributes for loam"
+    _EDGE = "error: target or source points has not been allocated!!"
+
+    def __init__(self, target_key, source_key, target_edges, target_planes, source_edges, source_planes, target_edges_tree=None, target_planes_tree=None,
+                 max_correspondence_distance=1.0, stream=None, _fixed_target_pose=None):
+        self._lib = _capi.load()
+        self.is_binary = _fixed_target_pose is None
+        self._keys = [target_key, source_key] if self.is_binary else [source_key]
+        self.fixed_target_pose = np.eye(4) if self.is_binary else np.asarray(_fixed_target_pose, dtype=np.float64)
+        # the reference constructs the edge factor first (:387-390); each aborts with its own text
+        if target_edges is not None and (target_edges.points_gpu is None or source_edges.points_gpu is None):
+            raise _capi.GPError(self._EDGE)
+        if target_planes is not None:
+            if target_planes.points_gpu is None:
+                raise _capi.GPError(self._LOAM.format("target"))
+            if source_planes.points_gpu is None:
+                raise _capi.GPError(self._LOAM.format("source"))
+        self.target_edges, self.source_edges, self.target_planes, self.source_planes = target_edges, source_edges, target_planes, source_planes
+        self.target_edges_tree = self._tree(target_edges, target_edges_tree, stream)
+        self.target_planes_tree = self._tree(target_planes, target_planes_tree, stream)
+        args = []
+        for tree, tgt, src in [(self.target_edges_tree, target_edges, source_edges), (self.target_planes_tree, target_planes, source_planes)]:
+            if tgt is None:
+                args += [None, None, 0, None, 0]
+                continue
+            GaussianVoxelMapGPU._sync_torch(tgt)
+            GaussianVoxelMapGPU._sync_torch(src)
+            args += [tree._h, tgt.ptr(tgt.points_gpu), tgt.size(), src.ptr(src.points_gpu), src.size()]
+        h = C.c_void_p()
+        _capi.check(self._lib.gp_loam_factor_create(*args, stream, C.byref(h)), "gp_loam_factor_create")
+        self._h = h
+        self.stream = stream
+        self.linearization_point = np.eye(4)
+        self._num_inliers = 0
+        if max_correspondence_distance != 1.0:
+            self.set_max_correspondence_distance(max_correspondence_distance, max_correspondence_distance)
+
+    @staticmethod
+    def _tree(target, tree, stream):
+        if target is None:
+            return None
+        tree = tree if tree is not None else KdTreeGPU(target, stream=stream)
+        if tree.frame.points_gpu is None or tree.frame.points_gpu.data_ptr() != target.points_gpu.data_ptr():
+            raise _capi.GPError("error: target_tree was not built over the target frame's points")
+        return tree
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_loam_factor_destroy(self._h)  # (before the trees it borrows, which are still referenced here)
+            self._h = None
+
+    def keys(self):
+        return self._keys
+
+    def set_max_correspondence_distance(self, dist_edge, dist_plane):
+        _capi.check(self._lib.gp_loam_factor_set_max_correspondence_distance(self._h, float(dist_edge), float(dist_plane)), "gp_loam_factor_set_max_correspondence_distance")
+
+    def set_enable_correspondence_validation(self, enable):
+        """validate_correspondences (:487-529): drop edge pairs / plane triples that lie in one scan line (off by default)"""
+        _capi.check(self._lib.gp_loam_factor_set_enable_correspondence_validation(self._h, int(bool(enable))), "gp_loam_factor_set_enable_correspondence_validation")
+
+    def set_correspondence_update_tolerance(self, angle, trans):
+        _capi.check(self._lib.gp_loam_factor_set_correspondence_update_tolerance(self._h, float(angle), float(trans)), "gp_loam_factor_set_correspondence_update_tolerance")
+
+    calc_delta = IntegratedICPFactorGPU.calc_delta
+
+    def linearize_delta(self, delta):
+        rec = _capi.Linearized6()
+        _capi.check(self._lib.gp_loam_factor_linearize(self._h, _pose16(delta), C.byref(rec)), "gp_loam_factor_linearize")
+        l = LinearizedSystem6(rec)
+        self._num_inliers = l.num_inliers
+        self.linearization_point = np.asarray(delta, dtype=np.float64)
+        self._linearized = True
+        return l
+
+    linearize = IntegratedICPFactorGPU.linearize
+
+    def error(self, values):
+        """evaluate(delta) on the stored correspondences; without any they are computed at `delta` itself first"""
+        delta = self.calc_delta(values)
+        if not getattr(self, "_linearized", False):
+            self.linearization_point = np.asarray(delta, dtype=np.float64)
+            self._linearized = True
+        out = C.c_double()
+        _capi.check(self._lib.gp_loam_factor_compute_error(self._h, _pose16(self.linearization_point), _pose16(delta), C.byref(out)), "gp_loam_factor_compute_error")
+        return out.value
+
+    def num_inliers(self):
+        return self._num_inliers
+
+    def num_correspondences(self):
+        """(edges, planes) of the last linearise"""
+        e, p = C.c_int(0), C.c_int(0)
+        _capi.check(self._lib.gp_loam_factor_num_correspondences(self._h, C.byref(e), C.byref(p)), "gp_loam_factor_num_correspondences")
+        return e.value, p.value
+
+
+class IntegratedPointToEdgeFactorGPU(IntegratedLOAMFactorGPU):
+    """IntegratedPointToEdgeFactor_ (:197-372): the LOAM factor's edge part alone.  set_max_correspondence_distance takes (dist_edge, dist_plane) like the combined
+    factor; the absent part's value is ignored."""
+
+    def __init__(self, target_key, source_key, target, source, target_tree=None, max_correspondence_distance=1.0, stream=None, _fixed_target_pose=None):
+        super().__init__(target_key, source_key, target, None, source, None, target_edges_tree=target_tree, max_correspondence_distance=max_correspondence_distance,
+                         stream=stream, _fixed_target_pose=_fixed_target_pose)
+
+
+class IntegratedPointToPlaneFactorGPU(IntegratedLOAMFactorGPU):
+    """IntegratedPointToPlaneFactor_ (:16-194): the LOAM factor's plane part alone."""
+
+    def __init__(self, target_key, source_key, target, source, target_tree=None, max_correspondence_distance=1.0, stream=None, _fixed_target_pose=None):
+        super().__init__(target_key, source_key, None, target, None, source, target_planes_tree=target_tree, max_correspondence_distance=max_correspondence_distance,
+                         stream=stream, _fixed_target_pose=_fixed_target_pose)
+
+
 def _poses16(deltas, count):
     d = np.asarray(deltas, dtype=np.float64)
     if d.shape != (count, 4, 4):
@@ -284,29 +405,31 @@ def _poses16(deltas, count):
 
 
 class CorrespondenceFactorBatchGPU:
-    """IntegratedGICPFactorGPU / IntegratedICPFactorGPU objects linearised and evaluated TOGETHER (gp_corr_batch_*, csrc/gp_corr_batch.hip): one search launch, one tile
-    launch per factor kind, one finalize launch, whatever their number, with the relative poses read from device memory.  Record order: the GICP factors in the
-    order given, then the ICP factors in the order given (`order`: positions in `factors`; the results below are returned in the order of `factors`).
+    """IntegratedGICPFactorGPU / IntegratedICPFactorGPU / LOAM factor objects linearised and evaluated TOGETHER (gp_corr_batch_*, csrc/gp_corr_batch.hip): a number of
+    launches that does not depend on their number, with the relative poses read from device memory.  Record order: the GICP factors in the order given, then the
+    ICP factors, then the LOAM factors (edge, plane or combined) (`order`: positions in `factors`; the results below are returned in the order of `factors`).
     The batch borrows the factors (kept alive here) and keeps correspondences of its own, in two sets: a linearise searches into the set it names (default 0), an
     error evaluation reads the set it names and never searches.  A record / an error has the bits of the factor's own linearize_delta / error at the same pose(s).
-    ICP factors with non-zero correspondence-update tolerances are refused."""
+    ICP and LOAM factors with non-zero correspondence-update tolerances are refused; a LOAM factor's cut-offs and validation switch are read here, at creation."""
 
     def __init__(self, factors, stream=None):
         self._lib = _capi.load()
         self.factors = list(factors)
         gicp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedGICPFactorGPU)]
         icp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedICPFactorGPU)]
-        if len(gicp) + len(icp) != len(self.factors):
-            raise TypeError("CorrespondenceFactorBatchGPU takes IntegratedGICPFactorGPU / IntegratedICPFactorGPU objects")
-        self.order = gicp + icp  # record r is factors[order[r]]
+        loam = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedLOAMFactorGPU)]
+        if len(gicp) + len(icp) + len(loam) != len(self.factors):
+            raise TypeError("CorrespondenceFactorBatchGPU takes IntegratedGICPFactorGPU / IntegratedICPFactorGPU / IntegratedLOAMFactorGPU objects")
+        self.order = gicp + icp + loam  # record r is factors[order[r]]
         if stream is None and self.factors:
             stream = self.factors[0].stream  # the stream the factors were created on (the library refuses a batch whose factors live on different streams)
         self._slot = np.argsort(np.asarray(self.order, dtype=np.int64)) if self.factors else np.zeros(0, np.int64)  # factors[i] is record _slot[i]
         self.stream = stream
         ga = (C.c_void_p * max(len(gicp), 1))(*[self.factors[i]._h.value for i in gicp])
         ia = (C.c_void_p * max(len(icp), 1))(*[self.factors[i]._h.value for i in icp])
+        la = (C.c_void_p * max(len(loam), 1))(*[self.factors[i]._h.value for i in loam])
         h = C.c_void_p()
-        _capi.check(self._lib.gp_corr_batch_create(ga, len(gicp), ia, len(icp), stream, C.byref(h)), "gp_corr_batch_create")
+        _capi.check(self._lib.gp_corr_batch_create_ex(ga, len(gicp), ia, len(icp), la, len(loam), stream, C.byref(h)), "gp_corr_batch_create_ex")
         self._h = h
         self._dev = None
 

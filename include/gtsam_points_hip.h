@@ -469,7 +469,40 @@ int gp_icp_factor_set_correspondence_update_tolerance(gp_icp_factor_t* f, double
 /* source points that had a correspondence in the last linearise (= its record's num_inliers); 0 before one */
 int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f);
 
-/* ---- a batch of GICP / ICP factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
+/* IntegratedPointToEdgeFactor_, IntegratedPointToPlaneFactor_ and IntegratedLOAMFactor_ (factors/integrated_loam_factor.hpp, impl/integrated_loam_factor_impl.hpp) in
+ * one handle: an edge part and a plane part, either of which may be absent (grid NULL and both counts 0).  Both grids are BORROWED, as for gp_icp_factor_create: the
+ * reference's target_edges_tree / target_planes_tree.  Neither part: GP_ERROR_INVALID_ARGUMENT; a part with a grid but NULL points likewise.
+ *   correspondences  per source point the K nearest target points of T_lin p (f64 on the f32 inputs) with squared distance < max, in ascending order of distance,
+ *                    K = 2 (edge, :235-279) or 3 (plane, :80-124); fewer than K within the cut-off: no correspondence.  Index 0 is the anchor x_j.
+ *   edge  (:300-365) v = x_j - x_l, c = 1/|v|, r = c (q - x_j) x (q - x_l) = A d with A = c [v]x, d = x_j - q, q = T p: error = d^T M d, H = sum J^T M J,
+ *                    b = sum J^T M d with M = A^T A = c^2 [v]x^T [v]x and J_t = [-[q]x, I], J_s = [R [p]x, -R] as for ICP.
+ *   plane (:127-194) n = normalize((x_j - x_l) x (x_j - x_m)), r = n o (x_j - q) element-wise: the point-to-plane ICP term with M = diag(n o n).
+ *                    M, c and n are formed in f64 from the f32 target points.  Degenerate neighbours (x_j = x_l, a collinear triple) are NOT guarded, as in the
+ *                    reference: the division yields non-finite values that flow into the sums, and the call still returns GP_OK.
+ *   validation       IntegratedLOAMFactor_::validate_correspondences (:487-529), off by default; a kernel behind the searches whenever it is enabled (also when the
+ *                    tolerances kept the correspondences: it is idempotent).  theta(p) = atan2(p.z, hypot(p.x, p.y)) in f64; an edge pair is dropped when
+ *                    |theta_j - theta_l| < 0.1 pi / 180, a plane triple when that holds and |theta_j - theta_m| < 0.1 * pi * 180.
+ *                    The second bound is the reference's expression as written (about 56.5 rad, so it always holds); parity with the reference is the target.
+ *   record           the edge part's finalised record plus the plane part's, added in that order in f64 (IntegratedLOAMFactor_::evaluate, :461-472);
+ *                    num_inliers is the sum of the two counts.  Two linearises at one pose are bit-identical.
+ * set_max_correspondence_distance takes DISTANCES (squared inside; default 1.0 each, :27, :205; must be positive); it does not touch stored correspondences.
+ * set_correspondence_update_tolerance is gp_icp_factor_set_correspondence_update_tolerance's host rule, applied to both parts.  compute_error has the semantics of
+ * gp_icp_factor_compute_error: on the stored correspondences when pose_lin is bit for bit the pose of the last linearise or search, otherwise it searches at pose_lin.
+ * Every entry point refuses a NULL handle on the host, before any device work. */
+typedef struct gp_loam_factor gp_loam_factor_t;
+int gp_loam_factor_create(const gp_point_grid_t* edge_grid, const float* target_edges_dev, int num_target_edges, const float* source_edges_dev, int num_source_edges,
+                          const gp_point_grid_t* plane_grid, const float* target_planes_dev, int num_target_planes, const float* source_planes_dev, int num_source_planes,
+                          gp_stream_t stream, gp_loam_factor_t** out);
+int gp_loam_factor_destroy(gp_loam_factor_t* f); /* leaves the grids alone */
+int gp_loam_factor_set_max_correspondence_distance(gp_loam_factor_t* f, double dist_edge, double dist_plane);
+int gp_loam_factor_set_enable_correspondence_validation(gp_loam_factor_t* f, int on);
+int gp_loam_factor_set_correspondence_update_tolerance(gp_loam_factor_t* f, double angle, double trans);
+int gp_loam_factor_linearize(gp_loam_factor_t* f, const double pose[16], gp_linearized6* out_host);
+int gp_loam_factor_compute_error(gp_loam_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
+/* source points that had a correspondence in the last linearise, per part (either pointer may be NULL); 0 before one */
+int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, int* planes);
+
+/* ---- a batch of GICP / ICP / LOAM factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
  * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of
  * launches that does not depend on their count -- one search launch, one tile launch per factor kind present (GICP, ICP point-to-point, ICP point-to-plane), one
  * finalize launch --, the poses read from a table double[F][16] (column-major) in device memory.  The batch BORROWS the factor handles (the caller keeps them and
@@ -489,9 +522,17 @@ int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f);
  * The issue_ forms are asynchronous on the batch's stream.  issue_compute_error_dev: out [F] may be device or host-mapped memory; done_flags (may be NULL) = F words of
  * host-mapped memory, word f receives done_seq behind error f (for a caller that polls instead of synchronising the stream).
  * gp_corr_batch_linearize / _compute_error: the synchronous host-pose forms on set 0 (poses up, wait, results down); compute_error evaluates on the correspondences of
- * the last linearise into set 0, with poses_lin the poses of that linearise (GICP's fused covariances are taken at them). */
+ * the last linearise into set 0, with poses_lin the poses of that linearise (GICP's fused covariances are taken at them).
+ * gp_corr_batch_create_ex adds LOAM members (gp_corr_batch_create means num_loam = 0); record order GICP, ICP, then LOAM, each in the order given.  A LOAM member with
+ * non-zero update tolerances is refused like an ICP one; validation is allowed and runs as a kernel behind the search launch, into the set being written.  A member's
+ * cut-offs and validation switch are read when the batch is created.  Launches with LOAM members: one more search launch (the K > 1 parts), one tile launch per term
+ * kind present (edge, plane), the validation launch if any member enables it, one finalize over the PARTS, and -- when a member has both parts -- one launch that
+ * hands each member its pose in front and one that adds the edge part's record and the plane part's in that order in f64 behind: a LOAM member's record and error
+ * equal, bit for bit, those of gp_loam_factor_linearize / _compute_error at the same pose(s), in both sets. */
 typedef struct gp_corr_batch gp_corr_batch_t;
 int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out);
+int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
+                            gp_stream_t stream, gp_corr_batch_t** out);
 int gp_corr_batch_destroy(gp_corr_batch_t* batch); /* synchronises the batch's stream; leaves the factors alone */
 int gp_corr_batch_size(const gp_corr_batch_t* batch);
 int gp_corr_batch_stream(const gp_corr_batch_t* batch, gp_stream_t* out);
