@@ -406,10 +406,10 @@ struct HostSlots {
   }
 };
 
-void release_side_streams();  // gp_knn.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
+void release_side_streams();  // gp_covariance.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
 }  // namespace gp
 
-struct gp_point_grid;  // private to gp_knn.hip
+struct gp_point_grid;  // gp_knn_grid.hpp: private to gp_knn.hip and gp_covariance.hip
 namespace gp {
 // gp_knn.hip, for the factors of gp_corr_factors.hip: corr[i] = index of the point of `grid` nearest to pose_lin * points[i] (column-major 4x4, f64 on the f32
 // inputs) with squared distance < max_sq_dist, or -1; n > 0.  Asynchronous on `stream`.
