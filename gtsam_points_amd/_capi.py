@@ -336,7 +336,6 @@ GP_TUNE_TILE_CHUNKS = 18
 GP_TUNE_MAX_WORKGROUPS = 19
 GP_TUNE_TEST_ARRIVAL_SKEW = 20
 GP_TUNE_SOURCE_MIRROR, GP_TUNE_EFFECTIVE_MIRROR = 21, 22
-GP_TUNE_EXPERIMENT = 23
 GP_TUNE_BUCKET_LOAD = 24
 GP_TUNE_FAR_POSE_RATIO = 25
 GP_TUNE_MAP_BUILD, GP_TUNE_KNN_STRUCTURE = 16, 32

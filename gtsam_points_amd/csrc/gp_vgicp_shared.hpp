@@ -37,12 +37,32 @@ struct StreamPlan {
   int tail;                     // points behind the last full chunk (the very last workgroup reads them with per-lane loads)
   int pad_;
   // per XCD: the XCDs do not run the same kernel equally fast (XCDs 4-7 end 0.5-0.9 us behind 0-3 on equal shares, whatever data they are
-  // given: profiles/r03_sweep.jsonl), so their shares differ (host: kXcdWeightPermille in gp_vgicp.hip)
+  // given: profiles/r03_sweep.jsonl), so their shares differ (host: kXcdWeightPermille in gp_vgicp_plan.hpp)
   int xbegin[kNumXCD];               // first chunk of the XCD's share
   int n[kNumXCD][3], pre[kNumXCD][3];  // rounds in front of the last one: chunks per workgroup, and chunks of the share in front of the round
   int before_last[kNumXCD];          // chunks of the share in front of its last round
   int lo[kNumXCD], extra[kNumXCD];   // the last round: `lo` chunks per workgroup, the first `extra` workgroups one more
 };
+
+constexpr int kChunkPoints = 64;
+constexpr int kPipelineChunks = 4;  // 64-point chunks per wave of vgicp_pipeline_kernel: 1024-point tiles (the 512- / 256-point instantiations went in round 6)
+// the points workgroup (x = XCD, q = position in the XCD's share) of a planned single-factor launch owns -- also what the host writes into the
+// tile table for the launches that cannot carry the descriptor in their arguments (make_stream_plan, gp_vgicp_plan.hpp)
+struct PlanFields {  // the fields of the plan workgroup (x, q) needs
+  int nr, pre, lo, extra, xbegin, L, before_last, gx, tail;
+};
+__host__ __device__ __forceinline__ PlanFields plan_fields(const StreamPlan& p, int x, int q) {
+  const int r = q / kStreamRound < 2 ? q / kStreamRound : 2;  // (workgroups of the last round do not use nr / pre)
+  return PlanFields{p.n[x][r], p.pre[x][r], p.lo[x], p.extra[x], p.xbegin[x], p.last_begin, p.before_last[x], p.wgs_per_xcd, p.tail};
+}
+__host__ __device__ __forceinline__ void plan_tile(const PlanFields& f, int x, int q, int* begin, int* count) {
+  const int i = q % kStreamRound, k = q - f.L;
+  const bool late = q >= f.L;
+  const int n = late ? f.lo + (k < f.extra ? 1 : 0) : f.nr;
+  const int c0 = late ? f.before_last + k * f.lo + (k < f.extra ? k : f.extra) : f.pre + i * f.nr;
+  *begin = (f.xbegin + c0) * kChunkPoints;
+  *count = n * kChunkPoints + ((x == kNumXCD - 1 && q == f.gx - 1) ? f.tail : 0);  // the very last workgroup also takes the points behind the last full chunk
+}
 
 // a single-factor launch carries its poses AND its factor descriptor in the kernel arguments: no H2D copy and no
 // dependent descriptor loads on the latency path (2.8 us per workgroup in the timeline traces)

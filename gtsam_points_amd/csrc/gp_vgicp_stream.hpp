@@ -26,6 +26,16 @@
 
 namespace gp {
 
+// per-workgroup phase timestamps (s_memtime) of the TRACE builds, for timeline analysis: [num_tiles][16] uint64 (slots 0-7 phases, 8 HW_ID, 9 XCC_ID,
+// 10 / 11 start and end on the device-wide 100 MHz clock), enabled by the host (gp_vgicp_batch_set_trace_buffer)
+#define GP_TRACE(slot)                                                                                 \
+  do {                                                                                                 \
+    if constexpr (TRACE) {                                                                             \
+      if (trace && threadIdx.x == 0) trace[(size_t)tile_idx * 16 + (slot)] = __builtin_amdgcn_s_memtime(); \
+    }                                                                                                  \
+  } while (0)
+#define GP_GETREG_HW_ID ((31 << 11) | (0 << 6) | 4)  // the whole HW_ID word (s_getreg_b32)
+
 // normals: one more 12-B row per chunk (64 slots of 16 B, like the points)
 template <bool NT>
 __device__ __forceinline__ void chunk_dma12_row(const GP_GLOBAL char* urow, unsigned voff, char* slot) {
@@ -50,33 +60,14 @@ struct WaveWork {
 
 // a workgroup's points [begin, begin + count) -> its four waves: the full chunks are dealt as evenly as they go (the first `extra` waves take
 // one more), the points behind the last full chunk go to the last wave
-template <int W = 4>
 __device__ __forceinline__ WaveWork split_tile(int begin, int count, int wave) {
-  static_assert(W == 4 || W == 8 || W == 16, "waves per workgroup");
+  constexpr int W = 4;
   const int chunks = count >> 6, base = chunks / W, extra = chunks % W;  // (W is a power of two: shift and mask)
   WaveWork ww;
   ww.first = (size_t)begin + (size_t)(wave * base + (wave < extra ? wave : extra)) * kChunkPoints;
   ww.n = base + (wave < extra ? 1 : 0);
   ww.tail = wave == W - 1 ? (count & 63) : 0;
   return ww;
-}
-
-// the points workgroup (x = XCD, q = position in the XCD's share) of a planned single-factor launch owns -- also what the host writes into the
-// tile table for the launches that cannot carry the descriptor in their arguments (make_stream_plan in gp_vgicp.hip)
-struct PlanFields {  // the fields of the plan workgroup (x, q) needs
-  int nr, pre, lo, extra, xbegin, L, before_last, gx, tail;
-};
-__host__ __device__ __forceinline__ PlanFields plan_fields(const StreamPlan& p, int x, int q) {
-  const int r = q / kStreamRound < 2 ? q / kStreamRound : 2;  // (workgroups of the last round do not use nr / pre)
-  return PlanFields{p.n[x][r], p.pre[x][r], p.lo[x], p.extra[x], p.xbegin[x], p.last_begin, p.before_last[x], p.wgs_per_xcd, p.tail};
-}
-__host__ __device__ __forceinline__ void plan_tile(const PlanFields& f, int x, int q, int* begin, int* count) {
-  const int i = q % kStreamRound, k = q - f.L;
-  const bool late = q >= f.L;
-  const int n = late ? f.lo + (k < f.extra ? 1 : 0) : f.nr;
-  const int c0 = late ? f.before_last + k * f.lo + (k < f.extra ? k : f.extra) : f.pre + i * f.nr;
-  *begin = (f.xbegin + c0) * kChunkPoints;
-  *count = n * kChunkPoints + ((x == kNumXCD - 1 && q == f.gx - 1) ? f.tail : 0);  // the very last workgroup also takes the points behind the last full chunk
 }
 
 // The last workgroup of a part (fused finalize, see InlinePoses): all 256 threads sum the part's rows -- every one stored write-through by its
@@ -91,8 +82,7 @@ __device__ __forceinline__ void finalize_part_rows(const double* __restrict__ pa
   // read past this CU's L1 and the XCD's L2 view of other XCDs' lines (sc1), all of a lane's rows requested in one batch
   const unsigned long long* base = reinterpret_cast<const unsigned long long*>(partials + (size_t)row_begin * ACC_STRIDE + comp);
   double total = 0.0;
-  // (wide workgroups, W > 4: the first four waves do what the 256 threads of the narrow form do -- the same order, the same bits as the split finalize kernel --
-  // the others only meet them at the barrier)
+  // (`wave < 4` here and below always holds in a 256-thread workgroup; the tests stay because the compiler emits other instructions without them)
   for (int t0 = slice; t0 < row_count && wave < 4; t0 += 32 * kSlices) {
     double v[32];
 #pragma unroll
@@ -130,7 +120,7 @@ __device__ __forceinline__ void finalize_part_error(const double* __restrict__ p
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const unsigned long long* base = reinterpret_cast<const unsigned long long*>(partials + (size_t)row_begin * ACC_STRIDE + ACC_ERR);
   double s = 0.0;
-  for (int t = threadIdx.x; t < row_count && wave < 4; t += 256)  // (wide workgroups: the first four waves, as above)
+  for (int t = threadIdx.x; t < row_count && wave < 4; t += 256)  // (always true, as above)
     s += __builtin_bit_cast(double, __hip_atomic_load(base + (size_t)t * ACC_STRIDE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
@@ -142,19 +132,18 @@ __device__ __forceinline__ void finalize_part_error(const double* __restrict__ p
   asm volatile("global_store_dwordx2 %0, %1, off sc0 sc1" : : "v"(flag), "v"(seq) : "memory");
 }
 
-// EXP (measurement instantiations of round 5, never the default; GP_TUNE_EXPERIMENT selects them for a synchronous planned single-factor linearise):
-//   1 = every workgroup touches its share of the map's block grid right behind its first request, so that an XCD's L2 holds the whole grid (1 MB for the headline map)
-//       by the time the first hop 1 asks for it (VERDICT r04 #1b: the cold first chunk);  2 = R C_A R^T in f32 (accumulate_core2<ROT32>: the upper bound of #1c)
-// W (round 6): waves per workgroup.  4 = the product geometry (1024 workgroups of 256 threads for a planned launch, four per compute unit);
-//   16 = ONE 1024-thread workgroup per compute unit (256 workgroups: a quarter of the dispatches, partial rows and arrivals; the sixteen waves' sums meet in LDS in
-//   a fixed pairwise tree), 8 = two per compute unit.  Same waves, same rings, same per-wave schedule: only who shares a row changes.
-//   MEASURED AND NOT ADOPTED (profiles/r06_wg_geometry.jsonl, r06_wg_geometry_kernel_stats.csv; commit 1af148a carries the launch code and the GP_TUNE_WG_WAVES knob):
-//   in step, alternating, whole fused kernel 12.40-12.46 us (W = 4) / 12.41 (16) / 12.40-12.51 (8); rocprofv3 averages 14.09 / 14.23 / 13.95 us -- the fused tail is a
-//   latency chain (row store -> arrival -> loads -> sums over PCIe), not a count of rows or dispatches.  Only W = 4 is instantiated.
-template <int MODE, bool NT, bool INL, bool SV, bool PK, bool TRACE = false, int EXP = 0, int W = 4>
-__global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDesc* __restrict__ factors, const TileDesc* __restrict__ tiles, int num_tiles,
-                                                               const double* __restrict__ poses_lin, const double* __restrict__ poses_eval, const InlinePoses inl,
-                                                               double* __restrict__ partials) {
+// Measured and not adopted (the code is gone, the numbers stay):
+//   round 5, two measurement builds behind GP_TUNE_EXPERIMENT -- every workgroup touching its share of the map's block grid behind its first request, and R C_A R^T in
+//   f32 -- in profiles/r05_kernel_experiments.txt; commit f92947a carries the builds (template axis EXP) and the knob.
+//   round 6, 8 and 16 waves per workgroup (one or two workgroups per compute unit instead of four) in profiles/r06_wg_geometry.jsonl and
+//   r06_wg_geometry_kernel_stats.csv; commit 1af148a carries the launch code and the GP_TUNE_WG_WAVES knob.  The fused tail is a latency chain (row store ->
+//   arrival -> loads -> sums over PCIe), not a count of rows or dispatches.
+// Four waves per workgroup: 1024 workgroups of 256 threads for a planned launch, four per compute unit.
+template <int MODE, bool NT, bool INL, bool SV, bool PK, bool TRACE = false>
+__global__ void __launch_bounds__(256, 4) vgicp_stream_kernel(const FactorDesc* __restrict__ factors, const TileDesc* __restrict__ tiles, int num_tiles,
+                                                              const double* __restrict__ poses_lin, const double* __restrict__ poses_eval, const InlinePoses inl,
+                                                              double* __restrict__ partials) {
+  constexpr int W = 4;  // waves per workgroup
   static_assert(MODE == MODE_LIN || MODE == MODE_ERR, "rigid linearise and error evaluation");
   constexpr int NACC = MODE == MODE_ERR ? 2 : 32;
   // PK: the source stream is the factor's PACKED MIRROR (SourceMirror, gp_host.hpp): per 64-point chunk 2304 contiguous bytes = 64 points (12 B) | 64 x
@@ -180,11 +169,9 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
   FactorDesc f;
   WaveWork ww;
   int factor_idx = 0, row;
-  int wgs_per_xcd = 0;  // (EXP 1)
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (INL) {
     PlanFields pf = plan_fields(inl.plan, bx, bq);
-    wgs_per_xcd = pf.gx;
     int tile_points = inl.tile_points, fn = inl.factor.n;
     const float* fpts = inl.factor.points;
     const float* fcov = inl.factor.covs;
@@ -211,7 +198,7 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
     f.normals = fnrm;
     f.packed = fpk;
     row = tile_idx;
-    ww = split_tile<W>(begin, count, wave);
+    ww = split_tile(begin, count, wave);
   } else {
     if (inl.xcd_chunk > 0) {
       const int c = inl.xcd_chunk;
@@ -225,7 +212,7 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
     f = factors[tile.factor];
     factor_idx = tile.factor;
     row = tile.row;
-    ww = split_tile<W>(__builtin_amdgcn_readfirstlane(tile.begin), __builtin_amdgcn_readfirstlane(tile.count), wave);
+    ww = split_tile(__builtin_amdgcn_readfirstlane(tile.begin), __builtin_amdgcn_readfirstlane(tile.count), wave);
   }
   unsigned long long* trace = TRACE ? inl.trace : nullptr;
   GP_TRACE(0);
@@ -280,17 +267,6 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
   const GP_GLOBAL char* gblocks = uniform_ptr((const GP_GLOBAL char*)f.map.gblocks);
   const GP_GLOBAL char* records = uniform_ptr((const GP_GLOBAL char*)f.map.records);
 
-  v4i warm = {0, 0, 0, 0};
-  if constexpr (EXP == 1) {
-    // workgroup q of an XCD asks for bytes [(k * wgs + q) * 4096 + 16 tid, + 16) of the grid, k = 0 .. 3: 2 MB per XCD at 128 workgroups.  Behind the points'
-    // request in the queue; both are retired by the vmcnt(0) in front of the first transform
-    const unsigned gbytes = gd0 * gd1 * gd2 * 16u;
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const unsigned off = ((unsigned)(k * wgs_per_xcd + bq) * 256u + threadIdx.x) * 16u;
-      if (off < gbytes) asm volatile("global_load_dwordx4 %0, %1, %2" : "+v"(warm) : "v"(off), "s"(gblocks) : "memory");
-    }
-  }
   // the translation lives in vector registers: a VOP3 instruction reads ONE scalar operand (gp_vgicp_tile2.hpp)
   double tvx, tvy, tvz;
   asm volatile("v_mov_b64 %0, %1" : "=v"(tvx) : "s"(Tl.tx));
@@ -395,7 +371,6 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
     // points first: only chunk 0's points (and normals) are in flight, so the first transform and hop 1 do not queue behind everybody's
     // covariances; those follow hop 1 (they are needed behind hop 2), the head of chunk 1 goes out before hop 2 and its covariances behind it
     vm_wait<0>();
-    if constexpr (EXP == 1) asm volatile("" : : "v"(warm));  // (the registers the warm-up loads land in stay reserved until here)
     GP_TRACE(1);
     front_ring(0, Pc);  // in flight: H0
     dma_cov(0, 0);
@@ -423,7 +398,7 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
         dma_head(j + 2, par);
         dma_cov(j + 2, par);
       }
-      if (hit) accumulate_core2<MODE, EXP == 2>(Tl, a, c01, c23, c45, Pc.ex + head.x, Pc.ey + head.y, Pc.ez + head.z, Pc.qx, Pc.qy, Pc.qz, acc);
+      if (hit) accumulate_core2<MODE>(Tl, a, c01, c23, c45, Pc.ex + head.x, Pc.ey + head.y, Pc.ez + head.z, Pc.qx, Pc.qy, Pc.qz, acc);
       if constexpr (TRACE) {
         if (j == 0) GP_TRACE(3);
         if (j == 1) GP_TRACE(5);
@@ -519,23 +494,11 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
   if (threadIdx.x < ACC_STRIDE) {
     double sum = 0.0;
     if (threadIdx.x < (MODE == MODE_ERR ? 2 : ACC_SIZE)) {
-      if constexpr (W == 4) {
-        const double* w0 = reinterpret_cast<const double*>(smem + 1 * kWaveBytes - 32 * 8);
-        const double* w1 = reinterpret_cast<const double*>(smem + 2 * kWaveBytes - 32 * 8);
-        const double* w2 = reinterpret_cast<const double*>(smem + 3 * kWaveBytes - 32 * 8);
-        const double* w3 = reinterpret_cast<const double*>(smem + 4 * kWaveBytes - 32 * 8);
-        sum = (w0[threadIdx.x] + w1[threadIdx.x]) + (w2[threadIdx.x] + w3[threadIdx.x]);
-      } else {  // fixed pairwise tree over the W waves in wave order: ((w0 + w1) + (w2 + w3)) + ((w4 + w5) + (w6 + w7)) ...
-        double v[W];
-#pragma unroll
-        for (int k = 0; k < W; k++) v[k] = reinterpret_cast<const double*>(smem + (k + 1) * kWaveBytes - 32 * 8)[threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < W; w <<= 1) {
-#pragma unroll
-          for (int k = 0; k < W; k += 2 * w) v[k] += v[k + w];
-        }
-        sum = v[0];
-      }
+      const double* w0 = reinterpret_cast<const double*>(smem + 1 * kWaveBytes - 32 * 8);
+      const double* w1 = reinterpret_cast<const double*>(smem + 2 * kWaveBytes - 32 * 8);
+      const double* w2 = reinterpret_cast<const double*>(smem + 3 * kWaveBytes - 32 * 8);
+      const double* w3 = reinterpret_cast<const double*>(smem + 4 * kWaveBytes - 32 * 8);
+      sum = (w0[threadIdx.x] + w1[threadIdx.x]) + (w2[threadIdx.x] + w3[threadIdx.x]);
     }
     GP_GLOBAL double* dst = (GP_GLOBAL double*)partials + (size_t)row * ACC_STRIDE + threadIdx.x;
     if (inl.arrive) {
@@ -570,7 +533,7 @@ __global__ void __launch_bounds__(64 * W, 4) vgicp_stream_kernel(const FactorDes
                              *reinterpret_cast<const unsigned long long*>(last + 2));
       }
     }
-  } else if (W == 4 && inl.arrive) {  // (wide workgroups exist for planned single-factor launches only: the host never arms this form for them)
+  } else if (inl.arrive) {
     // fused finalize by FACTOR (synchronous batched calls, small single factors): the workgroup that stores a factor's last row sums the factor's rows and
     // expands them into the record -- rigid_slice_total / rigid_wave_tree / rigid_expand_wave in the order of vgicp_finalize_rigid_kernel<1024>, whose 32
     // slices of rows are taken four to a thread here -- and hands record and completion word to the host while the other factors' tiles are still running:

@@ -179,15 +179,6 @@ __device__ __forceinline__ void load_cov6(P c9, double* a) {
   }
 }
 
-// optional per-workgroup phase timestamps (s_memtime) for timeline analysis: [num_tiles][16] uint64 (slots 0-7 phases, 8 HW_ID,
-// 9 XCC_ID), enabled by the host
-#define GP_TRACE(slot)                                                                                 \
-  do {                                                                                                 \
-    if constexpr (TRACE) {                                                                             \
-      if (trace && threadIdx.x == 0) trace[(size_t)tile_idx * 16 + (slot)] = __builtin_amdgcn_s_memtime(); \
-    }                                                                                                  \
-  } while (0)
-
 // =====================================================================================================================
 // vgicp_pipeline_kernel -- rolling LDS-DMA source pipeline, one 64-point chunk per wave step.
 //
@@ -204,7 +195,6 @@ __device__ __forceinline__ void load_cov6(P c9, double* a) {
 // A wave whose rows are not all there (last tile of a factor) or whose base pointers are not 16-B aligned reads its
 // points with plain per-lane loads instead (same arithmetic, same order).
 // =====================================================================================================================
-constexpr int kChunkPoints = 64;
 constexpr int kChunkBytes = kChunkPoints * 48;  // [64][3] floats, then [64][9] floats
 constexpr int kChunkDmaOps = 3;                 // 3 x 64 lanes x 16 B: pieces 0..47 are the points, 48..191 the covariances
 
@@ -281,9 +271,8 @@ __device__ __forceinline__ void grid_wait(v4i& blk) {
   }
 }
 
-// HW_ID register fields (s_getreg_b32): wave slot within the SIMD, and the whole word / the XCC id for the timeline traces
+// HW_ID register fields (s_getreg_b32): wave slot within the SIMD, and the XCC id for the finalize kernels' timeline
 #define GP_GETREG_WAVE_SLOT ((3 << 11) | (0 << 6) | 4)  // HW_REG_HW_ID[3:0]
-#define GP_GETREG_HW_ID ((31 << 11) | (0 << 6) | 4)
 #define GP_GETREG_XCC_ID ((31 << 11) | (0 << 6) | 20)
 
 // Waves per SIMD: 4 with f32 accumulators (<= 128 VGPRs), 3 with f64 accumulators (<= 168 VGPRs).  The kernel must not spill:
@@ -294,12 +283,13 @@ __device__ __forceinline__ void grid_wait(v4i& blk) {
 // together with hop 2 of chunk j -- one exposed round trip per step instead of two.  What chunk j+1 needs after its lookup (cell bit,
 // centre - l and q as floats, the block entry: 12 registers) stays live through the algebra of chunk j; the kernel has the room
 // (105 VGPRs without it, 128 allowed at four waves per SIMD).
-template <int MODE, bool OUTER_F32, int PPT, bool GRID, bool TRACE = false, bool LEAN = false, bool AHEAD = false>
+template <int MODE, bool OUTER_F32, bool GRID, bool LEAN = false, bool AHEAD = false>
 __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) vgicp_pipeline_kernel(const FactorDesc* __restrict__ factors, const TileDesc* __restrict__ tiles, int num_tiles,
                                                              const double* __restrict__ poses_lin, const double* __restrict__ poses_eval, const InlinePoses inl,
                                                              double* __restrict__ partials) {
   static_assert(MODE == MODE_LIN || MODE == MODE_ERR, "tuned kernel covers the rigid linearise and the error evaluation");
   constexpr int NACC = MODE == MODE_ERR ? 2 : ACC_SIZE;
+  constexpr int PPT = kPipelineChunks;
   constexpr int STAGES = 3;
   __shared__ __attribute__((aligned(16))) char smem[4 * STAGES * kChunkBytes];  // 36 KB
   // XCD-aware workgroup -> tile map (workgroup b runs on XCD b % 8)
@@ -312,18 +302,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
     tile_idx = (blockIdx.x % kNumXCD) * per + blockIdx.x / kNumXCD;
   }
   if (tile_idx >= num_tiles) return;
-  unsigned long long* trace = TRACE ? inl.trace : nullptr;
-  GP_TRACE(0);
-  if constexpr (TRACE) {
-    // s_memtime (the stamps above) runs at the shader clock but is not synchronised across compute units: only differences inside
-    // one workgroup mean anything.  s_memrealtime is the 100 MHz constant clock shared by the whole device: start / end of every
-    // workgroup on one time axis (10 ns resolution) for the ramp and the tail of the launch.
-    if (trace && threadIdx.x == 0) trace[(size_t)tile_idx * 16 + 10] = __builtin_amdgcn_s_memrealtime();
-    if (trace && threadIdx.x == 0) {
-      trace[(size_t)tile_idx * 16 + 8] = __builtin_amdgcn_s_getreg(GP_GETREG_HW_ID);
-      trace[(size_t)tile_idx * 16 + 9] = __builtin_amdgcn_s_getreg(GP_GETREG_XCC_ID);
-    }
-  }
   TileDesc tile;
   if (inl.use) {
     tile.factor = 0;
@@ -411,8 +389,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
       } else {
         grid_wait<0>(blk);
       }
-      if (j == 0) GP_TRACE(2);
-      if (j == 1) GP_TRACE(4);
       const unsigned long long bits = ((unsigned long long)(unsigned)blk.y << 32) | (unsigned long long)(unsigned)blk.x;
       const int pos = ((cz & 3) << 4) | ((cy & 3) << 2) | (cx & 3);
       if (inbox && ((bits >> pos) & 1ull)) idx = blk.z + __popcll(bits & ((1ull << pos) - 1ull));
@@ -422,8 +398,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
       v4i k0, k1, k2, k3;
       line_issue(lines + 64 * (size_t)l, k0, k1, k2, k3);
       line_wait(k0, k1, k2, k3);
-      if (j == 0) GP_TRACE(2);
-      if (j == 1) GP_TRACE(4);
       idx = line_match(k0, k1, k2, k3, cx, cy, cz);
       if (live && idx < 0 && k3.w >= 0) {  // full line, no match (rare): walk on
         for (;;) {
@@ -522,7 +496,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
       Ahead P[2];
       // in flight: chunk 0, chunk 1 (3 requests each)
       asm volatile("s_waitcnt vmcnt(3)" ::: "memory");  // chunk 0 is in LDS
-      GP_TRACE(1);
       front(0, P[0]);                                    // in flight: chunk 1, hop 1 of chunk 0
 #pragma unroll
       for (int j = 0; j < PPT; j++) {
@@ -539,11 +512,7 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
         } else {
           grid_wait<0>(P[j & 1].blk);
         }
-        if (j == 0) GP_TRACE(2);
-        if (j == 1) GP_TRACE(4);
         back(j, P[j & 1]);
-        if (j == 0) GP_TRACE(3);
-        if (j == 1) GP_TRACE(5);
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
@@ -557,9 +526,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
-      if (j == 0) GP_TRACE(1);
-      if (j == 1) GP_TRACE(3);
-      if (j == 2) GP_TRACE(5);
       const float* lp = reinterpret_cast<const float*>(wbase + (j % STAGES) * kChunkBytes);
       const float* lc = lp + kChunkPoints * 3 + 9 * lane;
       const float px = lp[3 * lane], py = lp[3 * lane + 1], pz = lp[3 * lane + 2];
@@ -577,7 +543,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
     }
   }
 
-  GP_TRACE(6);
   // ---- reduction.  The wave's ring (3 x 3 KB, drained) becomes a transposition buffer: 16 components x 64 lanes of f64
   // at a row stride of 68 doubles (conflicts <= 2-way) are written lane-major and read back so that every lane sums 16
   // values of one component, the 4 lanes of a quad are combined with two DPP swaps, and lane 4c holds component c.
@@ -648,10 +613,6 @@ __global__ void __launch_bounds__(256, (OUTER_F32 || MODE == MODE_ERR) ? 4 : 3) 
       sum = (w0[threadIdx.x] + w1[threadIdx.x]) + (w2[threadIdx.x] + w3[threadIdx.x]);
     }
     ((GP_GLOBAL double*)partials)[(size_t)tile.row * ACC_STRIDE + threadIdx.x] = sum;
-  }
-  GP_TRACE(7);
-  if constexpr (TRACE) {
-    if (trace && threadIdx.x == 0) trace[(size_t)tile_idx * 16 + 11] = __builtin_amdgcn_s_memrealtime();
   }
 }
 

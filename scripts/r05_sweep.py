@@ -1,6 +1,7 @@
 """Round-5 A/B on the GPU box (VERDICT r04 #1b / #1c): the C2 headline step as bench.py runs it (synchronous fused call) with the measurement instantiations of the stream
 kernel (GP_TUNE_EXPERIMENT: 1 = block-grid warm-up behind the first request, 2 = R C_A R^T in f32 -- breaks parity, timing only) against the product kernel, alternating,
 by the kernel's own 100 MHz stamps inside the steps (streaming part, whole fused kernel), host wall per step and the tile kernel back to back (HIP events).
+Needs the library of commit f92947a (GP_TUNE_EXPERIMENT = 23 and the two measurement instantiations were removed: not adopted).
 One JSON object per line.  Usage: python scripts/r05_sweep.py [--points N] [--steps K] [--reps R]"""
 import ctypes as C
 import json

@@ -113,6 +113,8 @@ def test_every_kernel_variant_matches_the_oracle(gpu, kitti00, variant, tol):
     # an invalid family is refused, and the refusal leaves the factor as it was
     with pytest.raises(gpu.GPError):
         f.set_tuning(KERNEL, 5)
+    with pytest.raises(gpu.GPError):
+        f.set_tuning(23, 1)  # was GP_TUNE_EXPERIMENT: removed with its measurement builds, an unknown key like any other
     assert_linearized_close(_sync_linearize(gpu, f, delta), fo.linearize(delta), tol, f"variant {variant} again")
 
 
