@@ -166,7 +166,11 @@ int build_table(gp_vgicp_batch* b) {
     for (int i = 0; i < F; i++) {
       gp::FactorDesc& d = descs[i];
       d.tile_begin = (int)tiles.size();
-      for (int p = 0; p < d.n; p += b->tile_points) tiles.push_back(gp::TileDesc{i, p, std::min(b->tile_points, d.n - p), (int)tiles.size()});
+      for (int t = 0, T = gp::fixed_tile_count(d.n, b->tile_points); t < T; t++) {
+        int begin = 0, count = 0;
+        gp::fixed_tile(t, d.n, b->tile_points, &begin, &count);
+        tiles.push_back(gp::TileDesc{i, begin, count, (int)tiles.size()});
+      }
       d.tile_count = (int)tiles.size() - d.tile_begin;
     }
   }
@@ -567,7 +571,8 @@ static int apply_tuning(gp_vgicp_tuning* t, int key, int value) {
       t->far_pose_ratio = value;
       return GP_OK;
     case GP_TUNE_BALANCE:
-      if (value < -1 || value > 600) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "GP_TUNE_BALANCE: -1 (automatic), 0 (flat) .. 600 (per mille of the mean share per dispatch round)");
+      // make_stream_plan refuses a skew that overdraws an XCD's share and deals that launch flat
+      if (value < -1 || value > 1000) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "GP_TUNE_BALANCE: -1 (automatic), 0 (flat) .. 1000 (per mille of the mean share per dispatch round)");
       t->balance = value;
       return GP_OK;
     default:
@@ -1037,6 +1042,35 @@ int gp_debug_stream_plan(int n, int skew_permille, const int* xcd_weights_permil
     for (int x = 0; x < gp::kNumXCD; x++)
       for (int q = 0; q < plan.wgs_per_xcd; q++, t++) gp::plan_tile(gp::plan_fields(plan, x, q), x, q, &begin[t], &count[t]);
   }
+  return GP_OK;
+}
+
+// ... the same with the launch's other inputs, down to the waves.  tile_points == 0: the planned launch of at most max_workgroups workgroups (GP_TUNE_MAX_WORKGROUPS;
+// make_stream_plan + plan_tile, what build_table() stores and the kernel derives); tile_points > 0: the fixed tiles of a small factor (a whole number of chunks per
+// wave).  waves, if given: [capacity * 4][3] = first point, full chunks and tail of every wave of every workgroup (split_tile, the kernel's own function).
+int gp_debug_stream_plan_ex(int n, int tile_points, int max_workgroups, int skew_permille, const int* xcd_weights_permille, int capacity, int* begin, int* count,
+                            long long* waves, int* num_tiles) {
+  if (n < 0 || skew_permille < -1 || !num_tiles || tile_points < 0 || tile_points % (4 * gp::kChunkPoints) != 0 || (tile_points == 0 && (max_workgroups < 8 || max_workgroups > 1024)))
+    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_debug_stream_plan_ex: bad arguments");
+  gp::StreamPlan plan;
+  const int G = tile_points ? gp::fixed_tile_count(n, tile_points) : make_stream_plan(n, skew_permille, xcd_weights_permille, &plan, max_workgroups);
+  *num_tiles = G;
+  if (!begin || !count) return GP_OK;
+  if (capacity < G) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_debug_stream_plan_ex: capacity too small");
+  if (tile_points) {
+    for (int t = 0; t < G; t++) gp::fixed_tile(t, n, tile_points, &begin[t], &count[t]);
+  } else {
+    int t = 0;
+    for (int x = 0; x < gp::kNumXCD; x++)
+      for (int q = 0; q < plan.wgs_per_xcd; q++, t++) gp::plan_tile(gp::plan_fields(plan, x, q), x, q, &begin[t], &count[t]);
+  }
+  if (waves)
+    for (int t = 0; t < G; t++)
+      for (int w = 0; w < 4; w++) {
+        const gp::WaveWork ww = gp::split_tile(begin[t], count[t], w);
+        long long* o = waves + ((size_t)t * 4 + w) * 3;
+        o[0] = (long long)ww.first, o[1] = ww.n, o[2] = ww.tail;
+      }
   return GP_OK;
 }
 

@@ -110,6 +110,14 @@ inline int make_stream_plan(int n, int skew_permille, const int* xcd_weights, gp
   return G;
 }
 
+// Fixed tiles (every batch, and a single factor below the planning threshold): a factor of n points is cut into tiles of tile_points, the last one partial.
+// build_table() fills the tile table with these, gp_debug_stream_plan_ex shows them.
+inline int fixed_tile_count(int n, int tile_points) { return (n + tile_points - 1) / tile_points; }
+inline void fixed_tile(int t, int n, int tile_points, int* begin, int* count) {
+  *begin = t * tile_points;
+  *count = std::min(tile_points, n - t * tile_points);
+}
+
 // the 6x6 expansion of the rigid finalize kernel on the host (same formulas: H_t from the 29 sums, Ad(delta), H_ts = -H_t Ad, H_s = Ad^T H_t Ad,
 // b_s = -Ad^T b_t): used by the synchronous single-factor call, whose finalize parts then deliver only their sums
 inline void expand_rigid_host(const double* sum, const double* pose /*col-major 4x4*/, double* dst /*[122]*/) {

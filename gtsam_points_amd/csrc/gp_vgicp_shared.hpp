@@ -64,6 +64,25 @@ __host__ __device__ __forceinline__ void plan_tile(const PlanFields& f, int x, i
   *count = n * kChunkPoints + ((x == kNumXCD - 1 && q == f.gx - 1) ? f.tail : 0);  // the very last workgroup also takes the points behind the last full chunk
 }
 
+// the stream of one wave: `first` point, `n` full 64-point chunks, then `tail` (< 64) points read with per-lane loads
+struct WaveWork {
+  size_t first;
+  int n;
+  int tail;
+};
+
+// a workgroup's points [begin, begin + count) -> its four waves: the full chunks are dealt as evenly as they go (the first `extra` waves take
+// one more), the points behind the last full chunk go to the last wave.  (Host side: gp_debug_stream_plan_ex shows the waves of a launch.)
+__host__ __device__ __forceinline__ WaveWork split_tile(int begin, int count, int wave) {
+  constexpr int W = 4;
+  const int chunks = count >> 6, base = chunks / W, extra = chunks % W;  // (W is a power of two: shift and mask)
+  WaveWork ww;
+  ww.first = (size_t)begin + (size_t)(wave * base + (wave < extra ? wave : extra)) * kChunkPoints;
+  ww.n = base + (wave < extra ? 1 : 0);
+  ww.tail = wave == W - 1 ? (count & 63) : 0;
+  return ww;
+}
+
 // a single-factor launch carries its poses AND its factor descriptor in the kernel arguments: no H2D copy and no
 // dependent descriptor loads on the latency path (2.8 us per workgroup in the timeline traces)
 struct InlinePoses {

@@ -51,24 +51,7 @@ __device__ __forceinline__ void vm_wait_blk_n(v4i& blk) {
   if constexpr (N == 5) asm volatile("s_waitcnt vmcnt(5)" : "+v"(blk) : : "memory");
 }
 
-// the stream of one wave: `first` point, `n` full 64-point chunks, then `tail` (< 64) points read with per-lane loads
-struct WaveWork {
-  size_t first;
-  int n;
-  int tail;
-};
-
-// a workgroup's points [begin, begin + count) -> its four waves: the full chunks are dealt as evenly as they go (the first `extra` waves take
-// one more), the points behind the last full chunk go to the last wave
-__device__ __forceinline__ WaveWork split_tile(int begin, int count, int wave) {
-  constexpr int W = 4;
-  const int chunks = count >> 6, base = chunks / W, extra = chunks % W;  // (W is a power of two: shift and mask)
-  WaveWork ww;
-  ww.first = (size_t)begin + (size_t)(wave * base + (wave < extra ? wave : extra)) * kChunkPoints;
-  ww.n = base + (wave < extra ? 1 : 0);
-  ww.tail = wave == W - 1 ? (count & 63) : 0;
-  return ww;
-}
+// (WaveWork and split_tile -- a workgroup's points -> its four waves' streams -- live in gp_vgicp_shared.hpp beside plan_tile: the host shows them too)
 
 // The last workgroup of a part (fused finalize, see InlinePoses): all 256 threads sum the part's rows -- every one stored write-through by its
 // workgroup before that workgroup's add to the arrival counter -- in exactly the order of the split form of vgicp_finalize_rigid_kernel<256>

@@ -830,8 +830,8 @@ enum {
   GP_TUNE_STAGGER = 3,          /* round-2 kernels: the odd wave slots of every SIMD start `value` x 512 clocks late (0 = off) */
   GP_TUNE_TILE_INTERLEAVE = 4,  /* 1 = consecutive factors that share a source cloud take turns tile by tile, 0 (default) = factor-major */
   GP_TUNE_BALANCE = 5,          /* stream kernel, one large factor: how much more a dispatch round of workgroups takes than the next one, in 1/1000 of
-                                   the mean share (0 = flat split; -1 = automatic, the default: 250 for small shares down to 100 for large ones; a compute unit issues from
-                                   its oldest waves first, csrc/gp_vgicp_shared.hpp) */
+                                   the mean share (0 = flat split .. 1000; -1 = automatic, the default: 150; a skew that would leave an XCD's last round less than a third
+                                   of the mean share is dealt flat; a compute unit issues from its oldest waves first, csrc/gp_vgicp_shared.hpp) */
   GP_TUNE_EFFECTIVE_KERNEL = 6, /* read-only: the family the batch's current table runs (-1 before the first pass) */
   GP_TUNE_XCD_WEIGHT_0 = 8,     /* .. + 7: stream kernel, one large factor: share of XCD x in 1/1000 of the mean share (500..1500); setting any of the eight
                                    replaces the library's measured table (the others then count as 1000) */
@@ -891,6 +891,11 @@ int gp_debug_expand_rigid(const double sums[32], const double pose[16], gp_linea
  * to its workgroups for a factor of n points and a GP_TUNE_BALANCE value, in tile-list order (XCD-major); *num_tiles = workgroups of the launch */
 int gp_debug_stream_plan(int n, int skew_permille, const int* xcd_weights_permille /* [8] or NULL = the library's table */, int capacity, int* begin, int* count,
                          int* num_tiles);
+/* ... and with the launch's other inputs, down to the waves: tile_points == 0 = the planned launch of at most max_workgroups (8 .. 1024, GP_TUNE_MAX_WORKGROUPS) workgroups;
+ * tile_points > 0 (a multiple of 256) = the fixed tiles of a factor below the planning threshold, in tile order.  waves (or NULL): [capacity * 4][3] = first point, full
+ * 64-point chunks and tail points of each of the four waves of every workgroup, as the stream kernel splits them */
+int gp_debug_stream_plan_ex(int n, int tile_points, int max_workgroups, int skew_permille, const int* xcd_weights_permille /* [8] or NULL */, int capacity, int* begin,
+                            int* count, long long* waves, int* num_tiles);
 /* host-side check hook (runs without a device): for an explicit shard assignment, *rows_per_shard = rows every rank contributes to the in-place ncclAllGather of a
  * multi-device pass (0: the plan does not allow it -- unequal or non-contiguous shards -- and the pass all-reduces), and send_offset_doubles[k] = where shard k's send
  * buffer starts inside the [F x width] stack, in doubles.  Runs the functions gp_vgicp_multi_batch_* itself uses. */

@@ -103,7 +103,7 @@ def results():
                f"{b['cpu_baseline']['ms_per_linearize']:.0f} ms @{b['cpu_baseline']['cores']} thr |")
     if big and "roofline" in big:
         out.append(f"| the same factor with an 8 M-point source (beyond the Infinity Cache) | 8.0 M | {big['ms_per_linearize']:.4f} | {big['value']:.3g} corr/s | in step {big['roofline']['kernel_ms']*1e3:.1f} µs = "
-                   f"**{big['roofline']['frac']:.3f}** (back to back {big['roofline']['frac_back_to_back']:.3f}) | — | — |")
+                   f"**{big['roofline']['frac']:.3f}** (back to back {big['roofline']['frac_back_to_back']:.3f}) | not run at this size; the same per-lane stream length (65,536 points on 8 workgroups, 31 – 33 chunks per wave) is held to the f64 reference in `tests/test_stream_edges_gpu.py`, its figure in DESIGN.md §2 | — |")
     x = c["C1"]
     out.append(f"| C1: two full kitti_00 scans, k = 10 covariances, 0.5 m | {x['points']/1e3:.1f} k | {x['ms']:.4f} | {x['corr_per_s']:.3g} corr/s | {x['roofline']['kernel_ms']*1e3:.1f} µs back to back, "
                f"{x['roofline']['frac']:.2f} (launch-bound) | {max(v for k, v in x['parity_vs_reference'].items() if k != 'num_inliers_equal'):.1e} | {x['cpu_baseline']['ms']:.2f} ms |")

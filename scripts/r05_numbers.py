@@ -105,7 +105,7 @@ def results():
                f"{b['cpu_baseline']['ms_per_linearize']:.0f} ms @{b['cpu_baseline']['cores']} thr |")
     if big.get("roofline"):
         br = big["roofline"]
-        out.append(f"| the same factor with an 8 M-point source (beyond the Infinity Cache) | 8.0 M | {big['ms_per_linearize']:.4f} | {big['value']:.3g} corr/s | streaming part in step {br['kernel_ms'] * 1e3:.1f} µs = **{br['frac']:.3f}** (back to back {br['frac_back_to_back']:.3f}) | — | — |")
+        out.append(f"| the same factor with an 8 M-point source (beyond the Infinity Cache) | 8.0 M | {big['ms_per_linearize']:.4f} | {big['value']:.3g} corr/s | streaming part in step {br['kernel_ms'] * 1e3:.1f} µs = **{br['frac']:.3f}** (back to back {br['frac_back_to_back']:.3f}) | not run at this size; the same per-lane stream length (65,536 points on 8 workgroups, 31 – 33 chunks per wave) is held to the f64 reference in `tests/test_stream_edges_gpu.py`, its figure in DESIGN.md §2 | — |")
     out.append(f"| C1: two full kitti_00 scans, k = 10 covariances, 0.5 m | {c1['points'] / 1e3:.1f} k | {c1['ms']:.4f} | {c1['corr_per_s']:.3g} corr/s | {c1['roofline']['kernel_ms'] * 1e3:.1f} µs back to back, {c1['roofline']['frac']:.2f} (launch-bound) | {pc1:.1e} | "
                f"{c1['cpu_baseline']['ms']:.2f} ms |")
     out.append(f"| C3: 256-factor submap graph, 1.0 m, ONE batched call | {c3['points'] / 1e6:.2f} M | {c3['ms']:.4f} (with copy {c3['ms_with_copy']:.4f}) | {c3['corr_per_s']:.3g} corr/s | {c3['roofline']['kernel_ms'] * 1e3:.1f} µs, {c3['roofline']['frac']:.2f} algorithmic "

@@ -99,7 +99,7 @@ def results():
     if big.get("roofline"):
         br = big["roofline"]
         out.append(f"| the same factor with an 8 M-point source (beyond the Infinity Cache) | 8.0 M | {rng([x['legs'].get('big_source_ms') for x in rs], '{:.4f}')} | {big['value']:.3g} corr/s | streaming part in step {br['kernel_ms'] * 1e3:.1f} µs = "
-                   f"**{rng([x['legs'].get('big_source_frac') for x in rs], '{:.3f}')}** (back to back {br['frac_back_to_back']:.3f}) | = headline kernel | — |")
+                   f"**{rng([x['legs'].get('big_source_frac') for x in rs], '{:.3f}')}** (back to back {br['frac_back_to_back']:.3f}) | not run at this size; the same per-lane stream length (65,536 points on 8 workgroups, 31 – 33 chunks per wave) is held to the f64 reference in `tests/test_stream_edges_gpu.py`, its figure in DESIGN.md §2 | — |")
     c1, c3, c5, mb = (cfg.get(k) or {} for k in ("C1", "C3", "C5", "map_build"))
     if c1.get("roofline"):
         pc1 = max(v for k, v in c1["parity_vs_reference"].items() if k != "num_inliers_equal")

@@ -677,7 +677,8 @@ def test_linearity_and_determinism_at_1m(gpu):
 def test_stream_kernel_at_size(gpu, variant, policy, n_src):
     """vgicp_stream_kernel (gp_vgicp_stream.hpp, family 12, default) with the default / the non-temporal / the per-batch policy on the source
     stream, at sizes no fixture reaches: one resident round of 1024 workgroups with 6-7 / 13-16 chunks each (one or two per wave; three or
-    four) and 13 points behind the last full chunk for the per-lane tail.
+    four) and 13 points behind the last full chunk for the per-lane tail.  Every other stream length -- waves of 0, 1, 2, 3 chunks beside longer ones, 16, 32 and 64
+    chunks per wave -- and the other plan shapes: tests/test_stream_edges_gpu.py.
     Against the oracle, plus bit-reproducibility and agreement with the round-2 kernel far below the parity tolerance."""
     from gtsam_points_amd import synthetic
 
