@@ -206,6 +206,7 @@ _SIGNATURES = {
     "gp_loam_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(Linearized6)]),
     "gp_loam_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gp_loam_factor_num_correspondences": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gp_loam_factor_get_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     # a batch of GICP / ICP / LOAM factors with device-resident poses (gp_corr_batch.hip)
     "gp_corr_batch_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -295,6 +295,15 @@ int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, in
   return GP_OK;
 }
 
+int gp_loam_factor_get_correspondences(const gp_loam_factor_t* f, int* edges_host, int* planes_host) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_get_correspondences: null");
+  if (!f->corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_get_correspondences: no correspondences are stored (never linearised)");
+  GP_HIP(hipStreamSynchronize(f->stream));
+  if (edges_host && f->edge && f->edge->n > 0) GP_HIP(hipMemcpy(edges_host, f->edge->corr.as<int>(), sizeof(int) * 2 * (size_t)f->edge->n, hipMemcpyDeviceToHost));
+  if (planes_host && f->plane && f->plane->n > 0) GP_HIP(hipMemcpy(planes_host, f->plane->corr.as<int>(), sizeof(int) * 3 * (size_t)f->plane->n, hipMemcpyDeviceToHost));
+  return GP_OK;
+}
+
 // the record of a combined factor: the edge part's finalised record plus the plane part's, added in that order in f64 as IntegratedLOAMFactor_::evaluate does
 // (:461-472); a factor of one part hands that part's record on
 static void loam_add(const double* edge, const double* plane, double* out, size_t count) {

@@ -379,6 +379,15 @@ class IntegratedLOAMFactorGPU:
         _capi.check(self._lib.gp_loam_factor_num_correspondences(self._h, C.byref(e), C.byref(p)), "gp_loam_factor_num_correspondences")
         return e.value, p.value
 
+    def correspondences(self):
+        """(edges (n, 2) or None, planes (n, 3) or None): the stored correspondences copied to the host, per source point the target indices in ascending order of
+        distance, a row of -1 where the point has none (read-only; for tests and diagnosis)"""
+        out = []
+        for src, K in ((self.source_edges, 2), (self.source_planes, 3)):
+            out.append(None if src is None else np.full((K, src.size()), -1, dtype=np.int32))
+        _capi.check(self._lib.gp_loam_factor_get_correspondences(self._h, *[None if a is None else a.ctypes.data for a in out]), "gp_loam_factor_get_correspondences")
+        return tuple(None if a is None else np.ascontiguousarray(a.T) for a in out)
+
 
 class IntegratedPointToEdgeFactorGPU(IntegratedLOAMFactorGPU):
     """IntegratedPointToEdgeFactor_ (:197-372): the LOAM factor's edge part alone.  set_max_correspondence_distance takes (dist_edge, dist_plane) like the combined

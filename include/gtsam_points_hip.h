@@ -501,6 +501,10 @@ int gp_loam_factor_linearize(gp_loam_factor_t* f, const double pose[16], gp_line
 int gp_loam_factor_compute_error(gp_loam_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
 /* source points that had a correspondence in the last linearise, per part (either pointer may be NULL); 0 before one */
 int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, int* planes);
+/* read-only copy of the stored correspondences (of the last search, behind the validation when it is enabled) to the host, for tests and diagnosis: edges_host
+ * int[2][num_source_edges], planes_host int[3][num_source_planes], slot k of source point i at [k * n + i], every slot -1 where the point has none.  Either pointer
+ * may be NULL; an absent or empty part writes nothing.  Synchronous.  GP_ERROR_INVALID_ARGUMENT before the first linearise / error evaluation. */
+int gp_loam_factor_get_correspondences(const gp_loam_factor_t* f, int* edges_host, int* planes_host);
 
 /* ---- a batch of GICP / ICP / LOAM factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
  * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of

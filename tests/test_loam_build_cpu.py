@@ -38,6 +38,7 @@ def test_loam_entry_points_refuse_bad_arguments_without_a_device():
     assert lib.gp_loam_factor_set_enable_correspondence_validation(None, 1) == INVALID
     assert lib.gp_loam_factor_set_correspondence_update_tolerance(None, 0.1, 0.1) == INVALID
     assert lib.gp_loam_factor_num_correspondences(None, None, None) == INVALID
+    assert lib.gp_loam_factor_get_correspondences(None, None, None) == INVALID
 
 
 def test_batch_create_ex_is_exported_and_refuses_on_the_host():
