@@ -1,4 +1,4 @@
-// gp_damped_step.hpp -- the pieces of the damped step that the dense system (gp_solver.hip) and the block-sparse system (gp_sparse.hip) share: the gather of A and b
+// gp_damped_step.hpp -- the pieces of the damped step that the dense system (gp_solver.hip) and the block-sparse system (gp_sparse.hip, gp_sparse_multi.hpp, gp_sparse_small.hip) share: the gather of A and b
 // out of the factors' gp_linearized6 records, the error sum, the damping, the pivot rule, the host-side contribution lists and the pinned step hand-off.  Both
 // systems call THESE, so a change to the step is made once and the two cannot drift apart.
 #pragma once

@@ -1,5 +1,5 @@
 """Time of the on-device normal-equation build + solve for pose graphs of growing size: the dense blocked LL^T (gp_solver.hip) and
-the block-sparse LL^T over the pose graph (gp_sparse.hip, natural order and nested dissection).
+the block-sparse LL^T over the pose graph (gp_sparse.hip and the gp_sparse_* files beside it, natural order and nested dissection).
 Graphs: `chain` = odometry chain with one fixed pose; `loops` = chain + i -> i+2 and i -> i+7 edges (the round-1 graph)."""
 import json
 import os

@@ -154,3 +154,31 @@ def reference_bucket_lookup(buckets, info, coord):
         if tuple(b[:3]) == tuple(int(c) for c in coord):
             return int(b[3])
     return -1
+
+
+# the graphs of tests/test_solver_gpu.py::test_one_launch_step_is_bit_identical; tests/test_sparse_cpu.py holds them to the forms of the one-launch step they reach
+ONE_LAUNCH_GRAPHS = ["c3:64", "c1:2", "band:16", "band:100", "chain:128", "freechain:40", "isolated", "hub:13"]
+ONE_LAUNCH_ORDERINGS = ["auto", "natural", "nd", "amd", "amd1"]
+
+
+def one_launch_graph(graph):
+    """(kind, P, factor slots) of a graph of ONE_LAUNCH_GRAPHS"""
+    kind, _, num = graph.partition(":")
+    if kind == "c3" or kind == "c1":  # BASELINE configs[2]'s / configs[0]'s graph: pose 0 held
+        n = int(num)
+        pairs = [(i, j) for i in range(n) for j in range(i + 1, min(i + 5, n))]
+        pairs = (pairs + [(j, i) for i, j in pairs])[: 4 * n]
+        return kind, n - 1, [(a - 1, b - 1) for a, b in pairs]
+    if kind == "band":
+        P = int(num)
+        return kind, P, [(-1, 0)] + [(i, i + d) for i in range(P) for d in (1, 2, 5) if i + d < P]
+    if kind == "chain":
+        P = int(num)
+        return kind, P, [(-1, 0)] + [(i, i + 1) for i in range(P - 1)]
+    if kind == "freechain":  # no pose held: more than eight one-column subtrees under the minimum-degree orderings (several batches of lists per level)
+        P = int(num)
+        return kind, P, [(i, i + 1) for i in range(P - 1)]
+    if kind == "hub":  # every pose tied to pose 0: in the natural order its column has P blocks (more than ten: the panel sweep's second pass of 64 rows)
+        P = int(num)
+        return kind, P, [(-1, 0)] + [(0, i) for i in range(1, P)]
+    return kind, 12, [(-1, 0), (0, 1), (1, 2), (-1, 5), (5, 6), (6, 7), (7, 5), (-1, 11), (-1, 3), (3, 4), (-1, 8), (8, 9), (9, 10)]

@@ -3,7 +3,7 @@ DenseLinearSolver::solve restated with numpy on the host as the checker (the ref
 import numpy as np
 import pytest
 
-from helpers import expmap, host_system as _host_system, pose_error
+from helpers import ONE_LAUNCH_GRAPHS, ONE_LAUNCH_ORDERINGS, expmap, host_system as _host_system, one_launch_graph, pose_error
 
 pytestmark = pytest.mark.gpu
 
@@ -317,14 +317,8 @@ def test_step_is_build_download_solve_in_one_call(gpu, kind):
     assert np.abs(x - bh).max() <= 1e-12 * np.abs(bh).max()
 
 
-def _c3_like_slots(n):
-    pairs = [(i, j) for i in range(n) for j in range(i + 1, min(i + 5, n))]
-    pairs = (pairs + [(j, i) for i, j in pairs])[: 4 * n]
-    return [(a - 1, b - 1) for a, b in pairs]  # pose 0 held
-
-
-@pytest.mark.parametrize("ordering", ["auto", "natural", "nd", "amd", "amd1"])
-@pytest.mark.parametrize("graph", ["c3:64", "c1:2", "band:16", "band:100", "chain:128", "freechain:40", "isolated"])
+@pytest.mark.parametrize("ordering", ONE_LAUNCH_ORDERINGS)
+@pytest.mark.parametrize("graph", ONE_LAUNCH_GRAPHS)
 def test_one_launch_step_is_bit_identical(gpu, graph, ordering):
     """a system whose factor fits the LDS of one compute unit runs its damped step as ONE launch (sparse_small_step_kernel: assembly, damping, the levels of the
     block-sparse LL^T, both substitutions, x / b / c / status to the host).  Same operations in the same order as the multi-launch form: x, b, c bit for bit, with every
@@ -332,22 +326,7 @@ def test_one_launch_step_is_bit_identical(gpu, graph, ordering):
     import torch
 
     rng = np.random.default_rng(17)
-    kind, _, num = graph.partition(":")
-    if kind == "c3" or kind == "c1":
-        n = int(num)
-        slots, P = _c3_like_slots(n), n - 1
-    elif kind == "band":
-        P = int(num)
-        slots = [(-1, 0)] + [(i, i + d) for i in range(P) for d in (1, 2, 5) if i + d < P]
-    elif kind == "chain":
-        P = int(num)
-        slots = [(-1, 0)] + [(i, i + 1) for i in range(P - 1)]
-    elif kind == "freechain":  # no pose held: more than eight one-column subtrees under the minimum-degree orderings (several batches of lists per level)
-        P = int(num)
-        slots = [(i, i + 1) for i in range(P - 1)]
-    else:
-        P = 12
-        slots = [(-1, 0), (0, 1), (1, 2), (-1, 5), (5, 6), (6, 7), (7, 5), (-1, 11), (-1, 3), (3, 4), (-1, 8), (8, 9), (9, 10)]
+    kind, P, slots = one_launch_graph(graph)
     rec = _random_records(slots, rng)
     rec_dev = torch.from_numpy(rec).cuda()
     one, multi = gpu.SparseLinearSystemGPU(P, slots, ordering=ordering), gpu.SparseLinearSystemGPU(P, slots, ordering=ordering)

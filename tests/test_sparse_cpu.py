@@ -103,3 +103,48 @@ def test_bad_arguments():
         gpa.sparse_symbolic(4, [(1, 1)], 0)
     with pytest.raises(gpa.GPError):
         gpa.sparse_symbolic(4, [(0, 1)], 7)
+
+
+def _fits_one_launch(P, s):
+    """gp_sparse_symbolic.hip's small_step_lds_bytes restated: factor, vectors, the teams' scratch and the index lists within one compute unit's LDS"""
+    nnz_l, lists = s["nnz_l_blocks"], s["num_lists"]
+    products = sum(w["products"] for w in s["work_lists"])
+    words = (P + 1) + nnz_l + (nnz_l + 1) + 2 * products + (P + 1) + 2 * (nnz_l - P) + (lists + 1) + P + nnz_l + (lists + 1) + 2
+    return P <= 128 and 8 * (36 * nnz_l + 24 * P + 8 * 158) + 4 * words + 64 <= 160 * 1024 - 1024
+
+
+def _column_blocks(P, slots, perm):
+    """blocks per column of L (diagonal included), by dense boolean elimination in the order perm"""
+    ip = np.empty(P, int)
+    ip[perm] = np.arange(P)
+    M = np.eye(P, dtype=bool)
+    for a, b in slots:
+        if a >= 0 and b >= 0:
+            M[ip[a], ip[b]] = M[ip[b], ip[a]] = True
+    for k in range(P):
+        rows = np.nonzero(M[k + 1 :, k])[0] + k + 1
+        M[np.ix_(rows, rows)] = True
+    return np.tril(M).sum(0)
+
+
+def test_one_launch_graphs_reach_every_form_of_the_step():
+    """The one-launch step picks a form per level from the number of work lists in it (up to four: teams of waves; five to eight: lone waves in level 0, lock step above;
+    more than eight: batches of eight), and a panel of more than ten blocks takes a second pass of 64 rows.  The graphs x orderings that
+    test_solver_gpu.py::test_one_launch_step_is_bit_identical runs (those that fit the LDS) reach every one of these, taken together."""
+    from helpers import ONE_LAUNCH_GRAPHS, ONE_LAUNCH_ORDERINGS, one_launch_graph
+
+    reached, widest = set(), 0
+    for graph in ONE_LAUNCH_GRAPHS:
+        _, P, slots = one_launch_graph(graph)
+        for name in ONE_LAUNCH_ORDERINGS:
+            s = gpa.sparse_symbolic(P, slots, gpa.SparseLinearSystemGPU.ORDERINGS[name])
+            if not _fits_one_launch(P, s):
+                continue
+            lists = np.bincount([w["level"] for w in s["work_lists"]], minlength=s["num_levels"])
+            for level, n in enumerate(lists):
+                reached.add(("level 0" if level == 0 else "above", "<= 4" if n <= 4 else ("5-8" if n <= 8 else "> 8")))
+            if lists.max() <= 4:  # every level goes to teams of waves: every column of this factor is swept by small_panel_sweep
+                widest = max(widest, int(_column_blocks(P, slots, s["perm"]).max()))
+    assert {("level 0", "<= 4"), ("level 0", "5-8"), ("above", "<= 4"), ("above", "5-8")} <= reached, reached
+    assert any(n == "> 8" for _, n in reached), reached
+    assert widest > 10, widest
