@@ -207,6 +207,18 @@ _SIGNATURES = {
     "gp_loam_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "gp_loam_factor_num_correspondences": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "gp_loam_factor_get_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # IntensityGradients::estimate and IntegratedColoredGICPFactor_ on a borrowed gp_point_grid (gp_colored_factors.hip)
+    "gp_estimate_intensity_gradients_from_neighbors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
+    "gp_estimate_intensity_gradients": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "gp_colored_gicp_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
+                                                C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_colored_gicp_factor_destroy": (C.c_int, [C.c_void_p]),
+    "gp_colored_gicp_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(Linearized6)]),
+    "gp_colored_gicp_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gp_colored_gicp_factor_set_photometric_term_weight": (C.c_int, [C.c_void_p, C.c_double]),
+    "gp_colored_gicp_factor_set_max_correspondence_distance": (C.c_int, [C.c_void_p, C.c_double]),
+    "gp_colored_gicp_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "gp_colored_gicp_factor_num_correspondences": (C.c_int, [C.c_void_p]),
     # a batch of GICP / ICP / LOAM factors with device-resident poses (gp_corr_batch.hip)
     "gp_corr_batch_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -11,32 +11,9 @@
 // the VGICP factor (gp_device.hpp ACC / ACCG), which goes through the same finalize kernels (gp_vgicp_shared.hpp).  The correspondence pass is its own kernel: with
 // the search inlined the tile kernel held 157 VGPRs, and measured 0.233 against 0.160 ms per linearise (profiles/r02_gicp_split_ab.jsonl).  The stored
 // correspondences are also what the reference's error() evaluates on (it does not search again).
-#include "gp_corr_factors.hpp"
+#include "gp_corr_tile.hpp"
 
 namespace gp {
-
-// One workgroup per tile of `tile_points` points, lane t of 256 takes points t, t + 256, ... of its tile and skips those without a target point within the cut-off
-// (integrated_gicp_factor_impl.hpp:166-170, integrated_icp_factor_impl.hpp:200-202).
-template <int MODE, class TERM>  // MODE_LIN (rigid pose: 29 sums + adjoint finalize), MODE_ERR, MODE_LIN_GENERAL (any 3x3 block: 92 explicit sums)
-__global__ void __launch_bounds__(256) corr_tile_kernel(TERM f, const CorrPoses poses, int n, int tile_points, double* __restrict__ partials, const int* __restrict__ corr) {
-  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
-  const Pose Tl = load_pose(poses.lin);
-  const Pose Te = MODE == MODE_ERR ? load_pose(poses.eval) : Tl;
-  double acc[NREG];
-#pragma unroll
-  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
-  const int begin = blockIdx.x * tile_points;
-  const int end = min(begin + tile_points, n);
-  for (int i = begin + threadIdx.x; i < end; i += 256) {
-    const int c = corr[i];
-    if (c < 0) continue;
-    if constexpr (TERM::kNeighbours == 1)
-      f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
-    else  // (the LOAM terms: corr is int[K][n], slot 0 the anchor)
-      f.template accumulate<MODE>(i, corr + i, (size_t)n, Tl, Te, acc);
-  }
-  store_tile_sums<MODE>(acc, partials);
-}
 
 // validate_correspondences of the LOAM factor over the stored correspondences of one part (gp_corr_factors.hpp: loam_validate_point), one point per lane
 __global__ void __launch_bounds__(256) loam_validate_kernel(const float* __restrict__ target_points, int* __restrict__ corr, int n, int K) {
@@ -52,33 +29,7 @@ __global__ void __launch_bounds__(256) loam_validate_kernel(const float* __restr
 
 // (the handles: gp_corr_factors.hpp)
 
-// One synchronous pass over the stored correspondences.  pose_eval == nullptr: a linearise at pose_lin, out_host is a gp_linearized6; otherwise the error at
-// pose_eval, out_host is a double.  The 29-sum kernel + adjoint finalize is exact only for an orthonormal 3x3 block; any other pose (e.g. built from 6-digit
-// quaternions, src/test/test_matching_cost_factors.cpp:50-55) takes the 92-sum path with the explicit J_s, like the VGICP factor.
-template <class TERM>
-int gp_corr_factor_core::run_pass(const TERM& term, const double* pose_lin, const double* pose_eval, void* out_host) {
-  gp::CorrPoses P;
-  memcpy(P.lin, pose_lin, sizeof(double) * 16);
-  memcpy(P.eval, pose_eval ? pose_eval : pose_lin, sizeof(double) * 16);
-  const bool rigid = gp::pose_is_rigid(pose_lin);
-  if (num_tiles > 0) {
-    if (pose_eval)
-      hipLaunchKernelGGL((gp::corr_tile_kernel<gp::MODE_ERR, TERM>), dim3(num_tiles), dim3(256), 0, stream, term, P, n, tile_points, partials.as<double>(), corr.as<int>());
-    else if (rigid)
-      hipLaunchKernelGGL((gp::corr_tile_kernel<gp::MODE_LIN, TERM>), dim3(num_tiles), dim3(256), 0, stream, term, P, n, tile_points, partials.as<double>(), corr.as<int>());
-    else
-      hipLaunchKernelGGL((gp::corr_tile_kernel<gp::MODE_LIN_GENERAL, TERM>), dim3(num_tiles), dim3(256), 0, stream, term, P, n, tile_points, partials.as<double>(), corr.as<int>());
-    GP_HIP(hipGetLastError());
-  }
-  const gp::DoneFlags done{static_cast<unsigned long long*>(h_done_dev), ++seq};
-  if (pose_eval)
-    GP_TRY(gp::launch_finalize_error_single(stream, partials.as<double>(), num_tiles, reinterpret_cast<double*>(h_out_dev), done));
-  else
-    GP_TRY(gp::launch_finalize_single(stream, nullptr, pose_lin, partials.as<double>(), num_tiles, reinterpret_cast<gp_linearized6*>(h_out_dev), !rigid, done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(h_done.ptr), 1, done.seq, stream, 100 + (long)num_tiles * (long)tile_points / 1000));  // spin budget ~4x the kernel (0.2 ns per point)
-  memcpy(out_host, h_out.ptr, pose_eval ? sizeof(double) : sizeof(gp_linearized6));
-  return GP_OK;
-}
+// (the tile kernel and the synchronous pass over the stored correspondences: gp_corr_tile.hpp)
 
 int gp_icp_factor::run_pass(const double* pose_lin, const double* pose_eval, void* out_host) {
   if (plane) return gp_corr_factor_core::run_pass(gp::IcpTerm<true>{desc}, pose_lin, pose_eval, out_host);
@@ -97,21 +48,6 @@ int gp_loam_part::validate() {
   return GP_OK;
 }
 
-// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137, integrated_loam_factor_impl.hpp:81-88, :236-243) on two column-major 4x4 poses:
-// diff = delta^-1 * last (the isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
-static bool keep_correspondences(bool corr_valid, const double* last, double tol_rot, double tol_trans, const double* delta) {
-  if (!corr_valid || !(tol_trans > 0.0 || tol_rot > 0.0)) return false;
-  double D[3][3], t[3];
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) D[r][c] = delta[4 * r] * last[4 * c] + delta[4 * r + 1] * last[4 * c + 1] + delta[4 * r + 2] * last[4 * c + 2];
-    t[r] = delta[4 * r] * (last[12] - delta[12]) + delta[4 * r + 1] * (last[13] - delta[13]) + delta[4 * r + 2] * (last[14] - delta[14]);
-  }
-  // angle in [0, pi] from sin (the skew part) and cos (the trace): what Eigen::AngleAxisd(diff.linear()).angle() gives for a rotation
-  const double sx = 0.5 * (D[2][1] - D[1][2]), sy = 0.5 * (D[0][2] - D[2][0]), sz = 0.5 * (D[1][0] - D[0][1]);
-  const double diff_rot = std::atan2(std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0));
-  const double diff_trans = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  return diff_rot < tol_rot && diff_trans < tol_trans;
-}
 static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta) { return keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, delta); }
 
 // ---- LOAM factor: what the entry points share ----

@@ -289,10 +289,26 @@ struct gp_corr_factor_core {
   // the correspondence pass of the LOAM parts at pose_lin (n > 0): the k nearest into corr (int[k][n], allocated by the part); the pose is kept by the factor
   int search_k(int k, const double* pose_lin) { return gp::launch_nearest_k_correspondences(grid, points, n, k, pose_lin, max_sq_dist, corr.as<int>(), stream); }
 
-  // One synchronous pass over the stored correspondences (gp_corr_factors.hip, which alone instantiates it).
+  // One synchronous pass over the stored correspondences (gp_corr_tile.hpp: defined there for the units that instantiate it with their terms).
   template <class TERM>
   int run_pass(const TERM& term, const double* pose_lin, const double* pose_eval, void* out_host);
 };
+
+// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137, integrated_loam_factor_impl.hpp:81-88, :236-243) on two column-major 4x4 poses:
+// diff = delta^-1 * last (the isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
+inline bool keep_correspondences(bool corr_valid, const double* last, double tol_rot, double tol_trans, const double* delta) {
+  if (!corr_valid || !(tol_trans > 0.0 || tol_rot > 0.0)) return false;
+  double D[3][3], t[3];
+  for (int r = 0; r < 3; r++) {
+    for (int c = 0; c < 3; c++) D[r][c] = delta[4 * r] * last[4 * c] + delta[4 * r + 1] * last[4 * c + 1] + delta[4 * r + 2] * last[4 * c + 2];
+    t[r] = delta[4 * r] * (last[12] - delta[12]) + delta[4 * r + 1] * (last[13] - delta[13]) + delta[4 * r + 2] * (last[14] - delta[14]);
+  }
+  // angle in [0, pi] from sin (the skew part) and cos (the trace): what Eigen::AngleAxisd(diff.linear()).angle() gives for a rotation
+  const double sx = 0.5 * (D[2][1] - D[1][2]), sy = 0.5 * (D[0][2] - D[2][0]), sz = 0.5 * (D[1][0] - D[0][1]);
+  const double diff_rot = std::atan2(std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0));
+  const double diff_trans = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+  return diff_rot < tol_rot && diff_trans < tol_trans;
+}
 
 struct gp_gicp_factor : gp_corr_factor_core {
   gp_point_grid* own_grid = nullptr;  // OWNED: the factor's target 1-NN structure

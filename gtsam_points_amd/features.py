@@ -7,6 +7,8 @@
   IntegratedICPFactorGPU    <- factors/integrated_icp_factor.hpp (point-to-point / point-to-plane; CPU-only upstream), on a shared KdTreeGPU
   IntegratedPointToEdgeFactorGPU / IntegratedPointToPlaneFactorGPU / IntegratedLOAMFactorGPU
                             <- factors/integrated_loam_factor.hpp (CPU-only upstream), on the 2 / 3 nearest points of shared KdTreeGPUs
+  estimate_intensity_gradients_gpu  <- factors/intensity_gradients.hpp:IntensityGradients::estimate (CPU-only upstream) -> IntensityGradientsGPU
+  IntegratedColoredGICPFactorGPU    <- factors/integrated_colored_gicp_factor.hpp (CPU-only upstream), on a shared KdTreeGPU and the target's intensity gradients
   CorrespondenceFactorBatchGPU  any number of the factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
 """
 import ctypes as C
@@ -276,6 +278,145 @@ def IntegratedPointToPlaneICPFactorGPU(target_key, source_key, target, source, t
     """IntegratedPointToPlaneICPFactor_ (factors/integrated_icp_factor.hpp): the ICP factor with use_point_to_plane = true"""
     return IntegratedICPFactorGPU(target_key, source_key, target, source, target_tree=target_tree, use_point_to_plane=True,
                                   max_correspondence_distance=max_correspondence_distance, stream=stream, _fixed_target_pose=_fixed_target_pose)
+
+
+class IntensityGradientsGPU:
+    """IntensityGradients (factors/intensity_gradients.hpp): per-point intensity gradients in the tangent plane, gradients_gpu float [N][3] on the device"""
+
+    def __init__(self, gradients_gpu, num_short=None):
+        self.gradients_gpu = gradients_gpu
+        self.num_short = num_short  # points with fewer than k neighbours, when the estimate searched for itself
+
+    def size(self):
+        return int(self.gradients_gpu.shape[0])
+
+    def download(self):
+        return self.gradients_gpu.cpu().numpy()
+
+
+def estimate_intensity_gradients_gpu(frame: PointCloudGPU, k_neighbors=10, neighbors=None, k_photo_neighbors=None, cell_size=0.0, stream=None):
+    """IntensityGradients::estimate (factors/intensity_gradients.cpp:20-133) -> IntensityGradientsGPU.
+    neighbors=None: one k-NN search with k_neighbors (:71-133); points with fewer neighbours get (0, 0, 0) and are counted in the result's num_short.
+    neighbors: an (N, k) int table (numpy or a device tensor, -1 where a point has fewer), of which the first k_photo_neighbors slots are used (all by default) (:20-69)."""
+    import torch
+
+    if frame.points_gpu is None or frame.normals_gpu is None or frame.intensities_gpu is None:
+        raise _capi.GPError("error: input frame doesn't have required attributes for intensity gradient estimation!!")  # :21-24
+    lib = _capi.load()
+    n = frame.size()
+    grads = torch.empty((n, 3), dtype=torch.float32, device=frame.device)
+    GaussianVoxelMapGPU._sync_torch(frame)
+    args = (frame.ptr(frame.points_gpu), frame.ptr(frame.normals_gpu), frame.ptr(frame.intensities_gpu), n)
+    out = IntensityGradientsGPU(grads)
+    if n == 0:
+        return out
+    if neighbors is None:
+        short = C.c_int(0)
+        _capi.check(lib.gp_estimate_intensity_gradients(*args, int(k_neighbors), float(cell_size), C.c_void_p(grads.data_ptr()), C.byref(short), stream),
+                    "gp_estimate_intensity_gradients")
+        out.num_short = short.value
+        return out
+    table = neighbors if isinstance(neighbors, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(neighbors, dtype=np.int32))
+    table = table.to(device=frame.device, dtype=torch.int32).reshape(n, -1).contiguous()
+    k = int(table.shape[1])
+    torch.cuda.current_stream(frame.device).synchronize()  # (the table's upload)
+    _capi.check(lib.gp_estimate_intensity_gradients_from_neighbors(*args, C.c_void_p(table.data_ptr()), k, int(k if k_photo_neighbors is None else k_photo_neighbors),
+                                                                   C.c_void_p(grads.data_ptr()), stream), "gp_estimate_intensity_gradients_from_neighbors")
+    _capi.check(lib.gp_stream_synchronize(stream), "sync")  # (the C entry is asynchronous; the table goes back to torch here)
+    return out
+
+
+class IntegratedColoredGICPFactorGPU:
+    """Colored GICP matching-cost factor on the GPU (IntegratedColoredGICPFactor_, impl/integrated_colored_gicp_factor_impl.hpp): GICP's geometric term on the 1-NN
+    correspondences within max_correspondence_distance (default 1 m, :28) weighted 1 - photometric_term_weight, plus the photometric residual
+    I_B - I_A - (P g_B) . (mu_B - T p_A) in the target's tangent plane weighted photometric_term_weight (default 0.25, :29).
+    target_tree: a KdTreeGPU over `target` that many factors may share; None builds one.  target_gradients: an IntensityGradientsGPU of `target`; None estimates
+    it with k = 10.  The search is the 3-D one (the reference's optional 4-D IntensityKdTree is not provided)."""
+
+    def __init__(self, target_key, source_key, target: PointCloudGPU, source: PointCloudGPU, target_tree=None, target_gradients=None, max_correspondence_distance=1.0,
+                 photometric_term_weight=0.25, stream=None, _fixed_target_pose=None):
+        self._lib = _capi.load()
+        self.is_binary = _fixed_target_pose is None
+        self._keys = [target_key, source_key] if self.is_binary else [source_key]
+        self.fixed_target_pose = np.eye(4) if self.is_binary else np.asarray(_fixed_target_pose, dtype=np.float64)
+        if target.points_gpu is None or target.covs_gpu is None or target.normals_gpu is None or target.intensities_gpu is None:
+            raise _capi.GPError("error: target frame doesn't have required attributes for colored_gicp")  # :37-40
+        if source.points_gpu is None or source.covs_gpu is None or source.intensities_gpu is None:
+            raise _capi.GPError("error: source frame doesn't have required attributes for colored_gicp")  # :42-45
+        self.target, self.source = target, source
+        self.target_tree = target_tree if target_tree is not None else KdTreeGPU(target, stream=stream)
+        if self.target_tree.frame.points_gpu is None or self.target_tree.frame.points_gpu.data_ptr() != target.points_gpu.data_ptr():
+            raise _capi.GPError("error: target_tree was not built over the target frame's points")
+        self.target_gradients = target_gradients if target_gradients is not None else estimate_intensity_gradients_gpu(target, 10, stream=stream)
+        if self.target_gradients.size() != target.size():
+            raise _capi.GPError("error: target_gradients does not have one gradient per target point")
+        GaussianVoxelMapGPU._sync_torch(target)
+        GaussianVoxelMapGPU._sync_torch(source)
+        h = C.c_void_p()
+        _capi.check(
+            self._lib.gp_colored_gicp_factor_create(self.target_tree._h, target.ptr(target.points_gpu), target.ptr(target.covs_gpu), target.ptr(target.normals_gpu),
+                                                    target.ptr(target.intensities_gpu), C.c_void_p(self.target_gradients.gradients_gpu.data_ptr()), target.size(),
+                                                    source.ptr(source.points_gpu), source.ptr(source.covs_gpu), source.ptr(source.intensities_gpu), source.size(),
+                                                    float(max_correspondence_distance) ** 2, float(photometric_term_weight), stream, C.byref(h)),
+            "gp_colored_gicp_factor_create",
+        )
+        self._h = h
+        self.stream = stream
+        self.linearization_point = np.eye(4)
+        self._num_inliers = 0
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_colored_gicp_factor_destroy(self._h)  # (before the tree and the gradients it borrows: both are still referenced here)
+            self._h = None
+
+    def keys(self):
+        return self._keys
+
+    def set_photometric_term_weight(self, weight):
+        _capi.check(self._lib.gp_colored_gicp_factor_set_photometric_term_weight(self._h, float(weight)), "gp_colored_gicp_factor_set_photometric_term_weight")
+
+    def set_max_correspondence_distance(self, dist):
+        _capi.check(self._lib.gp_colored_gicp_factor_set_max_correspondence_distance(self._h, float(dist)), "gp_colored_gicp_factor_set_max_correspondence_distance")
+
+    def set_correspondence_update_tolerance(self, angle, trans):
+        """keep the stored correspondences while a linearisation pose stays within (angle [rad], trans [m]) of the pose they were searched at (:101-114)"""
+        _capi.check(self._lib.gp_colored_gicp_factor_set_correspondence_update_tolerance(self._h, float(angle), float(trans)),
+                    "gp_colored_gicp_factor_set_correspondence_update_tolerance")
+
+    def calc_delta(self, values):
+        if not self.is_binary:
+            return pose_inverse(self.fixed_target_pose) @ np.asarray(values[self._keys[0]], dtype=np.float64)
+        return pose_inverse(values[self._keys[0]]) @ np.asarray(values[self._keys[1]], dtype=np.float64)
+
+    def linearize_delta(self, delta):
+        rec = _capi.Linearized6()
+        _capi.check(self._lib.gp_colored_gicp_factor_linearize(self._h, _pose16(delta), C.byref(rec)), "gp_colored_gicp_factor_linearize")
+        l = LinearizedSystem6(rec)
+        self._num_inliers = l.num_inliers
+        self.linearization_point = np.asarray(delta, dtype=np.float64)
+        self._linearized = True
+        return l
+
+    def linearize(self, values):
+        l = self.linearize_delta(self.calc_delta(values))
+        if self.is_binary:
+            return HessianFactor(self._keys, {(0, 0): l.H_target, (0, 1): l.H_target_source, (1, 1): l.H_source}, [-l.b_target, -l.b_source], l.error)
+        return HessianFactor(self._keys, {(0, 0): l.H_source}, [-l.b_source], l.error)
+
+    def error(self, values):
+        """evaluate(delta) on the stored correspondences; without any they are computed at `delta` itself first (:170-172)"""
+        delta = self.calc_delta(values)
+        if not getattr(self, "_linearized", False):
+            self.linearization_point = np.asarray(delta, dtype=np.float64)
+            self._linearized = True
+        out = C.c_double()
+        _capi.check(self._lib.gp_colored_gicp_factor_compute_error(self._h, _pose16(self.linearization_point), _pose16(delta), C.byref(out)),
+                    "gp_colored_gicp_factor_compute_error")
+        return out.value
+
+    def num_inliers(self):
+        return self._num_inliers
 
 
 class IntegratedLOAMFactorGPU:

@@ -506,6 +506,49 @@ int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, in
  * may be NULL; an absent or empty part writes nothing.  Synchronous.  GP_ERROR_INVALID_ARGUMENT before the first linearise / error evaluation. */
 int gp_loam_factor_get_correspondences(const gp_loam_factor_t* f, int* edges_host, int* planes_host);
 
+/* IntensityGradients::estimate (factors/intensity_gradients.cpp:20-133): per point i with normal n and intensity I, over the slots j = 1 .. k-1 of its k-NN list
+ * (slot 0 is the point itself and is skipped, :54, :100): row 0 of A is n with b_0 = 0 (:50-51, :96-97), row j is (p_j - ((p_j - p) . n) n) - p with
+ * b_j = I_j - I (:58-60, :104-106); H = A^T A, e = A^T b, g = H^-1 e (:63-65, :109-111).  f64 on the f32 inputs, the closed-form cofactor inverse, rounded once at
+ * the store into gradients_dev float[n][3].  A singular H is NOT guarded, as in the reference: its non-finite values are stored and the call returns GP_OK.
+ * _from_neighbors is the overload on a given neighbour table (:20-69): neighbors_dev int[n][k], of which the first k_photo slots are used, 1 <= k_photo <= k
+ * (:32-35).  A point with a slot among those that is no point index (the -1 padding of gp_knn_search; anything outside [0, n)) gets (0, 0, 0).  Asynchronous.
+ * gp_estimate_intensity_gradients (:71-133) builds a search structure, runs gp_knn_search (1 <= k <= 32) into a temporary table and takes all k slots:
+ * cell_size <= 0 picks 0.25 m and *num_short (may be NULL) is the number of points with fewer than k neighbours, as for gp_estimate_covariances; those points get
+ * (0, 0, 0).  Synchronous.  Both refuse a NULL array with GP_ERROR_INVALID_ARGUMENT before any device work.
+ * The reference's third entry (:135-242: normals, covariances and gradients from one search) is not provided: it turns a normal round at n . p > 0, a rule
+ * gp_estimate_normals_* (p . n > 1) does not share. */
+int gp_estimate_intensity_gradients_from_neighbors(const float* points_dev, const float* normals_dev, const float* intensities_dev, int num_points,
+                                                   const int* neighbors_dev, int k, int k_photo, float* gradients_dev, gp_stream_t stream);
+int gp_estimate_intensity_gradients(const float* points_dev, const float* normals_dev, const float* intensities_dev, int num_points, int k, double cell_size,
+                                    float* gradients_dev, int* num_short, gp_stream_t stream);
+
+/* IntegratedColoredGICPFactor_ (factors/integrated_colored_gicp_factor.hpp, impl/integrated_colored_gicp_factor_impl.hpp) on the 1-NN correspondences of T_lin p
+ * with squared distance < max (:119-129; the 3-D search of the other factors -- the reference's optional 4-D IntensityKdTree is not provided).  With q = T p_A,
+ * d = mu_B - q, P = I - n_B n_B^T and u = P g_B (g_B the target's intensity gradient, :236-241):
+ *   geometric    d with M_g = (C_B + R C_A R^T)^-1 taken at the LINEARISATION pose, as update_correspondences stores it (:134-138)
+ *   photometric  r_p = I_B - I_A - u . d (:207-209)
+ *   w_p = photometric_term_weight (default 0.25 upstream, :29), w_g = 1 - w_p (:174)
+ *   error = sum w_g d^T M_g d + w_p r_p^2 (:204, :211; no 1/2), H = sum J^T M J with M = w_g M_g + w_p u u^T (:229-231, :246-248),
+ *   b = sum J^T w with w = w_g M_g d - w_p r_p u (:232-233, :249-250), J_t = [-[q]x, I], J_s = [R [p]x, -R], R the pose's 3x3 block as given.
+ *   (The reference writes q - mu_B and J = [[q]x, -I], :203, :217-223: the products are the same.)
+ * `grid` is BORROWED, as for gp_icp_factor_create.  create returns GP_ERROR_INVALID_ARGUMENT, before any device work, for a NULL grid or array and for a weight
+ * outside [0, 1].  linearize / compute_error / set_correspondence_update_tolerance / num_correspondences have the semantics of their gp_icp_factor_* namesakes:
+ * compute_error evaluates on the stored correspondences when pose_lin is bit for bit the pose of the last linearise or search.  set_max_correspondence_distance
+ * takes a DISTANCE (squared inside; must be positive) and leaves stored correspondences alone.  Every entry point refuses a NULL handle on the host.  Two
+ * linearises at one pose are bit-identical. */
+typedef struct gp_colored_gicp_factor gp_colored_gicp_factor_t;
+int gp_colored_gicp_factor_create(const gp_point_grid_t* grid, const float* target_points_dev, const float* target_covs_dev, const float* target_normals_dev,
+                                  const float* target_intensities_dev, const float* target_gradients_dev, int num_target, const float* points_dev,
+                                  const float* covs_dev, const float* intensities_dev, int num_points, double max_correspondence_distance_sq,
+                                  double photometric_term_weight, gp_stream_t stream, gp_colored_gicp_factor_t** out);
+int gp_colored_gicp_factor_destroy(gp_colored_gicp_factor_t* f); /* leaves the grid alone */
+int gp_colored_gicp_factor_linearize(gp_colored_gicp_factor_t* f, const double pose[16], gp_linearized6* out_host);
+int gp_colored_gicp_factor_compute_error(gp_colored_gicp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
+int gp_colored_gicp_factor_set_photometric_term_weight(gp_colored_gicp_factor_t* f, double weight);
+int gp_colored_gicp_factor_set_max_correspondence_distance(gp_colored_gicp_factor_t* f, double dist);
+int gp_colored_gicp_factor_set_correspondence_update_tolerance(gp_colored_gicp_factor_t* f, double angle, double trans);
+int gp_colored_gicp_factor_num_correspondences(const gp_colored_gicp_factor_t* f);
+
 /* ---- a batch of GICP / ICP / LOAM factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
  * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of
  * launches that does not depend on their count -- one search launch, one tile launch per factor kind present (GICP, ICP point-to-point, ICP point-to-plane), one
