@@ -6,6 +6,8 @@ numpy, f64 on the f32 inputs.  A helper, not a test.
                                             closed-form cofactor inverse (Eigen's 3x3 inverse).  The rows are summed one after the other in slot order
                                             (reverse=True: from the last slot down -- what two correct f64 implementations may differ by).  A point with a -1
                                             among its first k_photo slots gets (0, 0, 0).  Returns (g (N,3), cond(H) (N,); inf where there is no H)
+                                            dtype: the float type every operation and every sum runs in (f64; np.longdouble for precision checks)
+  gradient_systems(...)                     the same up to the solve: (rows with a full list, H, e, rho = the largest |a_j| of each row)
   grad_H_cond(..., i)                       cond(H) of one point
   ColoredGICPFactorRef
     update_correspondences(delta) :101-140  the tolerance rule, a brute-force 1-NN of T p among the target points (icp_ref.nearest_two: sq_dist < max), and
@@ -31,28 +33,31 @@ def _f32_as_f64(a, shape):
 
 
 def inverse_sym3(H):
-    """the cofactor inverse of symmetric 3x3 matrices (N,3,3), from the upper triangle"""
+    """the cofactor inverse of symmetric 3x3 matrices (N,3,3), from the upper triangle, in H's own float type"""
     c00, c01, c02, c11, c12, c22 = H[:, 0, 0], H[:, 0, 1], H[:, 0, 2], H[:, 1, 1], H[:, 1, 2], H[:, 2, 2]
     i00 = c11 * c22 - c12 * c12
     i01 = c02 * c12 - c01 * c22
     i02 = c01 * c12 - c02 * c11
     with np.errstate(divide="ignore", invalid="ignore"):
-        inv = 1.0 / (c00 * i00 + c01 * i01 + c02 * i02)
+        inv = H.dtype.type(1.0) / (c00 * i00 + c01 * i01 + c02 * i02)
         m = np.stack([i00 * inv, i01 * inv, i02 * inv, (c00 * c22 - c02 * c02) * inv, (c01 * c02 - c00 * c12) * inv, (c00 * c11 - c01 * c01) * inv], axis=1)
     return m[:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(-1, 3, 3)
 
 
-def gradient_systems(points, normals, intensities, neighbors, k_photo=None, reverse=False, as_given=False):
-    """(rows with a full neighbour list, H (M,3,3), e (M,3)) of those rows.  as_given: the inputs are f64 and are not rounded to f32 first (exact test inputs)"""
+def gradient_systems(points, normals, intensities, neighbors, k_photo=None, reverse=False, as_given=False, dtype=np.float64):
+    """(rows with a full neighbour list, H (M,3,3), e (M,3), rho (M,) f64: the largest |a_j|_2 among a row's neighbour rows) of those rows.  as_given: the inputs
+    are f64 and are not rounded to f32 first (exact test inputs).  dtype: the float type every operation and every sum runs in (np.longdouble for the precision
+    check of tests/test_colored_domain_ref_cpu.py)"""
     read = (lambda a, shape: np.asarray(a, dtype=np.float64).reshape(shape)) if as_given else _f32_as_f64
-    p, n, I = read(points, (-1, 3)), read(normals, (-1, 3)), read(intensities, (-1,))
+    p, n, I = (read(a, shape).astype(dtype) for a, shape in ((points, (-1, 3)), (normals, (-1, 3)), (intensities, (-1,))))
     nb = np.asarray(neighbors, dtype=np.int64).reshape(len(p), -1)
     k_photo = nb.shape[1] if k_photo is None else int(k_photo)
     assert 1 <= k_photo <= nb.shape[1]  # :32-35
     rows = np.flatnonzero((nb[:, :k_photo] >= 0).all(axis=1))
     p0, n0, I0 = p[rows], n[rows], I[rows]
     H = n0[:, :, None] * n0[:, None, :]  # :50-51
-    e = np.zeros((len(rows), 3))
+    e = np.zeros((len(rows), 3), dtype=dtype)
+    rho = np.zeros(len(rows))
     slots = range(1, k_photo)
     for j in reversed(slots) if reverse else slots:  # :54-61
         t = nb[rows, j]
@@ -60,22 +65,33 @@ def gradient_systems(points, normals, intensities, neighbors, k_photo=None, reve
         a = (p[t] - along[:, None] * n0) - p0
         H = H + a[:, :, None] * a[:, None, :]
         e = e + a * (I[t] - I0)[:, None]
-    return rows, H, e
+        rho = np.maximum(rho, np.sqrt((a * a).sum(axis=1)).astype(np.float64))
+    return rows, H, e, rho
 
 
-def intensity_gradients(points, normals, intensities, neighbors, k_photo=None, reverse=False, as_given=False):
-    rows, H, e = gradient_systems(points, normals, intensities, neighbors, k_photo, reverse, as_given)
+def intensity_gradients(points, normals, intensities, neighbors, k_photo=None, reverse=False, as_given=False, dtype=np.float64):
+    """(g (N,3) in `dtype`, cond(H) (N,) f64 of the f64 rounding of H; inf where there is no H)"""
+    rows, H, e, _ = gradient_systems(points, normals, intensities, neighbors, k_photo, reverse, as_given, dtype)
     count = len(np.asarray(points).reshape(-1, 3))
-    g, cond = np.zeros((count, 3)), np.full(count, np.inf)
+    g, cond = np.zeros((count, 3), dtype=dtype), np.full(count, np.inf)
     if len(rows):
-        g[rows] = np.einsum("nij,nj->ni", inverse_sym3(H), e)  # :63-65
         with np.errstate(all="ignore"):
-            cond[rows] = np.linalg.cond(H)
+            g[rows] = np.einsum("nij,nj->ni", inverse_sym3(H), e)  # :63-65
+            cond[rows] = _cond(H.astype(np.float64))
     return g, cond
 
 
+def _cond(H):
+    """2-norm condition numbers of (M,3,3) matrices; inf for those with a non-finite entry (numpy.linalg refuses them)"""
+    out = np.full(len(H), np.inf)
+    ok = np.isfinite(H).all(axis=(1, 2))
+    if ok.any():
+        out[ok] = np.linalg.cond(H[ok])
+    return out
+
+
 def grad_H_cond(points, normals, intensities, neighbors, i, k_photo=None):
-    rows, H, _ = gradient_systems(points, normals, intensities, neighbors, k_photo)
+    rows, H, _, _ = gradient_systems(points, normals, intensities, neighbors, k_photo)
     at = np.flatnonzero(rows == i)
     return float(np.linalg.cond(H[at[0]])) if len(at) else float("inf")
 
