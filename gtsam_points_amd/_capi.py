@@ -219,6 +219,17 @@ _SIGNATURES = {
     "gp_colored_gicp_factor_set_max_correspondence_distance": (C.c_int, [C.c_void_p, C.c_double]),
     "gp_colored_gicp_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "gp_colored_gicp_factor_num_correspondences": (C.c_int, [C.c_void_p]),
+    # IntegratedCT_ICPFactor_ / IntegratedCT_GICPFactor_ on a borrowed gp_point_grid (gp_ct_factors.hip)
+    "gp_ct_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
+                                      C.POINTER(C.c_void_p)]),
+    "gp_ct_factor_destroy": (C.c_int, [C.c_void_p]),
+    "gp_ct_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(Linearized6)]),
+    "gp_ct_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gp_ct_factor_deskew": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int, C.c_void_p]),
+    "gp_ct_factor_num_time_bins": (C.c_int, [C.c_void_p]),
+    "gp_ct_factor_time_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ct_factor_pose_table": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gp_ct_factor_correspondences": (C.c_int, [C.c_void_p, C.c_void_p]),
     # a batch of GICP / ICP / LOAM factors with device-resident poses (gp_corr_batch.hip)
     "gp_corr_batch_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),

@@ -9,6 +9,8 @@
                             <- factors/integrated_loam_factor.hpp (CPU-only upstream), on the 2 / 3 nearest points of shared KdTreeGPUs
   estimate_intensity_gradients_gpu  <- factors/intensity_gradients.hpp:IntensityGradients::estimate (CPU-only upstream) -> IntensityGradientsGPU
   IntegratedColoredGICPFactorGPU    <- factors/integrated_colored_gicp_factor.hpp (CPU-only upstream), on a shared KdTreeGPU and the target's intensity gradients
+  IntegratedCTICPFactorGPU / IntegratedCTGICPFactorGPU
+                            <- factors/integrated_ct_icp_factor.hpp, integrated_ct_gicp_factor.hpp (CPU-only upstream): two pose keys, one pose per time stamp
   CorrespondenceFactorBatchGPU  any number of the factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
 """
 import ctypes as C
@@ -417,6 +419,117 @@ class IntegratedColoredGICPFactorGPU:
 
     def num_inliers(self):
         return self._num_inliers
+
+
+class IntegratedCTICPFactorGPU:
+    """Continuous-time ICP factor on the GPU (IntegratedCT_ICPFactor_, impl/integrated_ct_icp_factor_impl.hpp): the source was scanned while the sensor moved from
+    the pose of source_t0_key to that of source_t1_key; every point is transformed by the pose interpolated at its own time stamp (source.times_gpu, grouped into
+    bins 1e-3 apart, :41-55) and matched to its nearest target point within max_correspondence_distance (default 1 m, :27).  The residual is the scalar
+    point-to-plane distance on the target's normals.  target_tree: a KdTreeGPU over `target` that many factors may share; None builds one and holds it (:57-61)."""
+
+    _KIND = 0
+
+    def __init__(self, source_t0_key, source_t1_key, target: PointCloudGPU, source: PointCloudGPU, target_tree=None, max_correspondence_distance=1.0, stream=None):
+        self._lib = _capi.load()
+        self._keys = [source_t0_key, source_t1_key]
+        if target.points_gpu is None:
+            raise _capi.GPError("error: target frame doesn't have required attributes for ct_icp")  # :31-34
+        if source.points_gpu is None or source.times_gpu is None:
+            raise _capi.GPError("error: source frame doesn't have required attributes for ct_icp")  # :36-39
+        self._check_attributes(target, source)
+        self.target, self.source = target, source
+        self.target_tree = target_tree if target_tree is not None else KdTreeGPU(target, stream=stream)
+        if self.target_tree.frame.points_gpu is None or self.target_tree.frame.points_gpu.data_ptr() != target.points_gpu.data_ptr():
+            raise _capi.GPError("error: target_tree was not built over the target frame's points")
+        GaussianVoxelMapGPU._sync_torch(target)
+        GaussianVoxelMapGPU._sync_torch(source)
+        gicp = self._KIND == 1
+        h = C.c_void_p()
+        _capi.check(
+            self._lib.gp_ct_factor_create(self.target_tree._h, target.ptr(target.points_gpu), None if gicp else target.ptr(target.normals_gpu),
+                                          target.ptr(target.covs_gpu) if gicp else None, target.size(), source.ptr(source.points_gpu),
+                                          source.ptr(source.covs_gpu) if gicp else None, source.ptr(source.times_gpu), source.size(),
+                                          float(max_correspondence_distance) ** 2, self._KIND, stream, C.byref(h)),
+            "gp_ct_factor_create",
+        )
+        self._h = h
+        self.stream = stream
+        self._num_inliers = 0
+
+    @staticmethod
+    def _check_attributes(target, source):
+        if target.normals_gpu is None:
+            raise _capi.GPError("error: target cloud doesn't have normals!!")  # (the reference aborts with this at the first linearise, :133-136)
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._lib.gp_ct_factor_destroy(self._h)  # (before the tree it borrows: self.target_tree is still referenced here)
+            self._h = None
+
+    def keys(self):
+        return self._keys
+
+    def _poses(self, values):
+        return _pose16(values[self._keys[0]]), _pose16(values[self._keys[1]])
+
+    def linearize(self, values):
+        """update_poses + update_correspondences + the sums -> HessianFactor(k0, k1, H_00, H_01, -b_0, H_11, -b_1, error) (:132-199)"""
+        rec = _capi.Linearized6()
+        _capi.check(self._lib.gp_ct_factor_linearize(self._h, *self._poses(values), C.byref(rec)), "gp_ct_factor_linearize")
+        l = LinearizedSystem6(rec)
+        self._num_inliers = l.num_inliers
+        return HessianFactor(self._keys, {(0, 0): l.H_target, (0, 1): l.H_target_source, (1, 1): l.H_source}, [-l.b_target, -l.b_source], l.error)
+
+    def error(self, values):
+        """the error at `values` on the stored correspondences; without any they are searched at `values` first (:92-96)"""
+        out = C.c_double()
+        _capi.check(self._lib.gp_ct_factor_compute_error(self._h, *self._poses(values), C.byref(out)), "gp_ct_factor_compute_error")
+        return out.value
+
+    def num_inliers(self):
+        return self._num_inliers
+
+    def time_table(self):
+        """(normalised time of every bin float64 [bins], bin of every source point int32 [n])"""
+        table = np.zeros(self._lib.gp_ct_factor_num_time_bins(self._h), dtype=np.float64)
+        indices = np.zeros(self.source.size(), dtype=np.int32)
+        _capi.check(self._lib.gp_ct_factor_time_table(self._h, table.ctypes.data, indices.ctypes.data), "gp_ct_factor_time_table")
+        return table, indices
+
+    def pose_table(self):
+        """(T [bins, 3, 4], D0 [bins, 6, 6], D1 [bins, 6, 6]) of the last linearise (read-only; for tests and diagnosis)"""
+        rows = np.zeros((self._lib.gp_ct_factor_num_time_bins(self._h), 84), dtype=np.float64)
+        _capi.check(self._lib.gp_ct_factor_pose_table(self._h, rows.ctypes.data), "gp_ct_factor_pose_table")
+        return rows[:, :12].reshape(-1, 3, 4), rows[:, 12:48].reshape(-1, 6, 6), rows[:, 48:].reshape(-1, 6, 6)
+
+    def correspondences(self):
+        """the stored correspondences int32 [n], -1 where a point has none (read-only; for tests and diagnosis)"""
+        out = np.full(self.source.size(), -1, dtype=np.int32)
+        _capi.check(self._lib.gp_ct_factor_correspondences(self._h, out.ctypes.data), "gp_ct_factor_correspondences")
+        return out
+
+    def deskewed_source_points(self, values, local=False):
+        """T(t_i) p_i -- or T0^-1 T(t_i) p_i when `local` -- as float64 [n, 4], last component 1 (:290-308)"""
+        import torch
+
+        out = torch.empty((self.source.size(), 4), dtype=torch.float64, device=self.source.device)
+        torch.cuda.current_stream(self.source.device).synchronize()
+        _capi.check(self._lib.gp_ct_factor_deskew(self._h, *self._poses(values), int(bool(local)), C.c_void_p(out.data_ptr())), "gp_ct_factor_deskew")
+        return out.cpu().numpy()
+
+
+class IntegratedCTGICPFactorGPU(IntegratedCTICPFactorGPU):
+    """Continuous-time GICP factor on the GPU (IntegratedCT_GICPFactor_, impl/integrated_ct_gicp_factor_impl.hpp): the CT-ICP factor with the GICP term
+    r^T (C_B + R(t_i) C_A R(t_i)^T)^-1 r, the matrix taken at the poses of the last linearise and kept for error() (:171-200)."""
+
+    _KIND = 1
+
+    @staticmethod
+    def _check_attributes(target, source):
+        if target.covs_gpu is None:
+            raise _capi.GPError("error: target frame doesn't have required attributes for ct_gicp")  # :27-30
+        if source.covs_gpu is None:
+            raise _capi.GPError("error: source frame doesn't have required attributes for ct_gicp")  # :32-35
 
 
 class IntegratedLOAMFactorGPU:

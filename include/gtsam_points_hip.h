@@ -549,6 +549,39 @@ int gp_colored_gicp_factor_set_max_correspondence_distance(gp_colored_gicp_facto
 int gp_colored_gicp_factor_set_correspondence_update_tolerance(gp_colored_gicp_factor_t* f, double angle, double trans);
 int gp_colored_gicp_factor_num_correspondences(const gp_colored_gicp_factor_t* f);
 
+/* IntegratedCT_ICPFactor_ / IntegratedCT_GICPFactor_ (factors/integrated_ct_icp_factor.hpp, integrated_ct_gicp_factor.hpp and their impl/ files): a scan taken
+ * while the sensor moved from pose0 (first key) to pose1 (second key), every source point transformed by the pose interpolated at its own time stamp.
+ *   time table   built once, at create, on the host from times_dev (:41-55): in index order a new entry opens when t - table.back() > 1e-3 (strict; f64 on the f32
+ *                times), time_index[i] is the last entry at that moment, then every entry is divided by max(1e-9, table.back()).  No sort, no offset.
+ *   pose table   per call (update_poses, :202-248), GTSAM's Pose3 conventions (tangent (omega, v), right-trivialised derivatives), f64: for each entry t
+ *                delta = pose0^-1 pose1, vel = Log(delta), inc = Exp(t vel), T(t) = pose0 inc,
+ *                D0(t) = Ad(inc^-1) - t Jr(t vel) Jr^-1(vel) Ad(delta^-1), D1(t) = t Jr(t vel) Jr^-1(vel); small angles by series (pose0 == pose1 included).
+ *   search       the nearest target point of T(t_i) p_i with squared distance < max (strict, as gp_icp_factor_*), f64 on the f32 inputs.
+ *   per point    J = R(t_i) [-[p]x, I];  kind 0 (CT-ICP): the scalar e = n_B . (T p - x_B), H_a = n_B^T J D_a, error += e^2 (no 1/2);
+ *                kind 1 (CT-GICP): r = T p - x_B, H_a = J D_a, M = (C_B + R(t_i) C_A R(t_i)^T)^-1 of the LINEARISATION poses, error += r^T M r.
+ *   record       gp_linearized6 over (pose0, pose1): H_target = H_00 = sum H_0^T M H_0, H_source = H_11, H_target_source = H_01, b_target = b_0 = sum H_0^T M r,
+ *                b_source = b_1, error, num_inliers = matched points.  The reference's HessianFactor is (k0, k1, H_00, H_01, -b_0, H_11, -b_1, error).
+ * `grid` is BORROWED, as for gp_icp_factor_create.  create copies the times to the host once; it returns GP_ERROR_INVALID_ARGUMENT before any device work for a
+ * NULL grid, points or times, kind 0 without target normals, kind 1 without either covariance array, a kind that is neither, and a negative cut-off.
+ * linearize always searches.  compute_error evaluates on the stored correspondences (kind 1: with M of the stored linearisation pose table) and searches at the
+ * given poses only when nothing is stored (:92-96).  deskew writes T(t_i) p_i -- T0^-1 T(t_i) p_i when `local` -- as double[num_points][4], last component 1
+ * (:290-308).  All are synchronous; two linearises at the same poses are bit-identical.  num_points == 0: a zero record, error 0.
+ * For tests and callers: the number of table entries; the table (double[bins]) and the indices (int[num_points]); the pose table of the last linearise (or
+ * first error evaluation), double[bins][12 + 36 + 36] = T(t) 3x4 | D0 | D1, all row-major; the stored correspondences, int[num_points], -1 = none.  The last
+ * two return GP_ERROR_INVALID_ARGUMENT before anything is stored. */
+typedef struct gp_ct_factor gp_ct_factor_t;
+int gp_ct_factor_create(const gp_point_grid_t* grid, const float* target_points_dev, const float* target_normals_dev, const float* target_covs_dev, int num_target,
+                        const float* points_dev, const float* covs_dev, const float* times_dev, int num_points, double max_correspondence_distance_sq,
+                        int kind /* 0 ICP, 1 GICP */, gp_stream_t stream, gp_ct_factor_t** out);
+int gp_ct_factor_destroy(gp_ct_factor_t* f); /* leaves the grid alone */
+int gp_ct_factor_linearize(gp_ct_factor_t* f, const double pose0[16], const double pose1[16], gp_linearized6* out_host);
+int gp_ct_factor_compute_error(gp_ct_factor_t* f, const double pose0[16], const double pose1[16], double* out_host);
+int gp_ct_factor_deskew(gp_ct_factor_t* f, const double pose0[16], const double pose1[16], int local, double* out_dev);
+int gp_ct_factor_num_time_bins(const gp_ct_factor_t* f);
+int gp_ct_factor_time_table(const gp_ct_factor_t* f, double* table_host, int* indices_host);
+int gp_ct_factor_pose_table(gp_ct_factor_t* f, double* out_host);
+int gp_ct_factor_correspondences(gp_ct_factor_t* f, int* out_host);
+
 /* ---- a batch of GICP / ICP / LOAM factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
  * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of
  * launches that does not depend on their count -- one search launch, one tile launch per factor kind present (GICP, ICP point-to-point, ICP point-to-plane), one
