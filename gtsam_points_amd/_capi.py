@@ -323,6 +323,16 @@ _SIGNATURES = {
     "gp_pose_factors_issue_compute_error_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_pose_factors_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_pose_factors_compute_error": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    # PlaneEVMFactor / EdgeEVMFactor: BALM bundle adjustment (gp_ba_factors.hip)
+    "gp_ba_factors_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_ba_factors_destroy": (C.c_int, [C.c_void_p]),
+    "gp_ba_factors_num_records": (C.c_int, [C.c_void_p]),
+    "gp_ba_factors_factor_slots": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ba_factors_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ba_factors_issue_linearize_dev": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ba_factors_compute_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ba_factors_feature_num_poses": (C.c_int, [C.c_void_p, C.c_int]),
+    "gp_ba_factors_feature_hessian": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_debug_sparse_work_lists": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_time_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
 }

@@ -806,6 +806,41 @@ int gp_lm_graph_create_with_pose_factors(gp_vgicp_batch_t* batch, const int* pos
 int gp_lm_graph_create_with_factors(gp_vgicp_batch_t* batch, const int* vgicp_pairs, gp_corr_batch_t* corr, const int* corr_pairs, const gp_pose_factor* pose_factors,
                                     int num_pose_factors, int num_poses, const unsigned char* pose_fixed, int ordering, gp_stream_t stream, gp_lm_graph_t** out);
 
+/* ---- PlaneEVMFactor / EdgeEVMFactor: BALM bundle adjustment by eigenvalue minimisation (gp_ba_factors.hip) ----
+ * factors/bundle_adjustment_factor_evm.hpp, balm_feature.hpp, src/gtsam_points/factors/bundle_adjustment_factor_evm.cpp (Liu & Zhang, BALM, RA-L 2021).  One factor
+ * is one feature seen from K poses with N points; with q_i = T_pose(i) p_i its error is error_scale lambda_0 of cov(q) (plane) or lambda_0 + lambda_1 (edge: the
+ * reference's EdgeEVMFactor ignores error_scale in error() and linearize(), and so does this), its HessianFactor (keys, G = scale D^T H D, g = -scale J D, f = error)
+ * with D_i = [-[q_i]x, I]: the derivative for a world-frame (left) perturbation, tangent order (omega, v), handed on unchanged as the reference does.  All f64.
+ *   create        kinds [F] (GP_BA_PLANE / GP_BA_EDGE), error_scales [F], feature_offsets [F + 1] (feature f owns points [offsets[f], offsets[f + 1])), point_pose
+ *                 [num_points] (the pose index of each point, any order within a feature: the host sorts a feature's points by pose), points double[num_points][3].
+ *                 Everything is copied.  GP_ERROR_INVALID_ARGUMENT before any device work for: a NULL array or out, a count < 1, offsets that do not start at 0, are
+ *                 not sorted or do not end at num_points, a feature with fewer than 3 points, a pose index outside [0, num_poses), an unknown kind.
+ *   records       linearize writes R = U + Q gp_linearized6 records: first U unary records, one per pose that some feature touches, in pose order (target slot -1,
+ *                 source = the pose, like a prior's record: H_source = sum over features of G_aa, b_source = -sum g_a), then Q pair records, one per pose pair a < b that
+ *                 some feature co-observes, in (a, b) order (target a, source b, H_target_source = sum G_ab, the rest 0).  A feature's f and point count are the error /
+ *                 num_inliers share of the unary record of its LOWEST pose, so the sum of `error` over the records is the total.  factor_slots: out int[R][2] =
+ *                 (-1 | slot_of_pose[a], slot_of_pose[b]) for gp_dense_system_create / gp_sparse_system_create; a held pose (slot < 0) drops out as for every other
+ *                 factor, the errors stay in c.
+ *   bits          every sum has a fixed order and no atomics: two linearises at the same values agree bit for bit, and so do linearize and issue_linearize_dev.
+ *   values        values_host / poses_dev = double[num_poses][16], column-major 4x4.  issue_linearize_dev is asynchronous on the stream given to create; the others
+ *                 copy the values up, wait and copy the results down.  compute_errors: errors_host [F], each feature's error().
+ *   feature_hessian  feature i's own dense factor over its K = feature_num_poses(i) poses in ascending pose order: G [6K][6K] (symmetric, full), g [6K], f --
+ *                 through the same kernels, for single-factor callers and for checkers.
+ * A repeated eigenvalue gives inf / NaN, as in the reference. */
+#define GP_BA_PLANE 0
+#define GP_BA_EDGE 1
+typedef struct gp_ba_factors gp_ba_factors_t;
+int gp_ba_factors_create(const int* kinds, const double* error_scales, const int* feature_offsets, const int* point_pose, const double* points, int num_features, int num_points,
+                         int num_poses, gp_stream_t stream, gp_ba_factors_t** out);
+int gp_ba_factors_destroy(gp_ba_factors_t* b);
+int gp_ba_factors_num_records(const gp_ba_factors_t* b); /* R; 0 for NULL */
+int gp_ba_factors_factor_slots(const gp_ba_factors_t* b, const int* slot_of_pose, int* out);
+int gp_ba_factors_linearize(gp_ba_factors_t* b, const double* values_host, gp_linearized6* records_host);
+int gp_ba_factors_issue_linearize_dev(gp_ba_factors_t* b, const double* poses_dev, gp_linearized6* records_dev);
+int gp_ba_factors_compute_errors(gp_ba_factors_t* b, const double* values_host, double* errors_host);
+int gp_ba_factors_feature_num_poses(const gp_ba_factors_t* b, int feature); /* K; 0 for NULL or a feature out of range */
+int gp_ba_factors_feature_hessian(gp_ba_factors_t* b, int feature, const double* values_host, double* G, double* g, double* f);
+
 /* ---- voxelgrid_sampling / randomgrid_sampling / sample on the device (gp_sampling.hip) ----
  * Device counterparts of types/point_cloud_cpu.hpp:110-156 (point_cloud_cpu_funcs.cpp:27-75, 119-295, 298-456; CPU-only upstream).
  * A plan is built once per (cloud, resolution); any number of attribute reductions or index selections then run on it, on the plan's stream.
