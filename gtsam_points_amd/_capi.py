@@ -230,7 +230,9 @@ _SIGNATURES = {
     "gp_ct_factor_time_table": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_ct_factor_pose_table": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gp_ct_factor_correspondences": (C.c_int, [C.c_void_p, C.c_void_p]),
-    # a batch of GICP / ICP / LOAM factors with device-resident poses (gp_corr_batch.hip)
+    # a batch of GICP / ICP / LOAM / colored GICP factors with device-resident poses (gp_corr_batch.hip)
+    "gp_corr_batch_create_ex2": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p,
+                                           C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create_ex": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p), C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_corr_batch_destroy": (C.c_int, [C.c_void_p]),

@@ -1,11 +1,11 @@
 // gp_corr_batch.hip -- a batch of matching-cost factors on nearest-neighbour correspondences (GICP, point-to-point and point-to-plane ICP, LOAM edge / plane /
-// combined: gp_corr_factors.hip) whose relative poses live in DEVICE memory: what gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor, and what the device-resident LM graph
+// combined: gp_corr_factors.hip; colored GICP: gp_colored_factors.hip) whose relative poses live in DEVICE memory: what gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor, and what the device-resident LM graph
 // (gp_lm.hip) queues for these factors.
 //
 // A single factor's linearise is three launches and a wait with its pose in the kernel arguments (gp_{gicp,icp}_factor_linearize); F of them are 3 F launches and F
 // waits, and every pose goes through the host.  Here the launch count does not depend on F:
 //   linearise       one search launch (gp_knn.hip: nearest_correspond_batch_kernel -- search structure, cloud, cut-off and pose of each factor from tables in device
-//                   memory), one tile launch per factor KIND present (the kernels are instantiated per term: GICP, ICP point, ICP plane), one finalize launch
+//                   memory), one tile launch per factor KIND present (the kernels are instantiated per term: GICP, ICP point, ICP plane, colored GICP), one finalize launch
 //   error           the tile launches (MODE_ERR) on the STORED correspondences -- the reference's error() does not search (integrated_gicp_factor_impl.hpp:183-185) --
 //                   and one finalize launch
 // The per-point terms, the 1024-point tiles dealt to 256 lanes, the reduction of a tile's sums (gp_corr_factors.hpp) and the finalize kernels (gp_vgicp.hip, one
@@ -22,11 +22,17 @@
 // gp_loam_factor_linearize forms on the host, so the bits agree.  Without one, part p IS member p and neither launch exists: a batch of GICP / ICP members runs
 // exactly the launches it ran before.  The LOAM parts add one search launch (K = 2 and 3 together, gp_knn.hip: nearest_k_correspond_batch_kernel), one tile launch
 // per term kind present, and the validation launch when a member enables it; none of these counts depends on the number of members.
+//
+// Colored GICP members.  One part each, behind the LOAM parts in record order (so a batch of the older kinds keeps its order), but a 1-NN kind: their tiles lie in the
+// 1-NN prefix of the tile list, in front of the LOAM tiles, and the one nearest_correspond_batch_kernel launch searches them.  What the term reads beyond CorrBatchDesc
+// (both intensities, the target's normals and gradients, photometric_term_weight) is in a table of its own, ColoredBatchDesc; the tile kernel is the GICP / ICP one
+// instantiated with that table.  They add one tile launch per pass and nothing else.  A member's photometric_term_weight and max_correspondence_distance are read when
+// the batch is created (as a LOAM member's cut-offs are): a later gp_colored_gicp_factor_set_* does not reach an existing batch.
 // Not thread-safe per handle, re-entrant across handles, like the rest of the library.
 #include <type_traits>
 #include <vector>
 
-#include "gp_corr_factors.hpp"
+#include "gp_colored_term.hpp"
 
 namespace gp {
 
@@ -49,14 +55,28 @@ __device__ __forceinline__ TERM batch_term(const CorrBatchDesc& d) {
   }
 }
 
+// what the colored GICP tile kernels read of part t.factor: the single factor's own term as it stood when the batch was created (a table of its own beside
+// CorrBatchDesc, which the GICP / ICP kernels keep as it is)
+struct ColoredBatchDesc {
+  ColoredGicpTerm term;
+  const int* corr[2];  // [n] the two correspondence sets
+};
+
+template <class TERM>
+__device__ __forceinline__ TERM batch_term(const ColoredBatchDesc& d) {
+  static_assert(std::is_same<TERM, ColoredGicpTerm>::value, "ColoredBatchDesc serves the colored GICP term only");
+  return d.term;
+}
+
 // corr_tile_kernel (gp_corr_factors.hip) with the tile, the factor and the poses looked up: workgroup b takes tile tiles[b], lane t of 256 its points t, t + 256, ...
-template <int MODE, class TERM>
-__global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const CorrBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
+// DESC: CorrBatchDesc (GICP, ICP) or ColoredBatchDesc (colored GICP)
+template <int MODE, class TERM, class DESC>
+__global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const DESC* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
                                                                const double* __restrict__ poses_eval, const int set, double* __restrict__ partials) {
   constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
   constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
   const CorrTile t = tiles[blockIdx.x];
-  const CorrBatchDesc d = descs[t.factor];
+  const DESC& d = descs[t.factor];  // (read in place: a private copy of the larger table's entry would go to scratch for the set-indexed corr[])
   const TERM f = batch_term<TERM>(d);
   const Pose Tl = load_pose(poses_lin + 16 * (size_t)t.factor);
   const Pose Te = MODE == MODE_ERR ? load_pose(poses_eval + 16 * (size_t)t.factor) : Tl;
@@ -142,7 +162,7 @@ __global__ void __launch_bounds__(128) corr_batch_combine_kernel(const int2* __r
 // ---------------------------------------------------------------------------------------------------------------
 
 struct gp_corr_batch {
-  enum Kind { GICP = 0, ICP_POINT = 1, ICP_PLANE = 2, LOAM_EDGE = 3, LOAM_PLANE = 4, NUM_KINDS = 5 };
+  enum Kind { GICP = 0, ICP_POINT = 1, ICP_PLANE = 2, COLORED = 3, LOAM_EDGE = 4, LOAM_PLANE = 5, NUM_KINDS = 6 };  // the 1-NN kinds first: the order of the tile list
   static constexpr int kRecordDoubles = (int)(sizeof(gp_linearized6) / sizeof(double));
   hipStream_t stream = nullptr;
   int F = 0;                    // members = records
@@ -151,10 +171,11 @@ struct gp_corr_batch {
   bool validate = false;        // a LOAM member enables the correspondence validation
   int num_tiles = 0;            // = rows of the partial sums
   long total_points = 0;
-  int kind_begin[NUM_KINDS] = {0, 0, 0, 0, 0}, kind_count[NUM_KINDS] = {0, 0, 0, 0, 0};  // the tile list is ordered by kind: one tile launch per kind present
+  int kind_begin[NUM_KINDS] = {0, 0, 0, 0, 0, 0}, kind_count[NUM_KINDS] = {0, 0, 0, 0, 0, 0};  // the tile list is ordered by kind: one tile launch per kind present
   int tiles_1nn = 0, tiles_knn = 0;                           // the tiles of the 1-NN kinds come first, those of the LOAM kinds behind them
   gp::DeviceArray d_search, d_descs, d_tiles, d_rows;         // search descriptors | CorrBatchDesc[P] | CorrTile[num_tiles] | FactorDesc[P] (tile_begin / tile_count: the finalize's)
   gp::DeviceArray d_loam_descs;                               // LoamBatchDesc[P] (the LOAM parts' entries)
+  gp::DeviceArray d_colored_descs;                            // ColoredBatchDesc[P] (the colored GICP parts' entries)
   gp::DeviceArray d_part_member, d_member_parts;              // int[P] | int2[F]
   gp::DeviceArray d_part_poses[2], d_part_records, d_part_errors;  // combine: [P][16] lin | eval, gp_linearized6[P], double[P]
   gp::DeviceArray d_corr[2];                                  // int each: part p's correspondences (K rows of n) at its offset
@@ -173,11 +194,14 @@ struct gp_corr_batch {
     const gp::CorrBatchDesc* descs = d_descs.as<gp::CorrBatchDesc>();
     const gp::CorrTile* tiles = d_tiles.as<gp::CorrTile>();
     if (kind_count[GICP] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::GicpTerm>), dim3(kind_count[GICP]), dim3(256), 0, stream, descs, tiles + kind_begin[GICP], lin, eval, set, partials);
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::GicpTerm, gp::CorrBatchDesc>), dim3(kind_count[GICP]), dim3(256), 0, stream, descs, tiles + kind_begin[GICP], lin, eval, set, partials);
     if (kind_count[ICP_POINT] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<false>>), dim3(kind_count[ICP_POINT]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_POINT], lin, eval, set, partials);
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<false>, gp::CorrBatchDesc>), dim3(kind_count[ICP_POINT]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_POINT], lin, eval, set, partials);
     if (kind_count[ICP_PLANE] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<true>>), dim3(kind_count[ICP_PLANE]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_PLANE], lin, eval, set, partials);
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<true>, gp::CorrBatchDesc>), dim3(kind_count[ICP_PLANE]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_PLANE], lin, eval, set, partials);
+    if (kind_count[COLORED] > 0)
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::ColoredGicpTerm, gp::ColoredBatchDesc>), dim3(kind_count[COLORED]), dim3(256), 0, stream,
+                         d_colored_descs.as<gp::ColoredBatchDesc>(), tiles + kind_begin[COLORED], lin, eval, set, partials);
     const gp::LoamBatchDesc* ldescs = d_loam_descs.as<gp::LoamBatchDesc>();
     if (kind_count[LOAM_EDGE] > 0)
       hipLaunchKernelGGL((gp::loam_batch_tiles_kernel<MODE, gp::LoamEdgeTerm>), dim3(kind_count[LOAM_EDGE]), dim3(256), 0, stream, ldescs, tiles + kind_begin[LOAM_EDGE], lin, eval, set, partials);
@@ -264,18 +288,24 @@ int corr_batch_error_end(gp_corr_batch* b, double* out_host, long extra_spin_us)
 extern "C" {
 
 int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out) {
-  return gp_corr_batch_create_ex(gicp, num_gicp, icp, num_icp, nullptr, 0, stream, out);
+  return gp_corr_batch_create_ex2(gicp, num_gicp, icp, num_icp, nullptr, 0, nullptr, 0, stream, out);
 }
 
 int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
                             gp_stream_t stream, gp_corr_batch_t** out) {
+  return gp_corr_batch_create_ex2(gicp, num_gicp, icp, num_icp, loam, num_loam, nullptr, 0, stream, out);
+}
+
+int gp_corr_batch_create_ex2(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
+                             const gp_colored_gicp_factor_t* const* colored, int num_colored, gp_stream_t stream, gp_corr_batch_t** out) {
   if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null out");
   *out = nullptr;
-  if (num_gicp < 0 || num_icp < 0 || num_loam < 0 || (num_gicp > 0 && !gicp) || (num_icp > 0 && !icp) || (num_loam > 0 && !loam))
+  if (num_gicp < 0 || num_icp < 0 || num_loam < 0 || num_colored < 0 || (num_gicp > 0 && !gicp) || (num_icp > 0 && !icp) || (num_loam > 0 && !loam) ||
+      (num_colored > 0 && !colored))
     return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: bad arguments");
-  if (num_gicp + num_icp + num_loam == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
-  const int F = num_gicp + num_icp + num_loam;
-  // the parts in record order: a GICP / ICP member is one, a LOAM member its edge part and / or its plane part, in that order
+  if (num_gicp + num_icp + num_loam + num_colored == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
+  const int F = num_gicp + num_icp + num_loam + num_colored;
+  // the parts in record order: a GICP / ICP / colored GICP member is one, a LOAM member its edge part and / or its plane part, in that order
   struct Part {
     const gp_corr_factor_core* core;
     int kind, member, k;
@@ -307,6 +337,14 @@ int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, c
     if (l->edge) parts.push_back({l->edge.get(), gp_corr_batch::LOAM_EDGE, m, 2, l});
     if (l->plane) parts.push_back({l->plane.get(), gp_corr_batch::LOAM_PLANE, m, 3, l});
     validate = validate || l->validation;
+  }
+  for (int i = 0; i < num_colored; i++) {
+    if (!colored[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null colored GICP factor");
+    if (colored[i]->tol_rot != 0.0 || colored[i]->tol_trans != 0.0)
+      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: a colored GICP factor with non-zero correspondence-update tolerances cannot join a batch");
+    const int m = num_gicp + num_icp + num_loam + i;
+    member_parts[(size_t)m] = make_int2((int)parts.size(), 1);
+    parts.push_back({colored[i], gp_corr_batch::COLORED, m, 1, nullptr});
   }
   for (const Part& p : parts)
     if (p.core->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
@@ -355,6 +393,7 @@ int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, c
   std::vector<char> search(gp::corr_search_desc_bytes() * (size_t)P);
   std::vector<gp::CorrBatchDesc> descs((size_t)P);
   std::vector<gp::LoamBatchDesc> ldescs((size_t)P);
+  std::vector<gp::ColoredBatchDesc> cdescs((size_t)P);
   for (int p = 0; p < P; p++) {
     const Part& part = parts[(size_t)p];
     const gp_corr_factor_core* c = part.core;
@@ -364,7 +403,10 @@ int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, c
     gp::CorrBatchDesc& d = descs[(size_t)p];
     d = gp::CorrBatchDesc{};
     ldescs[(size_t)p] = gp::LoamBatchDesc{};
-    if (part.kind == gp_corr_batch::GICP) {
+    cdescs[(size_t)p] = gp::ColoredBatchDesc{};
+    if (part.kind == gp_corr_batch::COLORED) {
+      cdescs[(size_t)p] = gp::ColoredBatchDesc{static_cast<const gp_colored_gicp_factor*>(c)->term, {c0, c1}};  // (the weight as it stands now; the cut-off went into the search table)
+    } else if (part.kind == gp_corr_batch::GICP) {
       const gp::GicpTerm& t = static_cast<const gp_gicp_factor*>(c)->term;
       d.points = t.points, d.covs = t.covs, d.target_points = t.target_points, d.target_covs = t.target_covs;
     } else if (part.loam) {
@@ -379,6 +421,7 @@ int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, c
   GP_TRY(b->d_search.alloc(search.size()));
   GP_TRY(b->d_descs.alloc(sizeof(gp::CorrBatchDesc) * (size_t)P));
   GP_TRY(b->d_loam_descs.alloc(sizeof(gp::LoamBatchDesc) * (size_t)P));
+  GP_TRY(b->d_colored_descs.alloc(sizeof(gp::ColoredBatchDesc) * (size_t)P));
   GP_TRY(b->d_tiles.alloc(sizeof(gp::CorrTile) * std::max(tiles.size(), (size_t)1)));
   GP_TRY(b->d_rows.alloc(sizeof(gp::FactorDesc) * (size_t)P));
   GP_TRY(b->d_part_member.alloc(sizeof(int) * (size_t)P));
@@ -386,6 +429,7 @@ int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, c
   GP_HIP(hipMemcpy(b->d_search.ptr, search.data(), search.size(), hipMemcpyHostToDevice));
   GP_HIP(hipMemcpy(b->d_descs.ptr, descs.data(), sizeof(gp::CorrBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
   GP_HIP(hipMemcpy(b->d_loam_descs.ptr, ldescs.data(), sizeof(gp::LoamBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
+  GP_HIP(hipMemcpy(b->d_colored_descs.ptr, cdescs.data(), sizeof(gp::ColoredBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
   if (!tiles.empty()) GP_HIP(hipMemcpy(b->d_tiles.ptr, tiles.data(), sizeof(gp::CorrTile) * tiles.size(), hipMemcpyHostToDevice));
   GP_HIP(hipMemcpy(b->d_rows.ptr, rows.data(), sizeof(gp::FactorDesc) * (size_t)P, hipMemcpyHostToDevice));
   GP_HIP(hipMemcpy(b->d_part_member.ptr, part_member.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));

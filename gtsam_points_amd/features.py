@@ -668,12 +668,14 @@ def _poses16(deltas, count):
 
 
 class CorrespondenceFactorBatchGPU:
-    """IntegratedGICPFactorGPU / IntegratedICPFactorGPU / LOAM factor objects linearised and evaluated TOGETHER (gp_corr_batch_*, csrc/gp_corr_batch.hip): a number of
-    launches that does not depend on their number, with the relative poses read from device memory.  Record order: the GICP factors in the order given, then the
-    ICP factors, then the LOAM factors (edge, plane or combined) (`order`: positions in `factors`; the results below are returned in the order of `factors`).
+    """IntegratedGICPFactorGPU / IntegratedICPFactorGPU / LOAM factor / IntegratedColoredGICPFactorGPU objects linearised and evaluated TOGETHER (gp_corr_batch_*,
+    csrc/gp_corr_batch.hip): a number of launches that does not depend on their number, with the relative poses read from device memory.  Record order: the GICP
+    factors in the order given, then the ICP factors, then the LOAM factors (edge, plane or combined), then the colored GICP factors (`order`: positions in
+    `factors`; the results below are returned in the order of `factors`).
     The batch borrows the factors (kept alive here) and keeps correspondences of its own, in two sets: a linearise searches into the set it names (default 0), an
     error evaluation reads the set it names and never searches.  A record / an error has the bits of the factor's own linearize_delta / error at the same pose(s).
-    ICP and LOAM factors with non-zero correspondence-update tolerances are refused; a LOAM factor's cut-offs and validation switch are read here, at creation."""
+    ICP, LOAM and colored GICP factors with non-zero correspondence-update tolerances are refused.  A LOAM factor's cut-offs and validation switch, and a colored GICP
+    factor's photometric_term_weight and max_correspondence_distance, are read here, at creation: a later set_* on the factor does not reach an existing batch."""
 
     def __init__(self, factors, stream=None):
         self._lib = _capi.load()
@@ -681,9 +683,10 @@ class CorrespondenceFactorBatchGPU:
         gicp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedGICPFactorGPU)]
         icp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedICPFactorGPU)]
         loam = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedLOAMFactorGPU)]
-        if len(gicp) + len(icp) + len(loam) != len(self.factors):
-            raise TypeError("CorrespondenceFactorBatchGPU takes IntegratedGICPFactorGPU / IntegratedICPFactorGPU / IntegratedLOAMFactorGPU objects")
-        self.order = gicp + icp + loam  # record r is factors[order[r]]
+        colored = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedColoredGICPFactorGPU)]
+        if len(gicp) + len(icp) + len(loam) + len(colored) != len(self.factors):
+            raise TypeError("CorrespondenceFactorBatchGPU takes IntegratedGICPFactorGPU / IntegratedICPFactorGPU / IntegratedLOAMFactorGPU / IntegratedColoredGICPFactorGPU objects")
+        self.order = gicp + icp + loam + colored  # record r is factors[order[r]]
         if stream is None and self.factors:
             stream = self.factors[0].stream  # the stream the factors were created on (the library refuses a batch whose factors live on different streams)
         self._slot = np.argsort(np.asarray(self.order, dtype=np.int64)) if self.factors else np.zeros(0, np.int64)  # factors[i] is record _slot[i]
@@ -691,8 +694,9 @@ class CorrespondenceFactorBatchGPU:
         ga = (C.c_void_p * max(len(gicp), 1))(*[self.factors[i]._h.value for i in gicp])
         ia = (C.c_void_p * max(len(icp), 1))(*[self.factors[i]._h.value for i in icp])
         la = (C.c_void_p * max(len(loam), 1))(*[self.factors[i]._h.value for i in loam])
+        ca = (C.c_void_p * max(len(colored), 1))(*[self.factors[i]._h.value for i in colored])
         h = C.c_void_p()
-        _capi.check(self._lib.gp_corr_batch_create_ex(ga, len(gicp), ia, len(icp), la, len(loam), stream, C.byref(h)), "gp_corr_batch_create_ex")
+        _capi.check(self._lib.gp_corr_batch_create_ex2(ga, len(gicp), ia, len(icp), la, len(loam), ca, len(colored), stream, C.byref(h)), "gp_corr_batch_create_ex2")
         self._h = h
         self._dev = None
 

@@ -315,9 +315,9 @@ class LevenbergMarquardtGraphGPU:
     factors: IntegratedVGICPFactorGPU objects; pairs[i] = (target pose, source pose) of factor i, poses 0..num_poses-1; fixed: indices of held poses.
     pose_factors: BetweenFactorPose3 / PriorFactorPose3 objects over the same poses (gp_lm_graph_create_with_pose_factors): their records follow the VGICP ones,
     `factors` may then be empty (a pose graph) and `fixed` may be () (the priors fix the gauge).  values are [num_poses, 4, 4] float64 arrays (rigid).
-    corr_factors: IntegratedGICPFactorGPU / IntegratedICPFactorGPU / LOAM factor objects, corr_pairs[i] = (target pose, source pose) of corr_factors[i]
+    corr_factors: IntegratedGICPFactorGPU / IntegratedICPFactorGPU / LOAM factor / IntegratedColoredGICPFactorGPU objects, corr_pairs[i] = (target pose, source pose) of corr_factors[i]
     (gp_lm_graph_create_with_factors): the graph builds and owns a CorrespondenceFactorBatchGPU over them; their records lie between the VGICP ones and the pose
-    factors', in the batch's record order (GICP factors first, then ICP, then LOAM, each in the order given: `corr_order`).  The trials evaluate them on the correspondences
+    factors', in the batch's record order (GICP factors first, then ICP, then LOAM, then colored GICP, each in the order given: `corr_order`).  The trials evaluate them on the correspondences
     of the linearisation point, whether or not a linearise at a trial's values was queued ahead (two correspondence sets)."""
 
     def __init__(self, factors, pairs, num_poses, fixed=(0,), ordering="auto", stream=None, pose_factors=(), corr_factors=(), corr_pairs=()):

@@ -582,7 +582,7 @@ int gp_ct_factor_time_table(const gp_ct_factor_t* f, double* table_host, int* in
 int gp_ct_factor_pose_table(gp_ct_factor_t* f, double* out_host);
 int gp_ct_factor_correspondences(gp_ct_factor_t* f, int* out_host);
 
-/* ---- a batch of GICP / ICP / LOAM factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
+/* ---- a batch of GICP / ICP / LOAM / colored GICP factors with the relative poses in DEVICE memory (gp_corr_batch.hip) ----
  * What gp_vgicp_batch_issue_linearize_dev / _issue_compute_error_dev are to the VGICP factor: any number of the factors above linearised (or evaluated) in a number of
  * launches that does not depend on their count -- one search launch, one tile launch per factor kind present (GICP, ICP point-to-point, ICP point-to-plane), one
  * finalize launch --, the poses read from a table double[F][16] (column-major) in device memory.  The batch BORROWS the factor handles (the caller keeps them and
@@ -608,11 +608,20 @@ int gp_ct_factor_correspondences(gp_ct_factor_t* f, int* out_host);
  * cut-offs and validation switch are read when the batch is created.  Launches with LOAM members: one more search launch (the K > 1 parts), one tile launch per term
  * kind present (edge, plane), the validation launch if any member enables it, one finalize over the PARTS, and -- when a member has both parts -- one launch that
  * hands each member its pose in front and one that adds the edge part's record and the plane part's in that order in f64 behind: a LOAM member's record and error
- * equal, bit for bit, those of gp_loam_factor_linearize / _compute_error at the same pose(s), in both sets. */
+ * equal, bit for bit, those of gp_loam_factor_linearize / _compute_error at the same pose(s), in both sets.
+ * gp_corr_batch_create_ex2 adds colored GICP members (gp_corr_batch_create_ex means num_colored = 0); record order GICP, ICP, LOAM, then colored GICP, each in the
+ * order given, so a batch of the older kinds keeps its order.  A colored member is a 1-NN kind like GICP: the one search launch of the GICP / ICP members searches it
+ * too, and it adds one tile launch per pass (the single factor's term from a descriptor table of its own) and nothing else, whatever the number of members.  Its
+ * record and error equal, bit for bit, those of gp_colored_gicp_factor_linearize / _compute_error at the same pose(s), in both sets (M_g at poses_lin, d and the
+ * photometric residual at poses_eval).  A member's photometric_term_weight and max_correspondence_distance are read when the batch is created: a later
+ * gp_colored_gicp_factor_set_photometric_term_weight / _set_max_correspondence_distance does not reach an existing batch.  Refused with GP_ERROR_INVALID_ARGUMENT: a
+ * NULL handle, a colored factor created on another stream, one whose correspondence-update tolerances are not both zero (as for ICP and LOAM). */
 typedef struct gp_corr_batch gp_corr_batch_t;
 int gp_corr_batch_create(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, gp_stream_t stream, gp_corr_batch_t** out);
 int gp_corr_batch_create_ex(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
                             gp_stream_t stream, gp_corr_batch_t** out);
+int gp_corr_batch_create_ex2(const gp_gicp_factor_t* const* gicp, int num_gicp, const gp_icp_factor_t* const* icp, int num_icp, const gp_loam_factor_t* const* loam, int num_loam,
+                             const gp_colored_gicp_factor_t* const* colored, int num_colored, gp_stream_t stream, gp_corr_batch_t** out);
 int gp_corr_batch_destroy(gp_corr_batch_t* batch); /* synchronises the batch's stream; leaves the factors alone */
 int gp_corr_batch_size(const gp_corr_batch_t* batch);
 int gp_corr_batch_stream(const gp_corr_batch_t* batch, gp_stream_t* out);
