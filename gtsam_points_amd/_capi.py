@@ -337,7 +337,44 @@ _SIGNATURES = {
     "gp_ba_factors_feature_hessian": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_debug_sparse_work_lists": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_time_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    # FastOccupancyGrid, feature matching, RANSAC and the closed-form alignments (gp_registration.hip)
+    "gp_occupancy_grid_create": (C.c_int, [C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_occupancy_grid_destroy": (C.c_int, [C.c_void_p]),
+    "gp_occupancy_grid_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]),
+    "gp_occupancy_grid_overlap": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "gp_occupancy_grid_overlap_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "gp_occupancy_grid_get_overlaps": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    "gp_occupancy_grid_num_occupied_cells": (C.c_int, [C.c_void_p]),
+    "gp_occupancy_grid_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "gp_feature_nn_search": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_ransac_params_default": (None, [C.c_void_p]),
+    "gp_ransac_sample_index": (C.c_uint, [C.c_uint64, C.c_uint, C.c_uint, C.c_uint]),
+    "gp_ransac_estimate_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_align_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
 }
+
+GP_RANSAC_SCORED, GP_RANSAC_SAMPLE_FAILED, GP_RANSAC_INVALID_FEATURE, GP_RANSAC_POLY_REJECTED, GP_RANSAC_TABOO, GP_RANSAC_SKIPPED = 0, 1, 2, 3, 4, 5
+GP_FEATURE_MAX_DIM, GP_RANSAC_MAX_TABOO = 128, 64
+
+
+class RansacParams(C.Structure):
+    """gp_ransac_params (include/gtsam_points_hip.h): RANSACParams (registration/ransac.hpp:17-29) without num_threads, with chunk_iterations"""
+
+    _fields_ = [("max_iterations", C.c_int), ("dof", C.c_int), ("chunk_iterations", C.c_int), ("num_taboo", C.c_int), ("early_stop_inlier_rate", C.c_double),
+                ("poly_error_thresh", C.c_double), ("inlier_voxel_resolution", C.c_double), ("taboo_thresh_rot", C.c_double), ("taboo_thresh_trans", C.c_double),
+                ("seed", C.c_uint64), ("taboo_poses", C.c_void_p)]
+
+
+class RansacHypotheses(C.Structure):
+    _fields_ = [("status", C.c_void_p), ("source_indices", C.c_void_p), ("target_indices", C.c_void_p), ("poses", C.c_void_p), ("inliers", C.c_void_p)]
+
+
+class RansacResult(C.Structure):
+    _fields_ = [("T_target_source", C.c_double * 16), ("inlier_rate", C.c_double), ("best_inliers", C.c_int), ("best_iteration", C.c_int), ("num_scored", C.c_int),
+                ("early_stopped", C.c_int)]
+
+
+assert C.sizeof(RansacParams) == 72 and C.sizeof(RansacResult) == 152
 
 GP_POSE_FACTOR_BETWEEN, GP_POSE_FACTOR_PRIOR = 0, 1
 

@@ -1041,6 +1041,102 @@ int gp_debug_drop_error_words(gp_vgicp_batch_t* batch, int count);
  * ([2048][16] uint64: slots 0-7 phases, 8 HW_ID, 9 XCC_ID, 10 / 11 start / end on the device-wide clock; row 2047: the finalize kernel of the
  * synchronous call); NULL disables */
 int gp_vgicp_batch_set_trace_buffer(gp_vgicp_batch_t* batch, void* dev_buffer);
+
+/* ---- global registration: FastOccupancyGrid, feature matching, RANSAC, closed-form alignment (csrc/gp_registration.hip, csrc/gp_occupancy.hpp) ----
+ * Device counterparts of ann/fast_occupancy_grid.hpp, registration/ransac.hpp + impl/ransac_impl.hpp and registration/alignment.hpp; CPU-only upstream.  f64
+ * arithmetic on the f32 device points throughout.
+ *
+ * gp_occupancy_grid: the SET of occupied cells of FastOccupancyGrid.  cell = fast_floor((pose * p) * (1 / resolution)) + 2^20 per axis, blocks of 8 x 8 x 8 cells,
+ *   block key = three block coordinates masked to 21 bits in a uint64; coordinates outside 21 bits alias by the mask, as in the reference.  pose * p is evaluated
+ *   as ((r0 x + r1 y) + r2 z) + t per row, each operation rounded once (no fused multiply-add).  A point whose transformed coordinates are not finite has no cell.
+ *   The hash table is the library's own (64-bit compare-and-swap on keys, 32-bit OR on cell words; a power of two of slots, at most half full, sized from the
+ *   number of points inserted; every probe loop is bounded by the table size) -- the reference's 10-probe limit and rehash are not reproduced: the set is exact.
+ *   _insert: may be called any number of times, the result is the union; waits once (for the counts).  pose NULL = identity.
+ *   _overlap: number of points of the cloud whose cell is in the set (calc_overlap); waits.  _get_overlaps: 0 / 1 per point into a device array; asynchronous.
+ *   _overlap_batch: counts_out_dev[h] = calc_overlap(points, poses_dev[h]) for h < num_poses in ONE launch (poses_dev double[num_poses][16], column-major, on the
+ *   device; counts int[num_poses] on the device); asynchronous.  This is RANSAC's scoring kernel. */
+typedef struct gp_occupancy_grid gp_occupancy_grid_t;
+int gp_occupancy_grid_create(double resolution, gp_stream_t stream, gp_occupancy_grid_t** out);
+int gp_occupancy_grid_destroy(gp_occupancy_grid_t* grid);
+int gp_occupancy_grid_insert(gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose /* [16] or NULL */);
+int gp_occupancy_grid_overlap(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose /* [16] or NULL */, int* num_overlap);
+int gp_occupancy_grid_overlap_batch(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* poses_dev, int num_poses, int* counts_out_dev);
+int gp_occupancy_grid_get_overlaps(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose /* [16] or NULL */, unsigned char* overlaps_out_dev);
+int gp_occupancy_grid_num_occupied_cells(const gp_occupancy_grid_t* grid);
+/* (measurement) slots of the table and occupied blocks */
+int gp_occupancy_grid_info(const gp_occupancy_grid_t* grid, int* num_slots, int* num_blocks);
+
+/* Exact 1-NN among feature rows, brute force, tiled through LDS: for query i (row rows_dev[i] of query_features_dev, or row i when rows_dev is NULL)
+ *   indices_out_dev[i] = argmin_t sum_j (q_j - target[t][j])^2, sq_dists_out_dev[i] = that minimum,
+ * the differences and the sum in f64 on the f32 values (direct form, fused multiply-add accumulation in ascending j).  Features are float[N][dim] row-major on the
+ * device, 1 <= dim <= 128 (GP_FEATURE_MAX_DIM).  Among targets at exactly the same f64 distance either may be returned.  A row index outside [0, num_query_rows),
+ * or a query no target compares below +inf with (NaN features), gives index -1 and distance +inf.  Asynchronous on `stream`. */
+#define GP_FEATURE_MAX_DIM 128
+int gp_feature_nn_search(const float* target_features_dev, int num_target, const float* query_features_dev, int num_query_rows, int dim, const int* rows_dev, int num_queries,
+                         int* indices_out_dev, double* sq_dists_out_dev, gp_stream_t stream);
+
+/* estimate_pose_ransac (impl/ransac_impl.hpp:24-191), one device thread per hypothesis, iterations 0 .. max_iterations - 1 in chunks of chunk_iterations in stream order.
+ * Per iteration, in this order (the first that applies is the iteration's status):
+ *   sampling     dof 6: 3, dof 4: 2 distinct source indices (:39-48).  The d-th draw of iteration `it` (d = 0, 1, ... counts every draw, redraws included) is
+ *                  index = ((r >> 32) * num_source) >> 32,  r = mix(mix(seed + G * (it + 1)) + G * (d + 1)),  G = 0x9E3779B97F4A7C15,
+ *                  mix(z): z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) * 0x94D049BB133111EB; return z ^ (z >> 31),
+ *                all in uint64 arithmetic modulo 2^64 (gp_ransac_sample_index is this function on the host).  A draw equal to an index already held is drawn again;
+ *                more than 64 redraws in one iteration: GP_RANSAC_SAMPLE_FAILED.  std::mt19937 parity is neither possible nor wanted.  With sample_indices_dev
+ *                (int[max_iterations][3], the third unused for dof 4) the caller's indices are taken as they are (they must lie inside the source cloud).
+ *   invalid feature  a sampled source row with every |f_j| <= 1e-3 (Eigen's isZero(1e-3), :57): GP_RANSAC_INVALID_FEATURE
+ *   matching     gp_feature_nn_search of the sampled rows among the target features (:62); a query without a match takes target 0, as the reference does (:64)
+ *   polygon      max over the sample's edges of |dt - ds| / max(dt, ds, 1e-6) (:73-88) > poly_error_thresh: GP_RANSAC_POLY_REJECTED
+ *   alignment    align_points_se3 / align_points_4dof of the sample (alignment.cpp:11-65): R = u1 v1^T + u2 v2^T + (u1 x u2)(v1 x v2)^T from the two leading singular pairs
+ *                of H's 3x3 block (one-sided Jacobi), which equals U diag(1, 1, det(U) det(V)) V^T; dof 4: the rotation about z that maximises trace(R^T H) on the 2x2 block
+ *   taboo        angle(taboo^-1 T) < taboo_thresh_rot and |t(taboo^-1 T)| < taboo_thresh_trans for one of up to 64 poses (:149-156): GP_RANSAC_TABOO
+ *   score        inliers = gp_occupancy_grid_overlap_batch of the source at T over a grid of the target at inlier_voxel_resolution (:115-117): GP_RANSAC_SCORED
+ * Selection is deterministic (the reference's depends on thread timing): behind each chunk a device flag is set when one of its scored hypotheses has
+ * inliers > num_source * early_stop_inlier_rate (:163); every kernel of a later chunk reads the flag first and leaves, its iterations get GP_RANSAC_SKIPPED.
+ * The result is the scored hypothesis with the most inliers, ties to the lowest iteration; inlier_rate = best_inliers / num_TARGET (:190, the reference's own
+ * denominator).  Without a scored hypothesis: identity, best_iteration -1, inlier_rate 0.  Everything is queued on one stream behind one host wait.
+ * Per-iteration arrays (gp_ransac_hypotheses, each pointer a device array or NULL): status int[H]; source / target indices int[H][3] (-1 where not drawn / not
+ * matched); poses double[H][16] column-major (zeros before the alignment); inliers int[H] (-1 where not scored).
+ * GP_ERROR_INVALID_ARGUMENT before any launch: fewer source points than samples, an empty target, dof outside {4, 6}, dim outside 1 .. 128, more than 64 taboo
+ * poses, max_iterations or chunk_iterations < 1, a resolution that is not positive and finite. */
+enum { GP_RANSAC_SCORED = 0, GP_RANSAC_SAMPLE_FAILED = 1, GP_RANSAC_INVALID_FEATURE = 2, GP_RANSAC_POLY_REJECTED = 3, GP_RANSAC_TABOO = 4, GP_RANSAC_SKIPPED = 5 };
+#define GP_RANSAC_MAX_TABOO 64
+#define GP_RANSAC_MAX_REDRAWS 64
+typedef struct gp_ransac_params {
+  int max_iterations;              /* 5000 */
+  int dof;                         /* 6 (SE3) or 4 (XYZ + RZ) */
+  int chunk_iterations;            /* 1024 */
+  int num_taboo;                   /* 0 */
+  double early_stop_inlier_rate;   /* 0.8 */
+  double poly_error_thresh;        /* 0.5 */
+  double inlier_voxel_resolution;  /* 1.0 */
+  double taboo_thresh_rot;         /* 0.5 degrees in radians */
+  double taboo_thresh_trans;       /* 0.25 */
+  uint64_t seed;                   /* 5489 */
+  const double* taboo_poses;       /* host double[num_taboo][16], column-major */
+} gp_ransac_params;
+typedef struct gp_ransac_hypotheses {
+  int* status;
+  int* source_indices;
+  int* target_indices;
+  double* poses;
+  int* inliers;
+} gp_ransac_hypotheses;
+typedef struct gp_ransac_result {
+  double T_target_source[16];
+  double inlier_rate;
+  int best_inliers;
+  int best_iteration;
+  int num_scored;
+  int early_stopped;
+} gp_ransac_result;
+void gp_ransac_params_default(gp_ransac_params* params);
+unsigned gp_ransac_sample_index(uint64_t seed, unsigned iteration, unsigned draw, unsigned num_source); /* host code */
+int gp_ransac_estimate_pose(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const float* target_features_dev,
+                            const float* source_features_dev, int dim, const gp_ransac_params* params, const int* sample_indices_dev, const gp_ransac_hypotheses* hypotheses,
+                            gp_ransac_result* result, gp_stream_t stream);
+/* the weighted N-point overloads of align_points_se3 / align_points_4dof (alignment.cpp:67-139): points double[N][3] and weights double[N] on the device, the
+ * weighted means and H summed in a fixed tree order (no floating-point atomics), the rotation as above; pose_out: host double[16], column-major.  Waits. */
+int gp_align_points(const double* target_points_dev, const double* source_points_dev, const double* weights_dev, int num_points, int dof, double* pose_out, gp_stream_t stream);
 #ifdef __cplusplus
 }
 #endif
