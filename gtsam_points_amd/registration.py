@@ -122,7 +122,7 @@ def _features(f, device, what):
 def match_features_gpu(target_features, source_features, rows=None, device="cuda:0", stream=None):
     """The exact nearest target row of each query row: (int32 [nq] indices, float64 [nq] squared distances), device tensors.  Brute force over the D-dimensional rows
     (1 <= D <= 128), the distance the direct sum of squared differences in f64.  rows: optional source row indices (the queries); without it every source row is a
-    query.  Among target rows at exactly the same distance either may be returned."""
+    query.  Among target rows at exactly the same distance the lowest index is returned."""
     import torch
 
     dev = target_features.device if isinstance(target_features, torch.Tensor) and target_features.is_cuda else torch.device(device)

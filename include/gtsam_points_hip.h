@@ -1069,7 +1069,7 @@ int gp_occupancy_grid_info(const gp_occupancy_grid_t* grid, int* num_slots, int*
 /* Exact 1-NN among feature rows, brute force, tiled through LDS: for query i (row rows_dev[i] of query_features_dev, or row i when rows_dev is NULL)
  *   indices_out_dev[i] = argmin_t sum_j (q_j - target[t][j])^2, sq_dists_out_dev[i] = that minimum,
  * the differences and the sum in f64 on the f32 values (direct form, fused multiply-add accumulation in ascending j).  Features are float[N][dim] row-major on the
- * device, 1 <= dim <= 128 (GP_FEATURE_MAX_DIM).  Among targets at exactly the same f64 distance either may be returned.  A row index outside [0, num_query_rows),
+ * device, 1 <= dim <= 128 (GP_FEATURE_MAX_DIM).  Among targets at exactly the same f64 distance the LOWEST index is returned (the determinism of gp_ransac_estimate_pose rests on it).  A row index outside [0, num_query_rows),
  * or a query no target compares below +inf with (NaN features), gives index -1 and distance +inf.  Asynchronous on `stream`. */
 #define GP_FEATURE_MAX_DIM 128
 int gp_feature_nn_search(const float* target_features_dev, int num_target, const float* query_features_dev, int num_query_rows, int dim, const int* rows_dev, int num_queries,

@@ -62,6 +62,38 @@ def band_count(points32, pose, resolution, tol=1e-10):
     return int((np.abs(v - np.round(v)) < tol).any(axis=1).sum())
 
 
+def occ_hash(key):
+    """gp_occupancy.hpp occ_hash: key * 0x9E3779B97F4A7C15 mod 2^64, xor with itself shifted right by 32, the low 32 bits"""
+    h = (int(key) * 0x9E3779B97F4A7C15) & M64
+    return (h ^ (h >> 32)) & 0xFFFFFFFF
+
+
+def home_slot(key, slots):
+    """the slot a block key's probe chain starts at in a table of `slots` (a power of two)"""
+    return occ_hash(key) & (slots - 1)
+
+
+def block_key(bx, by, bz):
+    """the key of the block with (unmasked) block coordinates cell >> 3, the cell counted from -2^20"""
+    return (int(bx) & MASK21) | ((int(by) & MASK21) << 21) | ((int(bz) & MASK21) << 42)
+
+
+def probe_table(block_keys, slots):
+    """linear probing of the keys, in this order, into `slots` slots: the list of slots' keys (None = free).  The device's table holds the same keys whatever the
+    order (the slots differ with the order of the claims, the SET does not); this is for the conditions on planted collisions only."""
+    table = [None] * slots
+    for k in block_keys:
+        s = home_slot(k, slots)
+        for _ in range(slots):
+            if table[s] is None or table[s] == k:
+                table[s] = k
+                break
+            s = (s + 1) & (slots - 1)
+        else:
+            raise AssertionError("table full")
+    return table
+
+
 class OccupancySet:
     def __init__(self, resolution):
         self.resolution = float(resolution)
@@ -88,17 +120,27 @@ class OccupancySet:
 
 # ---- feature matching ------------------------------------------------------------------------------------------------------------------------------------------------
 def match_features(target_features, source_features, rows=None):
-    """(index int64 [nq], squared distance f64 [nq], number of targets at exactly the minimum [nq]); the sum over j serial in ascending j"""
+    """(index int64 [nq], squared distance f64 [nq], number of targets at exactly the minimum [nq]); the sum over j serial in ascending j.
+    Among targets at exactly the minimum the LOWEST index is returned (np.argmin returns the first occurrence): the device's rule, which the determinism of RANSAC
+    rests on.  A target whose sum is NaN or +inf is never `<` the best so far and is never returned (a NaN feature on either side makes the sum NaN); a query that no
+    target compares below +inf with -- a NaN query row, every target row NaN or infinite, a row index outside the source rows -- gives (-1, +inf, 0)."""
     T = np.asarray(target_features, np.float32).astype(np.float64)
     S = np.asarray(source_features, np.float32).astype(np.float64)
     rows = np.arange(len(S)) if rows is None else np.asarray(rows, np.int64).reshape(-1)
     idx, sq, ties = np.zeros(len(rows), np.int64), np.zeros(len(rows)), np.zeros(len(rows), np.int64)
     for i, r in enumerate(rows.tolist()):
-        acc = np.zeros(len(T))
-        for j in range(T.shape[1]):
-            d = S[r, j] - T[:, j]
-            acc = acc + d * d
-        idx[i] = int(np.argmin(acc))
+        acc = np.full(len(T), np.nan)
+        if 0 <= r < len(S):
+            acc = np.zeros(len(T))
+            with np.errstate(invalid="ignore", over="ignore"):
+                for j in range(T.shape[1]):
+                    d = S[r, j] - T[:, j]
+                    acc = acc + d * d
+        below = acc < np.inf  # (False for NaN)
+        if not below.any():
+            idx[i], sq[i], ties[i] = -1, np.inf, 0
+            continue
+        idx[i] = int(np.argmin(np.where(below, acc, np.inf)))
         sq[i] = acc[idx[i]]
         ties[i] = int((acc == sq[i]).sum())
     return idx, sq, ties
@@ -255,7 +297,7 @@ def hypotheses(target32, source32, target_features, source_features, iterations,
     m_idx, _, m_ties = match_features(target_features, source_features, rows)
     for k, it in enumerate(alive):
         si = out["source_indices"][it, :samples]
-        ti = m_idx[samples * k : samples * k + samples]
+        ti = np.maximum(m_idx[samples * k : samples * k + samples], 0)  # a sampled row without a match takes target 0 (ransac_impl.hpp:64)
         out["target_indices"][it, :samples] = ti
         out["match_ties"][it] = int(m_ties[samples * k : samples * k + samples].max())
         t, s = tp[ti], sp[si]
@@ -334,3 +376,42 @@ def make_case(dof, seed=1):
     sf[good] = tf[pick[good]] + (0.01 * rng.normal(size=(int(good.sum()), CASE_DIM))).astype(np.float32)
     sf[list(CASE_ZERO_ROWS)] = 0.0
     return {"target": target, "source": source, "target_features": tf, "source_features": sf, "T_true": T, "pick": pick, "dof": dof}
+
+
+# ---- the small inputs of tests/test_ransac_edges_gpu.py (tests/test_ransac_edges_ref_cpu.py holds them to their conditions) ------------------------------------------------
+SMALL_DIM = 8
+SMALL_ZERO_ROWS = (3, 40, 77, 114, 151, 188)
+SMALL_ROW_1E3, SMALL_ROW_2M10, SMALL_ROW_NAN = 10, 20, 30  # float32(1e-3) in one entry (valid: it widens to just above 1e-3); every entry 2^-10 (invalid); every entry NaN
+
+
+@functools.lru_cache(maxsize=None)
+def make_small_case(dof, far=0.0, seed=2):
+    """make_case in small: the target a golden scan cut to at most 512 points, moved by (far, far, 0) and rounded to f32; the source 256 of them moved by the inverse of a
+    known pose; D = 8 descriptors, ~70 % true matches, six all-zero rows and the three special rows above"""
+    rng = np.random.default_rng(seed + 10 * dof)
+    full = scan()
+    target = (full[:: len(full) // 512 + 1][:512].astype(np.float64) + [far, far, 0.0]).astype(np.float32)
+    pick = np.sort(rng.choice(len(target), 256, replace=False))
+    T = np.eye(4)
+    T[:3, :3] = rot([0.2, -0.1, 1.0], 0.6) if dof == 6 else rot([0, 0, 1], 0.6)
+    T[:3, 3] = [3.0, -2.0, 0.5]
+    Ti = pose_inverse(T)
+    source = (target[pick].astype(np.float64) @ Ti[:3, :3].T + Ti[:3, 3]).astype(np.float32)
+    tf = rng.normal(size=(len(target), SMALL_DIM)).astype(np.float32)
+    sf = rng.normal(size=(len(source), SMALL_DIM)).astype(np.float32)
+    good = rng.random(len(source)) < 0.7
+    sf[good] = tf[pick[good]] + (0.01 * rng.normal(size=(int(good.sum()), SMALL_DIM))).astype(np.float32)
+    sf[list(SMALL_ZERO_ROWS)] = 0.0
+    sf[SMALL_ROW_1E3] = 0.0
+    sf[SMALL_ROW_1E3, 5] = np.float32(1e-3)
+    sf[SMALL_ROW_2M10] = np.float32(2.0 ** -10)
+    sf[SMALL_ROW_NAN] = np.nan
+    return {"target": np.ascontiguousarray(target), "source": np.ascontiguousarray(source), "target_features": tf, "source_features": sf, "T_true": T, "pick": pick, "dof": dof,
+            "good": good}
+
+
+def alignment_residual(T, s, t):
+    """sum |T s - t|^2 over the sample's points (rows of s and t), in f64"""
+    s, t = np.asarray(s, np.float64), np.asarray(t, np.float64)
+    d = s @ T[:3, :3].T + T[:3, 3] - t
+    return float((d * d).sum())

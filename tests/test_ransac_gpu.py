@@ -49,14 +49,15 @@ def run(gpu, dof, **kw):
     return res, dev, p
 
 
-def compare(dof, res, dev, p, sample_indices=None):
-    """the device's per-iteration arrays and result against the restatement run with the same parameters; returns the restatement's pre-skip hypotheses"""
-    c = rr.make_case(dof)
+def compare(dof, res, dev, p, sample_indices=None, case=None):
+    """the device's per-iteration arrays and result against the restatement run with the same parameters; returns the restatement's pre-skip hypotheses.
+    case: another input than rr.make_case(dof) (tests/test_ransac_edges_gpu.py: rr.make_small_case), at inlier_voxel_resolution 1.0 like it"""
+    c = rr.make_case(dof) if case is None else case
     H = p.max_iterations
     samples = 3 if dof == 6 else 2
     ref = rr.hypotheses(c["target"], c["source"], c["target_features"], c["source_features"], H, dof=dof, seed=p.seed, poly_error_thresh=p.poly_error_thresh,
                         taboo_list=tuple(p.taboo_list), taboo_thresh_rot=p.taboo_thresh_rot, taboo_thresh_trans=p.taboo_thresh_trans, sample_indices=sample_indices)
-    grid = target_set(dof)
+    grid = target_set(dof) if case is None else rr.OccupancySet(1.0).insert(c["target"])
     counts = np.full(H, -1, np.int64)
     band = np.zeros(H, np.int64)
     for it in np.flatnonzero(ref["status"] == rr.SCORED):
