@@ -14,11 +14,7 @@
 
 namespace gp {
 
-struct GridGeom {
-  int lo[3];   // block coordinate (cell coordinate >> 2) of the low corner
-  int dim[3];  // blocks per axis
-};
-
+// (GridGeom: gp_device.hpp)
 __host__ __device__ __forceinline__ long long grid_block_index(const GridGeom& g, int cx, int cy, int cz) {
   const int bx = (cx >> 2) - g.lo[0], by = (cy >> 2) - g.lo[1], bz = (cz >> 2) - g.lo[2];
   return ((long long)bz * g.dim[1] + by) * g.dim[0] + bx;

@@ -44,6 +44,12 @@ struct __attribute__((aligned(16))) GridBlock {
 };
 static_assert(sizeof(GridBlock) == 16, "GridBlock must be 16 B");
 
+// the box a block grid covers (index and bit of a cell: gp_binning.hpp)
+struct GridGeom {
+  int lo[3];   // block coordinate (cell coordinate >> 2) of the low corner
+  int dim[3];  // blocks per axis
+};
+
 struct VoxelMapView {
   // block grid (null when the bounding box would need more than the block budget: the line table below is used then)
   const GridBlock* gblocks;
@@ -142,6 +148,9 @@ __host__ __device__ __forceinline__ int fast_floor(double x) {
   const int n = (int)x;
   return n - (x < (double)n);
 }
+
+// the `mask` of bucket_index for a table of n buckets: n - 1 when n is a power of two, else 0 (the probe then takes the remainder)
+__host__ __device__ __forceinline__ uint32_t pow2_mask(int64_t n) { return (n > 0 && (n & (n - 1)) == 0) ? (uint32_t)(n - 1) : 0u; }
 
 __host__ __device__ __forceinline__ uint32_t bucket_index(uint64_t hash, int i, uint32_t num_buckets, uint32_t mask) {
   const uint64_t h = hash + (uint64_t)i;

@@ -461,29 +461,43 @@ struct gp_voxelmap {
   hipStream_t stream = nullptr;
   gp_voxelmap_info info{};
 
-  gp::DeviceArray buckets;      // gp_voxel_bucket[num_buckets]
-  gp::DeviceArray records;      // gp::VoxelRecord[num_voxels]   (kernel gather layout)
-  gp::DeviceArray num_points;   // int[num_voxels]               (reference-visible arrays below)
-  gp::DeviceArray voxel_means;  // float[num_voxels][3]
-  gp::DeviceArray voxel_covs;   // float[num_voxels][9]
-  gp::DeviceArray voxel_intensities;  // float[num_voxels]
-  gp::DeviceArray voxel_coords; // int[num_voxels][3] voxel coordinate of each voxel index
+  // THE table of the map's arrays: each device array with the host copy that offload() keeps of it; array_bytes() is its size for the current `info`.
+  // alloc_voxel_arrays, download, clone, offload and reload (gp_voxelmap.hip, gp_voxelmap_store.hip) walk it; a new per-voxel array is one more row here.  kGblocks stays last: the one array a map may lack (has_grid)
+  enum ArrayId { kBuckets, kRecords, kNumPoints, kMeans, kCovs, kIntensities, kCoords, kGblocks, kNumArrays };
+  struct Array {
+    gp::DeviceArray dev;
+    std::vector<char> host;
+  };
+  Array arrays[kNumArrays];
+  size_t array_bytes(int id) const {
+    static constexpr size_t kEntry[kNumArrays] = {sizeof(gp_voxel_bucket), sizeof(gp::VoxelRecord), sizeof(int),     sizeof(float) * 3,
+                                                  sizeof(float) * 9,       sizeof(float),           sizeof(int) * 3, sizeof(gp::GridBlock)};
+    const size_t n = id == kBuckets ? (size_t)info.num_buckets : id == kGblocks ? (has_grid ? (size_t)num_grid_blocks() : 0) : (size_t)info.num_voxels;
+    return kEntry[id] * n;
+  }
+  gp::DeviceArray& buckets = arrays[kBuckets].dev;                // gp_voxel_bucket[num_buckets]
+  gp::DeviceArray& records = arrays[kRecords].dev;                // gp::VoxelRecord[num_voxels]   (kernel gather layout)
+  gp::DeviceArray& num_points = arrays[kNumPoints].dev;           // int[num_voxels]               (reference-visible arrays below)
+  gp::DeviceArray& voxel_means = arrays[kMeans].dev;              // float[num_voxels][3]
+  gp::DeviceArray& voxel_covs = arrays[kCovs].dev;                // float[num_voxels][9]
+  gp::DeviceArray& voxel_intensities = arrays[kIntensities].dev;  // float[num_voxels]
+  gp::DeviceArray& voxel_coords = arrays[kCoords].dev;            // int[num_voxels][3] voxel coordinate of each voxel index
+  gp::DeviceArray& gblocks = arrays[kGblocks].dev;                // occupancy-block grid (gp::GridBlock[num_grid_blocks()]); empty when the box is too large
+  // (not in the table: no host copy -- a reload builds it again)
   gp::DeviceArray plines;  // line table of the hashed VGICP kernel family (gp::VoxelMapView::plines): built on first use when the map has its block grid (round 4: its
                            // 16 MB fill and its kernel were 12 us of every map build, for a table no kernel of the default path reads)
   uint32_t plmask = 0;
   bool private_built = false;
   std::mutex private_mutex;    // (batches of several threads may ask at once)
   int ensure_private_table();  // (gp_voxelmap.hip) builds plines on the map's stream and synchronises it; no-op when built
-  gp::DeviceArray gblocks;  // occupancy-block grid (gp::GridBlock[gdim0 * gdim1 * gdim2]); empty when the box is too large
-  int glo[3] = {0, 0, 0}, gdim[3] = {0, 0, 0};
+  gp::GridGeom grid{};  // the box of gblocks
   bool has_grid = false;
+  long long num_grid_blocks() const { return (long long)grid.dim[0] * grid.dim[1] * grid.dim[2]; }
   bool force_hashed_build = false;  // gp_voxelmap_set_tuning(GP_TUNE_MAP_BUILD): the next insert() uses the hashed build
   int bucket_load_percent = 33;     // GP_TUNE_BUCKET_LOAD: the binned build enters the reference's doubling sequence at the first size that holds the voxels at this load factor
 
-  // offloaded copies (OffloadableGPU)
-  bool offloaded = false;
+  bool offloaded = false;   // OffloadableGPU: the arrays live in arrays[].host
   uint64_t generation = 0;  // bumped whenever the device arrays are (re)allocated: factor tables built from view() go stale
-  std::vector<char> h_buckets, h_records, h_num_points, h_means, h_covs, h_intensities, h_coords, h_gblocks;
 
   bool loaded() const { return buckets.ptr != nullptr && !offloaded; }
   gp::VoxelMapView view() const;

@@ -884,7 +884,7 @@ int64_t gp_vgicp_batch_actual_bytes(gp_vgicp_batch_t* batch) {
     if (std::find(maps.begin(), maps.end(), f->target) == maps.end()) maps.push_back(f->target);
   }
   for (const auto* m : maps)
-    bytes += 64ll * m->info.num_voxels + (m->has_grid && batch->use_grid ? 16ll * m->gdim[0] * m->gdim[1] * m->gdim[2] : 16ll * m->info.num_buckets);
+    bytes += 64ll * m->info.num_voxels + (m->has_grid && batch->use_grid ? 16ll * m->num_grid_blocks() : 16ll * m->info.num_buckets);
   return bytes;
 }
 

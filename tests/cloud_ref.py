@@ -173,7 +173,7 @@ def merge(points_f32, covs_f32, intensities, res):
 
 
 def symmetric_part(covs9):
-    """0.5 (C + C^T) of column-major rows: what the device map keeps of a covariance (csrc/gp_voxelmap.hip, segmented_stats_kernel)"""
+    """0.5 (C + C^T) of column-major rows: what the device map keeps of a covariance (csrc/gp_voxelmap_kernels.hpp, segmented_stats_kernel)"""
     c = np.asarray(covs9, dtype=np.float64).reshape(-1, 3, 3)
     return (0.5 * (c + c.transpose(0, 2, 1))).reshape(-1, 9)
 

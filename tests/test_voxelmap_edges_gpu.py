@@ -390,3 +390,41 @@ def test_h_offload_reload_and_clone_are_bit_identical(gpu, build):
     if rc != 0:
         pytest.skip("gp_voxelmap_clone_to_device refuses a clone to the map's own device: " + gpu.load().gp_last_error().decode())
     same(gpu.GaussianVoxelMapGPU(0.3, _handle=h), "clone to the same device")
+
+
+def test_h_offload_reload_and_clone_without_a_grid_are_bit_identical(gpu):
+    """the same paths for a map WITHOUT a block grid (the "too large" input of test_h_assign_without_a_grid: its line table is built at assign): a reload builds the
+    line table again and a clone copies it, and the hashed kernel family of a VGICP factor on the clone finds every voxel through it"""
+    rng = np.random.default_rng(19)
+    res = 0.5
+    coords = np.unique(rng.integers(-20, 20, size=(300, 3)), axis=0)
+    coords = np.concatenate([coords, coords[:40] + 40000])
+    V = len(coords)
+    means = ((coords + rng.uniform(0.2, 0.8, size=(V, 3))) * res).astype(np.float32)
+    covs6 = np.tile(np.array([0.01, 0, 0, 0.01, 0, 0.01], np.float32), (V, 1))
+    vm, _ = _assign(gpu, res, coords, np.full(V, 4), means, covs6, np.arange(V))
+    assert vm.voxelmap_info.num_voxels == V and _has_grid(gpu, vm) == 0
+    src = gpu.PointCloudGPU(means, np.tile(np.eye(3, dtype=np.float32) * 0.01, (V, 1, 1)))
+    before = [x.copy() for x in vm.download_f64()] + [vm.download()[k].copy() for k in ("buckets", "num_points", "means", "covs", "intensities")]
+    look = vm.lookup(src)
+    np.testing.assert_array_equal(look, np.arange(V))
+
+    def same(m, what):
+        assert _has_grid(gpu, m) == 0, what
+        after = list(m.download_f64()) + [m.download()[k] for k in ("buckets", "num_points", "means", "covs", "intensities")]
+        for x, y in zip(before, after):
+            assert x.tobytes() == y.tobytes(), what
+        assert np.array_equal(m.lookup(src), look), what
+
+    assert vm.offload_gpu() and vm.reload_gpu()
+    same(vm, "offload -> reload")
+    h = C.c_void_p()
+    rc = gpu.load().gp_voxelmap_clone_to_device(vm._h, 0, None, C.byref(h))
+    if rc != 0:
+        pytest.skip("gp_voxelmap_clone_to_device refuses a clone to the map's own device: " + gpu.load().gp_last_error().decode())
+    clone = gpu.GaussianVoxelMapGPU(res, _handle=h)
+    same(clone, "clone to the same device")
+    f = gpu.IntegratedVGICPFactorGPU(0, 1, clone, src)
+    rec = gpu._capi.Linearized6()
+    gpu._capi.check(f._lib.gp_vgicp_factor_linearize(f._h, gpu.types._pose16(np.eye(4)), C.byref(rec)), "linearize")
+    assert gpu.LinearizedSystem6(rec).num_inliers == V

@@ -16,7 +16,7 @@ A helper, not a test; it reads nothing outside the repository and does not use o
   insert        replaces the map: create_bucket_table allocates a new table and insert new arrays, zeroed (gaussian_voxelmap_gpu.cu:217-225,295-296); nothing
                 of an earlier cloud survives.  (The CPU map accumulates; the GPU class is the one restated here.)
 
-What the device stores (csrc/gp_voxelmap.hip): mean_local = float32(sum(p - centre) / n) with centre = (coord + 0.5) * res in f64; download_f64 returns
+What the device stores (csrc/gp_voxelmap_kernels.hpp): mean_local = float32(sum(p - centre) / n) with centre = (coord + 0.5) * res in f64; download_f64 returns
 centre + float64(mean_local); the f32 arrays are float32(centre + sum(p - centre) / n) and float32(cov).  `Map.means_stored` is that first quantity from fsum.
 
 The build's path (csrc/gp_binning.hip bin_points_once): blocks of 4 x 4 x 4 voxels over the bounding box of the valid points; more than 2^24 blocks -> the hashed
@@ -28,7 +28,7 @@ import numpy as np
 
 LIMIT = 1.0e9               # gp_binning.hip point_cell
 MAX_GRID_BLOCKS = 1 << 24   # gp_binning.hpp kMaxGridBlocks
-STATS_BATCH = 512           # gp_voxelmap.hip kStatsBatch
+STATS_BATCH = 512           # gp_voxelmap_kernels.hpp kStatsBatch
 STATS_GROUP = 16            # lanes per voxel = voxels per workgroup of segmented_stats_kernel
 POPULATIONS = (1, 15, 16, 17, 31, 33, 511, 512, 513, 1025, 5000)
 FACE_RESOLUTIONS = (0.5, 0.1, 0.3, 1e-3, 100.0)
