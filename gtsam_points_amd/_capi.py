@@ -252,7 +252,7 @@ _SIGNATURES = {
     "gp_cloud_gather": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "gp_debug_voxelgrid_hooks": (C.c_int, [C.c_int, C.c_int]),
     "gp_debug_sample_hash": (C.c_uint, [C.c_uint64, C.c_uint]),
-    # remove_outliers / filter / sort_by_time: index selections on the device (gp_knn.hip, gp_sampling.hip)
+    # remove_outliers / filter / sort_by_time: index selections on the device (gp_knn.hip, gp_cloud_filter.hip)
     "gp_cloud_mean_neighbor_distances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gp_cloud_mean_neighbor_distances_from": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
     "gp_cloud_inlier_threshold": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.POINTER(C.c_double), C.c_void_p]),

@@ -1,7 +1,6 @@
 // gp_binning.hip -- see gp_binning.hpp
 #include "gp_binning.hpp"
 
-#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 
@@ -313,34 +312,20 @@ __global__ void __launch_bounds__(256) bins_cells_kernel(const unsigned* __restr
 }  // namespace
 
 namespace {
-thread_local int g_inject_sort_faults = 0;  // test hook: the next so many builds of this thread see a faulted sort (gp_debug_inject_sort_fault)
-thread_local bool g_inject_corrupt = false;  // ... whose first tile also leaves garbage keys behind (count < 0)
-thread_local int g_sort_fallbacks = 0;      // builds of this thread that went through the one-class sort
+thread_local SortHooks g_sort_hooks;  // test hooks of this thread's builds (gp_debug_inject_sort_fault: count < 0 = the faulted sort's first tile also leaves garbage keys)
 int bin_points_once(const float* points_dev, int n, double inv_cell, hipStream_t s, PointBins* bins, bool* too_large, int ticket_classes, bool* sort_fault);
 }  // namespace
 
 void inject_sort_faults(int count) {
-  g_inject_sort_faults = count < 0 ? -count : count;
-  g_inject_corrupt = count < 0;
+  g_sort_hooks.inject = count < 0 ? -count : count;
+  g_sort_hooks.corrupt = count < 0;
 }
-int sort_fallbacks() { return g_sort_fallbacks; }
+int sort_fallbacks() { return g_sort_hooks.fallbacks; }
 
+// A fault: a tile of the sort waited for a predecessor that had not even been started (the device did not start workgroups in blockIdx order: gp_sort.hpp).
+// Everything the build derived from the keys is void; it runs again with the single ticket counter, which needs no such order.
 int bin_points(const float* points_dev, int n, double inv_cell, hipStream_t s, PointBins* bins, bool* too_large) {
-  bool fault = false;
-  int classes = kSortTicketClasses;
-  if (g_inject_sort_faults > 0) {
-    g_inject_sort_faults--;
-    classes = -kSortTicketClasses - (g_inject_corrupt ? kSortCorruptHook : 0);
-  }
-  GP_TRY(bin_points_once(points_dev, n, inv_cell, s, bins, too_large, classes, &fault));
-  if (!fault) return GP_OK;
-  // A tile of the sort waited for a predecessor that had not even been started (the device did not start workgroups in blockIdx order: gp_sort.hpp). Everything the
-  // build derived from the keys is void; build again with the single ticket counter, which needs no such order.
-  g_sort_fallbacks++;
-  GP_HIP(hipStreamSynchronize(s));
-  GP_TRY(bin_points_once(points_dev, n, inv_cell, s, bins, too_large, 1, &fault));
-  if (fault) return fail(GP_ERROR_HIP, "bin_points: the radix sort made no progress (one-class form)");
-  return GP_OK;
+  return with_sort_fallback(g_sort_hooks, s, "bin_points", [&](int classes, bool* fault) { return bin_points_once(points_dev, n, inv_cell, s, bins, too_large, classes, fault); });
 }
 
 namespace {
@@ -382,25 +367,12 @@ int bin_points_once(const float* points_dev, int n, double inv_cell, hipStream_t
   GP_TRY(bins->occ_blocks.alloc_pooled(sizeof(int) * (size_t)n, s));  // at most one block per cell
   // the host combines the workgroups' boxes as they arrive (bounded spin, then the stream -- which also surfaces a failed kernel)
   int h_bbox[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  {
-    const volatile int* hs = slots.host;
-    const auto t_wait = std::chrono::steady_clock::now();
-    bool synced = false;
-    for (int w = 0; w < box_wgs; w++) {
-      for (int spins = 0; hs[8 * w + 7] != seq_box; spins++) {
-        if ((spins & 63) == 63 && !synced && std::chrono::steady_clock::now() - t_wait > std::chrono::microseconds(500)) {
-          GP_HIP(hipStreamSynchronize(s));
-          synced = true;
-        } else if (synced && hs[8 * w + 7] != seq_box) {
-          return fail(GP_ERROR_HIP, "bin_points: the bounding-box kernel finished without leaving its boxes");
-        }
-      }
-      for (int a = 0; a < 3; a++) {
-        h_bbox[a] = std::min(h_bbox[a], (int)hs[8 * w + a]);
-        h_bbox[3 + a] = std::max(h_bbox[3 + a], (int)hs[8 * w + 3 + a]);
-      }
+  GP_TRY(slots.collect(box_wgs, seq_box, s, "bin_points", [&](const volatile int* box) {
+    for (int a = 0; a < 3; a++) {
+      h_bbox[a] = std::min(h_bbox[a], (int)box[a]);
+      h_bbox[3 + a] = std::max(h_bbox[3 + a], (int)box[3 + a]);
     }
-  }
+  }));
   if (h_bbox[0] > h_bbox[3]) {  // no finite point at all
     GP_TRY(bins->cell_start.alloc_pooled(sizeof(int), s));
     GP_HIP(hipMemsetAsync(bins->cell_start.ptr, 0, sizeof(int), s));

@@ -404,6 +404,26 @@ struct HostSlots {
     *out = w[d];
     return GP_OK;
   }
+  // the host's half: takes the records of slots [0, workgroups) in order as they arrive and hands each (eight words) to per_slot.  Bounded spin -- the clock is read
+  // every 64 spins --, after 500 us ONE synchronisation of the stream (which also surfaces a failed kernel); a slot that is still stale behind it is an error
+  template <class PerSlot>
+  int collect(int workgroups, int seq, hipStream_t s, const char* who, PerSlot&& per_slot) const {
+    const volatile int* hs = host;
+    const auto t_wait = std::chrono::steady_clock::now();
+    bool synced = false;
+    for (int w = 0; w < workgroups; w++) {
+      for (int spins = 0; hs[8 * w + 7] != seq; spins++) {
+        if ((spins & 63) == 63 && !synced && std::chrono::steady_clock::now() - t_wait > std::chrono::microseconds(500)) {
+          GP_HIP(hipStreamSynchronize(s));
+          synced = true;
+        } else if (synced && hs[8 * w + 7] != seq) {
+          return fail(GP_ERROR_HIP, std::string(who) + ": the bounding-box kernel finished without leaving its boxes");
+        }
+      }
+      per_slot(hs + 8 * w);
+    }
+    return GP_OK;
+  }
 };
 
 void release_side_streams();  // gp_covariance.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks

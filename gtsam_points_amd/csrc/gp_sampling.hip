@@ -15,7 +15,7 @@
 #include <cmath>
 #include <cstdint>
 
-#include "gp_sort.hpp"
+#include "gp_select.hpp"
 
 struct gp_voxelgrid_plan {
   int n = 0;           // points of the cloud
@@ -30,6 +30,7 @@ struct gp_voxelgrid_plan {
 };
 
 namespace gp {
+thread_local SortHooks g_voxelgrid_sort_hooks;  // (gp_sort.hpp)
 namespace {
 
 constexpr double kCoordLimit = 1048576.0;  // 2^20: a coordinate c is kept when 0 <= c + 2^20 <= 2^21 - 1, i.e. -2^20 <= u < 2^20 for c = floor(u)
@@ -267,49 +268,8 @@ __global__ void __launch_bounds__(256) sampling_hash_indices_kernel(const int* _
   const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (i < (size_t)m) keys[i] = sample_hash(seed, (unsigned)indices[i]);
 }
-__global__ void __launch_bounds__(256) sampling_compact_kernel(const int* __restrict__ selected, const int* __restrict__ scan, int n, int* __restrict__ indices_out) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (size_t)n && selected[i]) indices_out[scan[i]] = (int)i;  // scan[i] < number of selected points <= n
-}
 
-inline unsigned blocks_of(size_t elements) { return (unsigned)((elements + 255) / 256); }
-
-thread_local int g_force_wide_keys = 0;  // test hooks (gp_debug_voxelgrid_hooks)
-thread_local int g_inject_faults = 0;
-thread_local int g_fallbacks = 0;
-
-// the four arrays of a pair sort and its state; the sorted pairs end up in (keys_a, vals_a)
-struct PairSort {
-  DeviceArray keys_a, vals_a, keys_b, vals_b, state;
-  int alloc(int n, hipStream_t s, bool with_vals_a) {
-    GP_TRY(keys_a.alloc_pooled(sizeof(unsigned) * (size_t)n, s));
-    GP_TRY(keys_b.alloc_pooled(sizeof(unsigned) * (size_t)n, s));
-    GP_TRY(vals_b.alloc_pooled(sizeof(int) * (size_t)n, s));
-    if (with_vals_a) GP_TRY(vals_a.alloc_pooled(sizeof(int) * (size_t)n, s));
-    GP_TRY(state.alloc_pooled(sizeof(unsigned) * radix_sort_state_words32(n, 32), s));
-    return GP_OK;
-  }
-  int sort(DeviceArray& vals, int n, int key_bits, bool vals_iota, hipStream_t s, int classes) {
-    bool in_b = false;
-    GP_TRY(radix_sort_pairs(keys_a.as<unsigned>(), vals.as<int>(), keys_b.as<unsigned>(), vals_b.as<int>(), n, key_bits, vals_iota, state.as<unsigned>(), false, false, s, &in_b, classes));
-    if (in_b) {
-      keys_a.swap(keys_b);
-      vals.swap(vals_b);
-    }
-    return GP_OK;
-  }
-  void release_on(hipStream_t s) {  // every use was ordered on s
-    keys_a.release_on(s), vals_a.release_on(s), keys_b.release_on(s), vals_b.release_on(s), state.release_on(s);
-  }
-};
-
-int next_ticket_classes() {
-  if (g_inject_faults > 0) {
-    g_inject_faults--;
-    return -kSortTicketClasses;  // gp_sort.hpp: tile 0 raises the fault word as if its wait had expired
-  }
-  return kSortTicketClasses;
-}
+thread_local int g_force_wide_keys = 0;  // test hook (gp_debug_voxelgrid_hooks)
 
 int plan_build_once(gp_voxelgrid_plan* plan, const float* points, int classes, bool* fault) {
   *fault = false;
@@ -337,26 +297,13 @@ int plan_build_once(gp_voxelgrid_plan* plan, const float* points, int classes, b
     ps.release_on(s), scan_state.release_on(s), total.release_on(s), key64.release_on(s);
   };
   long long lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-0x80000000ll, -0x80000000ll, -0x80000000ll}, valid = 0;
-  {
-    const volatile int* hs = slots.host;
-    const auto t_wait = std::chrono::steady_clock::now();
-    bool synced = false;
-    for (int w = 0; w < box_wgs; w++) {
-      for (int spins = 0; hs[8 * w + 7] != seq_box; spins++) {
-        if ((spins & 63) == 63 && !synced && std::chrono::steady_clock::now() - t_wait > std::chrono::microseconds(500)) {
-          GP_HIP(hipStreamSynchronize(s));
-          synced = true;
-        } else if (synced && hs[8 * w + 7] != seq_box) {
-          return fail(GP_ERROR_HIP, "gp_voxelgrid_plan_create: the bounding-box kernel finished without leaving its boxes");
-        }
-      }
-      for (int a = 0; a < 3; a++) {
-        lo[a] = std::min<long long>(lo[a], hs[8 * w + a]);
-        hi[a] = std::max<long long>(hi[a], hs[8 * w + 3 + a]);
-      }
-      valid += hs[8 * w + 6];
+  GP_TRY(slots.collect(box_wgs, seq_box, s, "gp_voxelgrid_plan_create", [&](const volatile int* box) {
+    for (int a = 0; a < 3; a++) {
+      lo[a] = std::min<long long>(lo[a], box[a]);
+      hi[a] = std::max<long long>(hi[a], box[3 + a]);
     }
-  }
+    valid += box[6];
+  }));
   plan->num_valid = (int)valid;
   plan->num_voxels = 0;
   if (valid == 0) {
@@ -422,34 +369,18 @@ int plan_build_once(gp_voxelgrid_plan* plan, const float* points, int classes, b
   return GP_OK;
 }
 
-// selected[] (int[n], 0 / 1) -> indices_out in ascending order; *count on the host (one wait)
-int compact_selected(const DeviceArray& selected, int n, int* indices_out, hipStream_t s, int* count) {
-  DeviceArray scan, scratch;
-  GP_TRY(scan.alloc_pooled(sizeof(int) * (size_t)n, s));
-  GP_TRY(scratch.alloc_pooled(sizeof(int) * scan_scratch_ints(n), s));
-  GP_TRY(exclusive_scan_strided(selected.as<int>(), 1, scan.as<int>(), 1, (long long)n, scratch.as<int>(), s));
-  hipLaunchKernelGGL(sampling_compact_kernel, dim3(blocks_of((size_t)n)), dim3(256), 0, s, (const int*)selected.as<int>(), (const int*)scan.as<int>(), n, indices_out);
-  GP_HIP(hipGetLastError());
-  HostWords hw;
-  GP_TRY(HostWords::get(&hw));
-  GP_TRY(hw.finish(s, scratch.as<int>() + (n + kScanThreads - 1) / kScanThreads, 8));  // (the scan leaves its grand total there: gp_scan.hpp)
-  *count = reinterpret_cast<volatile int*>(hw.host)[8];
-  scan.release_on(s), scratch.release_on(s);
-  if (*count < 0 || *count > n) return fail(GP_ERROR_HIP, "gp_voxelgrid_plan_random_indices: inconsistent selection count");
-  return GP_OK;
-}
-
 int random_indices_once(gp_voxelgrid_plan* plan, double rate, unsigned long long seed, int* indices_out, int* num_selected, int classes, bool* fault) {
   *fault = false;
   const int n = plan->n, m = plan->num_valid;
   hipStream_t s = plan->stream;
-  DeviceArray selected;
+  const char* who = "gp_voxelgrid_plan_random_indices";
+  DeviceArray selected;  // int[n], 0 / 1: the stored flags of the compactions below
   GP_TRY(selected.alloc_pooled(sizeof(int) * (size_t)n, s));
   GP_HIP(hipMemsetAsync(selected.ptr, 0, sizeof(int) * (size_t)n, s));
   if (rate >= 0.99) {  // every valid point (:300-303)
     hipLaunchKernelGGL(sampling_mark_kernel, dim3(blocks_of((size_t)m)), dim3(256), 0, s, (const int*)plan->order.as<int>(), m, selected.as<int>());
     GP_HIP(hipGetLastError());
-    GP_TRY(compact_selected(selected, n, indices_out, s, num_selected));
+    GP_TRY(select_indices(ScanArrayInput{selected.as<int>(), 1}, n, indices_out, s, num_selected, who));
     selected.release_on(s);
     return GP_OK;
   }
@@ -480,7 +411,7 @@ int random_indices_once(gp_voxelgrid_plan* plan, double rate, unsigned long long
                      (const int*)plan->voxel_start.as<int>(), (const int*)plan->order.as<int>(), m, points_per_voxel, selected.as<int>());
   GP_HIP(hipGetLastError());
   int count = 0;
-  GP_TRY(compact_selected(selected, n, indices_out, s, &count));
+  GP_TRY(select_indices(ScanArrayInput{selected.as<int>(), 1}, n, indices_out, s, &count, who));
   if ((size_t)count > max_num_points) {  // :445-449: keep max_num_points of them -- the smallest (hash, point index)
     const int keep = (int)max_num_points;
     hipLaunchKernelGGL(sampling_hash_indices_kernel, dim3(blocks_of((size_t)count)), dim3(256), 0, s, (const int*)indices_out, count, seed, ps.keys_a.as<unsigned>());
@@ -494,189 +425,17 @@ int random_indices_once(gp_voxelgrid_plan* plan, double rate, unsigned long long
       hipLaunchKernelGGL(sampling_mark_kernel, dim3(blocks_of((size_t)keep)), dim3(256), 0, s, (const int*)ps.vals_a.as<int>(), keep, selected.as<int>());
       GP_HIP(hipGetLastError());
     }
-    GP_TRY(compact_selected(selected, n, indices_out, s, &count));
+    GP_TRY(select_indices(ScanArrayInput{selected.as<int>(), 1}, n, indices_out, s, &count, who));
     if (count != keep) return done(fail(GP_ERROR_HIP, "gp_voxelgrid_plan_random_indices: the capped selection lost points"));
   }
   *num_selected = count;
   return done(GP_OK);
 }
 
-// ---- remove_outliers / filter / sort_by_time (point_cloud_cpu_funcs.cpp:459-465, 576-650; point_cloud_cpu.hpp:158-203): indices for sample() ------------------------
-// sum d, sum d^2 and the number of the FINITE entries of d[] (short points carry +inf), in an order fixed by n alone: a workgroup takes a tile of kStatTile entries,
-// lane t its entries t, t + 256, ... in ascending order; the lanes meet in the shuffle tree and the four waves in wave order (gp_corr_factors.hip, store_tile_sums);
-// one workgroup then adds the tiles' partials the same way (lane t: tiles t, t + 256, ...).  No floating-point atomics: two runs give the same bits.
-constexpr int kStatTile = 4096;
-__device__ __forceinline__ void stat_reduce(double sum, double sq, int count, double* __restrict__ out_sums /*[2]*/, int* __restrict__ out_count) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __shared__ double lds[4][2];
-  __shared__ int lds_count[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_xor(sum, off, 64);
-    sq += __shfl_xor(sq, off, 64);
-    count += __shfl_xor(count, off, 64);
-  }
-  if (lane == 0) lds[wave][0] = sum, lds[wave][1] = sq, lds_count[wave] = count;
-  __syncthreads();
-  if (threadIdx.x < 2) out_sums[threadIdx.x] = (lds[0][threadIdx.x] + lds[1][threadIdx.x]) + (lds[2][threadIdx.x] + lds[3][threadIdx.x]);
-  if (threadIdx.x == 2) *out_count = (lds_count[0] + lds_count[1]) + (lds_count[2] + lds_count[3]);
-}
-__global__ void __launch_bounds__(256) stat_tile_kernel(const double* __restrict__ values, int n, double* __restrict__ partial_sums /*[tiles][2]*/, int* __restrict__ partial_counts) {
-  const size_t begin = (size_t)blockIdx.x * kStatTile, end = min(begin + (size_t)kStatTile, (size_t)n);
-  double sum = 0.0, sq = 0.0;
-  int count = 0;
-  for (size_t i = begin + threadIdx.x; i < end; i += 256) {
-    const double d = values[i];
-    if (fabs(d) <= 1.7976931348623157e308) {  // (false for inf and NaN)
-      sum += d;
-      sq += d * d;
-      count++;
-    }
-  }
-  stat_reduce(sum, sq, count, partial_sums + 2 * (size_t)blockIdx.x, partial_counts + blockIdx.x);
-}
-__global__ void __launch_bounds__(256) stat_total_kernel(const double* __restrict__ partial_sums, const int* __restrict__ partial_counts, int tiles, double* __restrict__ out /*[3]*/) {
-  double sum = 0.0, sq = 0.0;
-  int count = 0;
-  for (int t = threadIdx.x; t < tiles; t += 256) {
-    sum += partial_sums[2 * (size_t)t];
-    sq += partial_sums[2 * (size_t)t + 1];
-    count += partial_counts[t];
-  }
-  __shared__ int total_count;
-  stat_reduce(sum, sq, count, out, &total_count);
-  __syncthreads();
-  if (threadIdx.x == 0) out[2] = (double)total_count;
-}
-
-// the flags of the two compactions, as functions of the position (the scan and the scatter both evaluate them: no flag array)
-struct BelowThreshold {
-  const double* values;
-  double thresh;
-  __device__ __forceinline__ int operator()(long long i) const {
-    const double v = values[i];
-    return v < thresh && fabs(v) <= 1.7976931348623157e308;
-  }
-};
-struct MaskSet {
-  const unsigned char* mask;
-  __device__ __forceinline__ int operator()(long long i) const { return mask[i] != 0; }
-};
-template <typename Flag>
-__global__ void __launch_bounds__(256) select_scatter_kernel(const Flag flag, const int* __restrict__ scan, int n, int* __restrict__ indices_out) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (size_t)n && flag((long long)i)) indices_out[scan[i]] = (int)i;  // scan[i] < number of selected entries <= n
-}
-
-// flags -> exclusive scan -> scatter: the selected positions in ascending order; *count on the host (one wait)
-template <typename Flag>
-int select_indices(const Flag& flag, int n, int* indices_out, hipStream_t s, int* count, const char* who) {
-  DeviceArray scan, state, total;
-  GP_TRY(scan.alloc_pooled(sizeof(int) * (size_t)n, s));
-  GP_TRY(state.alloc_pooled(sizeof(unsigned long long) * onepass_state_words(n), s));
-  GP_TRY(total.alloc_pooled(sizeof(int), s));
-  GP_HIP(hipMemsetAsync(state.ptr, 0, sizeof(unsigned long long) * onepass_state_words(n), s));
-  GP_TRY(exclusive_scan_of(flag, scan.as<int>(), (long long)n, total.as<int>(), s, state.as<unsigned long long>()));
-  hipLaunchKernelGGL(select_scatter_kernel<Flag>, dim3(blocks_of((size_t)n)), dim3(256), 0, s, flag, (const int*)scan.as<int>(), n, indices_out);
-  GP_HIP(hipGetLastError());
-  HostWords hw;
-  GP_TRY(HostWords::get(&hw));
-  GP_TRY(hw.finish(s, total.as<int>(), 8));
-  *count = reinterpret_cast<volatile int*>(hw.host)[8];
-  scan.release_on(s), state.release_on(s), total.release_on(s);
-  if (*count < 0 || *count > n) return fail(GP_ERROR_HIP, std::string(who) + ": inconsistent selection count");
-  return GP_OK;
-}
-
-// a 32-bit key that is monotone in the order of the floats: -0 = +0, every NaN the largest key (NaN times go last, among themselves in ascending index)
-__host__ __device__ __forceinline__ unsigned time_sort_key(unsigned bits) {
-  if ((bits & 0x7fffffffu) > 0x7f800000u) return 0xffffffffu;
-  if (bits == 0x80000000u) bits = 0u;
-  return (bits & 0x80000000u) ? ~bits : (bits | 0x80000000u);
-}
-__global__ void __launch_bounds__(256) time_keys_kernel(const float* __restrict__ times, int n, unsigned* __restrict__ keys) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < (size_t)n) keys[i] = time_sort_key(__float_as_uint(times[i]));
-}
-
-int sort_by_time_once(const float* times, int n, int* indices_out, hipStream_t s, int classes, bool* fault) {
-  *fault = false;
-  PairSort ps;
-  GP_TRY(ps.alloc(n, s, false));
-  hipLaunchKernelGGL(time_keys_kernel, dim3(blocks_of((size_t)n)), dim3(256), 0, s, times, n, ps.keys_a.as<unsigned>());
-  GP_HIP(hipGetLastError());
-  bool in_b = false;  // (the caller's array is the sort's value storage: four passes end in it)
-  GP_TRY(radix_sort_pairs(ps.keys_a.as<unsigned>(), indices_out, ps.keys_b.as<unsigned>(), ps.vals_b.as<int>(), n, 32, true, ps.state.as<unsigned>(), false, false, s, &in_b, classes));
-  if (in_b) GP_HIP(hipMemcpyAsync(indices_out, ps.vals_b.ptr, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
-  GP_TRY(radix_sort_fault(ps.state.as<unsigned>(), n, 32, s, fault));  // (waits)
-  ps.release_on(s);
-  return GP_OK;
-}
-
 }  // namespace
 }  // namespace gp
 
 extern "C" {
-
-int gp_cloud_inlier_threshold(const double* mean_dists_dev, int n, double std_thresh, double* stats_host, gp_stream_t stream) {
-  if (n < 0 || n >= (1 << 30) || !stats_host || (n > 0 && !mean_dists_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_inlier_threshold: bad arguments");
-  if (!std::isfinite(std_thresh)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_inlier_threshold: std_thresh must be finite");
-  stats_host[0] = stats_host[1] = stats_host[2] = stats_host[3] = 0.0;
-  if (n == 0) return GP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  const int tiles = (n + gp::kStatTile - 1) / gp::kStatTile;
-  gp::DeviceArray sums, counts;  // double[tiles][2] + the three totals, int[tiles]
-  GP_TRY(sums.alloc_pooled(sizeof(double) * (2 * (size_t)tiles + 4), s));
-  GP_TRY(counts.alloc_pooled(sizeof(int) * (size_t)tiles, s));
-  double* totals = sums.as<double>() + 2 * (size_t)tiles;
-  hipLaunchKernelGGL(gp::stat_tile_kernel, dim3(tiles), dim3(256), 0, s, mean_dists_dev, n, sums.as<double>(), counts.as<int>());
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(gp::stat_total_kernel, dim3(1), dim3(256), 0, s, (const double*)sums.as<double>(), (const int*)counts.as<int>(), tiles, totals);
-  GP_HIP(hipGetLastError());
-  double h[3] = {0.0, 0.0, 0.0};
-  GP_HIP(hipMemcpyAsync(h, totals, sizeof(h), hipMemcpyDeviceToHost, s));
-  GP_HIP(hipStreamSynchronize(s));
-  sums.release_on(s), counts.release_on(s);
-  const double m = h[2];
-  if (m > 0.0) {  // :598-600 with the divisor m: the one-pass variance, not clamped (a negative one gives a NaN threshold, below which nothing lies -- as upstream)
-    const double mean = h[0] / m;
-    const double var = h[1] / m - mean * mean;
-    stats_host[0] = mean;
-    stats_host[1] = var;
-    stats_host[2] = mean + std::sqrt(var) * std_thresh;
-  }
-  stats_host[3] = m;
-  return GP_OK;
-}
-
-int gp_cloud_select_below(const double* values_dev, int n, double thresh, int* indices_out_dev, int* num_selected, gp_stream_t stream) {
-  if (n < 0 || n >= (1 << 30) || !num_selected || (n > 0 && (!values_dev || !indices_out_dev))) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_select_below: bad arguments");
-  *num_selected = 0;
-  if (n == 0) return GP_OK;
-  return gp::select_indices(gp::BelowThreshold{values_dev, thresh}, n, indices_out_dev, (hipStream_t)stream, num_selected, "gp_cloud_select_below");
-}
-
-int gp_cloud_select_mask(const unsigned char* mask_dev, int n, int* indices_out_dev, int* num_selected, gp_stream_t stream) {
-  if (n < 0 || n >= (1 << 30) || !num_selected || (n > 0 && (!mask_dev || !indices_out_dev))) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_select_mask: bad arguments");
-  *num_selected = 0;
-  if (n == 0) return GP_OK;
-  return gp::select_indices(gp::MaskSet{mask_dev}, n, indices_out_dev, (hipStream_t)stream, num_selected, "gp_cloud_select_mask");
-}
-
-int gp_cloud_sort_by_time_indices(const float* times_dev, int n, int* indices_out_dev, gp_stream_t stream) {
-  if (n < 0 || n >= (1 << 30) || (n > 0 && (!times_dev || !indices_out_dev))) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_cloud_sort_by_time_indices: bad arguments");
-  if (n == 0) return GP_OK;
-  hipStream_t s = (hipStream_t)stream;
-  bool fault = false;
-  GP_TRY(gp::sort_by_time_once(times_dev, n, indices_out_dev, s, gp::next_ticket_classes(), &fault));
-  if (fault) {  // as gp_voxelgrid_plan_create: the sort is void; again with the single ticket counter
-    gp::g_fallbacks++;
-    GP_HIP(hipStreamSynchronize(s));
-    GP_TRY(gp::sort_by_time_once(times_dev, n, indices_out_dev, s, 1, &fault));
-    if (fault) return gp::fail(GP_ERROR_HIP, "gp_cloud_sort_by_time_indices: the radix sort made no progress (one-class form)");
-  }
-  return GP_OK;
-}
 
 int gp_voxelgrid_plan_create(const float* points_dev, int num_points, double resolution, gp_stream_t stream, gp_voxelgrid_plan_t** out) {
   if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelgrid_plan_create: out is NULL");
@@ -688,14 +447,9 @@ int gp_voxelgrid_plan_create(const float* points_dev, int num_points, double res
   plan->resolution = resolution;
   plan->stream = (hipStream_t)stream;
   if (num_points > 0) {
-    bool fault = false;
-    int rc = gp::plan_build_once(plan, points_dev, gp::next_ticket_classes(), &fault);
-    if (rc == GP_OK && fault) {
-      // a tile of a sort waited for a workgroup that had not been started (gp_sort.hpp): the build is void; again with the single ticket counter
-      gp::g_fallbacks++;
-      rc = hipStreamSynchronize(plan->stream) == hipSuccess ? gp::plan_build_once(plan, points_dev, 1, &fault) : gp::fail(GP_ERROR_HIP, "gp_voxelgrid_plan_create: synchronisation failed");
-      if (rc == GP_OK && fault) rc = gp::fail(GP_ERROR_HIP, "gp_voxelgrid_plan_create: the radix sort made no progress (one-class form)");
-    }
+    // (a fault: a tile of a sort waited for a workgroup that had not been started (gp_sort.hpp); the build is void and runs again with the single ticket counter)
+    const int rc = gp::with_sort_fallback(gp::g_voxelgrid_sort_hooks, plan->stream, "gp_voxelgrid_plan_create",
+                                          [&](int classes, bool* fault) { return gp::plan_build_once(plan, points_dev, classes, fault); });
     if (rc != GP_OK) {
       (void)hipDeviceSynchronize();
       delete plan;
@@ -746,15 +500,9 @@ int gp_voxelgrid_plan_random_indices(gp_voxelgrid_plan_t* plan, double sampling_
   if (plan->n > 0 && !indices_out_dev) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelgrid_plan_random_indices: NULL array");
   *num_selected = 0;
   if (plan->num_valid == 0) return GP_OK;
-  bool fault = false;
-  GP_TRY(gp::random_indices_once(plan, sampling_rate, seed, indices_out_dev, num_selected, gp::next_ticket_classes(), &fault));
-  if (fault) {
-    gp::g_fallbacks++;
-    GP_HIP(hipStreamSynchronize(plan->stream));
-    GP_TRY(gp::random_indices_once(plan, sampling_rate, seed, indices_out_dev, num_selected, 1, &fault));
-    if (fault) return gp::fail(GP_ERROR_HIP, "gp_voxelgrid_plan_random_indices: the radix sort made no progress (one-class form)");
-  }
-  return GP_OK;
+  return gp::with_sort_fallback(gp::g_voxelgrid_sort_hooks, plan->stream, "gp_voxelgrid_plan_random_indices", [&](int classes, bool* fault) {
+    return gp::random_indices_once(plan, sampling_rate, seed, indices_out_dev, num_selected, classes, fault);
+  });
 }
 
 int gp_voxelgrid_plan_destroy(gp_voxelgrid_plan_t* plan) {
@@ -776,8 +524,8 @@ int gp_cloud_gather(const float* attr_dev, int width, const int* indices_dev, in
 
 int gp_debug_voxelgrid_hooks(int force_wide_keys, int sort_faults) {
   gp::g_force_wide_keys = force_wide_keys;
-  gp::g_inject_faults = sort_faults < 0 ? 0 : sort_faults;
-  return gp::g_fallbacks;
+  gp::g_voxelgrid_sort_hooks.inject = sort_faults < 0 ? 0 : sort_faults;
+  return gp::g_voxelgrid_sort_hooks.fallbacks;
 }
 unsigned gp_debug_sample_hash(unsigned long long seed, unsigned index) { return gp::sample_hash(seed, index); }
 

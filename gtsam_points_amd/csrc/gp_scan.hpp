@@ -1,6 +1,7 @@
-// gp_scan.hpp -- exclusive prefix sum of a strided int array on the device: one launch (decoupled look-back, round 4); the three-launch form (per-block scan,
-// scan of the block sums by one workgroup, add) remains for arrays beyond 2^31 - 4096 entries.  Used by the occupancy-grid build (gp_voxelmap.hip); the arrays are a few
-// 10^4 .. 10^7 entries long and the scan runs once per map build, so it is written for clarity, not tuned.
+// gp_scan.hpp -- exclusive prefix sum of an int sequence on the device in ONE launch (decoupled look-back, round 4): of a strided array, or of a function of the
+// position.  At most 2^31 - 16384 entries.  Used by the occupancy-grid build (gp_voxelmap.hip), the voxel-grid plan and the index selections (gp_sampling.hip,
+// gp_select.hpp); the arrays are a few 10^4 .. 10^7 entries long.  The kernels of the older three-launch form (per-block scan, scan of the block sums by one
+// workgroup, add) remain for the hashed k-NN grid's build, which launches them itself (gp_knn.hip).
 #pragma once
 
 #include "gp_host.hpp"
@@ -170,8 +171,8 @@ __global__ void __launch_bounds__(1024) scan_onepass_kernel(const Input input, c
   }
 }
 
-// scratch: at least ceil(m / 1024) + 1 ints + (one-pass form) 2 * onepass_state_words(m) + 2 ints.  `in` and `out` may alias only when they are the same array with the same
-// stride.  The grand total is left at scratch[ceil(m / 1024)] (both forms).
+// scratch of exclusive_scan_strided: at least ceil(m / 1024) + 1 ints + 2 * onepass_state_words(m) + 2 ints.  `in` and `out` may alias only when they are the same array
+// with the same stride.  The grand total is left at scratch[ceil(m / 1024)].
 inline size_t scan_scratch_ints(long long m) { return (size_t)(m / kScanThreads) + 8 + 2 * onepass_state_words(m) + 2; }
 
 // exclusive scan of input(0 .. m - 1) into out[] (dense), the grand total into *total: one launch.  zeroed_state as below (required).  m <= 2^31 - 16384.
@@ -182,27 +183,24 @@ inline int exclusive_scan_of(const Input& input, int* out, long long m, int* tot
   GP_HIP(hipGetLastError());
   return GP_OK;
 }
-
-// zeroed_state: onepass_state_words(m) words the CALLER has zeroed on `s` (a build that runs several scans zeroes all their states with one fill), or null
-inline int exclusive_scan_strided(const int* in, int in_stride, int* out, int out_stride, long long m, int* scratch, hipStream_t s, unsigned long long* zeroed_state = nullptr) {
+// ... of an array: the kernel is handed the pointer too, so a dense, 16-byte-aligned array is read four entries at a time
+inline int exclusive_scan_of(const ScanArrayInput& input, int* out, long long m, int* total, hipStream_t s, unsigned long long* zeroed_state, int out_stride = 1) {
   if (m <= 0) return GP_OK;
-  const int nb = (int)((m + kScanThreads - 1) / kScanThreads);
-  if (m <= (1ll << 31) - kOnePassTile) {
-    // the state words live behind the total's slot, 8-byte aligned
-    unsigned long long* state = zeroed_state ? zeroed_state : reinterpret_cast<unsigned long long*>(reinterpret_cast<uintptr_t>(scratch + nb + 2 + 1) & ~uintptr_t(7));
-    if (!zeroed_state) GP_HIP(hipMemsetAsync(state, 0, sizeof(unsigned long long) * onepass_state_words(m), s));
-    hipLaunchKernelGGL(scan_onepass_kernel<ScanArrayInput>, dim3((unsigned)((m + kOnePassTile - 1) / kOnePassTile)), dim3(1024), 0, s, ScanArrayInput{in, in_stride}, in,
-                       in_stride, out, out_stride, m, state, scratch + nb);
-    GP_HIP(hipGetLastError());
-    return GP_OK;
-  }
-  hipLaunchKernelGGL(strided_scan_block_kernel<0>, dim3(nb), dim3(kScanThreads), 0, s, in, in_stride, out, out_stride, scratch, m);
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(strided_scan_sums_kernel<0>, dim3(1), dim3(kScanThreads), 0, s, scratch, nb, scratch + nb);
-  GP_HIP(hipGetLastError());
-  hipLaunchKernelGGL(strided_scan_add_kernel<0>, dim3(nb), dim3(kScanThreads), 0, s, out, out_stride, (const int*)scratch, m);
+  hipLaunchKernelGGL(scan_onepass_kernel<ScanArrayInput>, dim3((unsigned)((m + kOnePassTile - 1) / kOnePassTile)), dim3(1024), 0, s, input, input.in, input.stride, out, out_stride, m,
+                     zeroed_state, total);
   GP_HIP(hipGetLastError());
   return GP_OK;
+}
+
+// the array form over one scratch block.  zeroed_state: onepass_state_words(m) words the CALLER has zeroed on `s` (a build that runs several scans zeroes all their
+// states with one fill), or null: the state words then live in the scratch, behind the total's slot, and are zeroed here
+inline int exclusive_scan_strided(const int* in, int in_stride, int* out, int out_stride, long long m, int* scratch, hipStream_t s, unsigned long long* zeroed_state = nullptr) {
+  if (m <= 0) return GP_OK;
+  if (m > (1ll << 31) - kOnePassTile) return fail(GP_ERROR_INVALID_ARGUMENT, "exclusive_scan_strided: at most 2^31 - 16384 entries");
+  const int nb = (int)((m + kScanThreads - 1) / kScanThreads);
+  unsigned long long* state = zeroed_state ? zeroed_state : reinterpret_cast<unsigned long long*>(reinterpret_cast<uintptr_t>(scratch + nb + 2 + 1) & ~uintptr_t(7));  // (8-byte aligned)
+  if (!zeroed_state) GP_HIP(hipMemsetAsync(state, 0, sizeof(unsigned long long) * onepass_state_words(m), s));
+  return exclusive_scan_of(ScanArrayInput{in, in_stride}, out, m, scratch + nb, s, state, out_stride);
 }
 
 }  // namespace gp

@@ -351,4 +351,57 @@ inline int radix_sort_fault(const unsigned* state, int n, int key_bits, hipStrea
   return GP_OK;
 }
 
+// The test hooks of a family of callers (thread-local instances: gp_binning.hip's own, and the voxel-grid plan's, which the cloud filters share): the next `inject`
+// first runs get a negative class count -- tile 0 raises the fault word (corrupt: and leaves garbage keys, kSortCorruptHook) --, `fallbacks` counts the second runs.
+struct SortHooks {
+  int inject = 0;
+  bool corrupt = false;
+  int fallbacks = 0;
+  int first_classes() {
+    if (inject <= 0) return kSortTicketClasses;
+    inject--;
+    return -kSortTicketClasses - (corrupt ? kSortCorruptHook : 0);
+  }
+};
+extern thread_local SortHooks g_voxelgrid_sort_hooks;  // gp_debug_voxelgrid_hooks' (defined in gp_sampling.hip): the plan build, the random selection, the time sort (gp_cloud_filter.hip)
+
+// THE retry rule of every caller: body(classes, &fault) runs once; if it reports a faulted sort, everything it derived from the keys is void: the stream is drained
+// and body runs again with ONE ticket class, which needs no start order.  A second fault is an error.
+template <class Body>
+int with_sort_fallback(SortHooks& hooks, hipStream_t s, const char* who, Body&& body) {
+  bool fault = false;
+  GP_TRY(body(hooks.first_classes(), &fault));
+  if (!fault) return GP_OK;
+  hooks.fallbacks++;
+  GP_HIP(hipStreamSynchronize(s));
+  GP_TRY(body(1, &fault));
+  if (fault) return fail(GP_ERROR_HIP, std::string(who) + ": the radix sort made no progress (one-class form)");
+  return GP_OK;
+}
+
+// the four arrays of a pair sort and its state; the sorted pairs end up in (keys_a, vals_a)
+struct PairSort {
+  DeviceArray keys_a, vals_a, keys_b, vals_b, state;
+  int alloc(int n, hipStream_t s, bool with_vals_a) {
+    GP_TRY(keys_a.alloc_pooled(sizeof(unsigned) * (size_t)n, s));
+    GP_TRY(keys_b.alloc_pooled(sizeof(unsigned) * (size_t)n, s));
+    GP_TRY(vals_b.alloc_pooled(sizeof(int) * (size_t)n, s));
+    if (with_vals_a) GP_TRY(vals_a.alloc_pooled(sizeof(int) * (size_t)n, s));
+    GP_TRY(state.alloc_pooled(sizeof(unsigned) * radix_sort_state_words32(n, 32), s));
+    return GP_OK;
+  }
+  int sort(DeviceArray& vals, int n, int key_bits, bool vals_iota, hipStream_t s, int classes) {
+    bool in_b = false;
+    GP_TRY(radix_sort_pairs(keys_a.as<unsigned>(), vals.as<int>(), keys_b.as<unsigned>(), vals_b.as<int>(), n, key_bits, vals_iota, state.as<unsigned>(), false, false, s, &in_b, classes));
+    if (in_b) {
+      keys_a.swap(keys_b);
+      vals.swap(vals_b);
+    }
+    return GP_OK;
+  }
+  void release_on(hipStream_t s) {  // every use was ordered on s
+    keys_a.release_on(s), vals_a.release_on(s), keys_b.release_on(s), vals_b.release_on(s), state.release_on(s);
+  }
+};
+
 }  // namespace gp

@@ -880,12 +880,12 @@ int gp_voxelgrid_plan_random_indices(gp_voxelgrid_plan_t* plan, double sampling_
 int gp_voxelgrid_plan_destroy(gp_voxelgrid_plan_t* plan);
 int gp_cloud_gather(const float* attr_dev, int width, const int* indices_dev, int num_indices, float* out_dev, gp_stream_t stream);
 /* test hooks (thread-local, no device state): force_wide_keys != 0 makes every plan of this thread take the two-sort route (the one a bounding box of more than
- * 2^32 - 1 cells takes); the next `sort_faults` plan builds / index selections see their first sort report an expired wait and must run again through the one-class
+ * 2^32 - 1 cells takes); the next `sort_faults` plan builds / index selections / time sorts (gp_cloud_sort_by_time_indices) see their first sort report an expired wait and must run again through the one-class
  * sort.  Returns how many did so far.  gp_debug_sample_hash: the rank value of (seed, point index), host code. */
 int gp_debug_voxelgrid_hooks(int force_wide_keys, int sort_faults);
 unsigned gp_debug_sample_hash(unsigned long long seed, unsigned index);
 
-/* ---- remove_outliers / filter / sort_by_time on the device: index selections for gp_cloud_gather (gp_knn.hip, gp_sampling.hip) ----
+/* ---- remove_outliers / filter / sort_by_time on the device: index selections for gp_cloud_gather (gp_knn.hip, gp_cloud_filter.hip) ----
  * Device counterparts of find_inlier_points / remove_outliers (point_cloud_cpu_funcs.cpp:576-650), filter / filter_by_index (point_cloud_cpu.hpp:158-203) and
  * sort_by_time (point_cloud_cpu_funcs.cpp:459-465); CPU-only upstream.  Each produces int indices; sample() = gp_cloud_gather carries the attributes.
  * mean_neighbor_distances: d_i = (sum_{j < k} |p_nbr(i,j) - p_i|) / k over the k nearest points of the cloud itself (the point is its own first neighbour, distance

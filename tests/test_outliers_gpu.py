@@ -195,7 +195,7 @@ def test_refusals_run_nothing(gpu):
             gpu.find_inlier_points_gpu(frame, **kwargs)
 
 
-@pytest.mark.parametrize("n", [1, 256, 257, 100_003])
+@pytest.mark.parametrize("n", [1, 15, 16, 256, 257, 16_384, 16_385, 100_003])  # (15 / 16: a scan thread's sixteen elements, one short of them; 16 384 / 16 385: one scan tile, one past it)
 def test_filter_keeps_the_masked_rows(gpu, n):
     import torch
 
@@ -270,3 +270,18 @@ def test_sort_by_time(gpu, n):
             assert np.array_equal(idx, np.arange(m))  # already sorted, ties included: the identity (stable)
     with pytest.raises(gpu.GPError):
         gpu.sort_by_time_gpu(make_frame(gpu, attrs, names=("points", "covs")))
+
+
+@pytest.mark.parametrize("n", [257, 5000])  # (5000: more than one sort tile)
+def test_a_faulted_time_sort_is_run_again_with_one_class(gpu, n):
+    """the retry rule the time sort shares with the plan build (gp_sort.hpp, with_sort_fallback): the hook makes tile 0 of the first sort raise the fault word, the host
+    sorts again with one ticket class, the result is the same and the hooks' counter rises by exactly one"""
+    lib = gpu.load()
+    times = times_case(n, seed=n)
+    frame = make_frame(gpu, {"points": np.zeros((n, 3), np.float32), "times": times.reshape(n, 1)}, names=("points", "times"))
+    before = lib.gp_debug_voxelgrid_hooks(0, 1)
+    try:
+        idx = gpu.sort_by_time_gpu(frame).sample_indices_gpu.cpu().numpy()
+    finally:
+        after = lib.gp_debug_voxelgrid_hooks(0, 0)
+    assert np.array_equal(idx, orf.sort_by_time(times)) and after == before + 1

@@ -240,6 +240,12 @@ def test_randomgrid_rate_one_keeps_every_valid_point_in_order(gpu):
         idx = out.sample_indices_gpu.cpu().numpy()
         assert np.array_equal(idx, np.flatnonzero(np.isfinite(cloud).all(1))) and out.num_dropped == 3
         assert out.points_gpu.cpu().numpy().tobytes() == cloud[idx].tobytes()
+    small = full_scan()[:16_385].copy()  # one scan tile and one entry: the stored-flag compaction through its 16-byte loads and its scalar tail
+    small[[0, 15, 16, 9000, 16_383, 16_384]] = np.nan
+    out = gpu.randomgrid_sampling_gpu(make_frame(gpu, {"points": small}, names=("points",)), 0.5, 1.0, seed=4)
+    idx = out.sample_indices_gpu.cpu().numpy()
+    assert np.array_equal(idx, np.flatnonzero(np.isfinite(small).all(1))) and out.num_dropped == 6
+    assert out.points_gpu.cpu().numpy().tobytes() == small[idx].tobytes()
 
 
 def test_randomgrid_is_uniform_inside_a_voxel(gpu):
