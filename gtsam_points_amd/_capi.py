@@ -351,6 +351,13 @@ _SIGNATURES = {
     "gp_ransac_sample_index": (C.c_uint, [C.c_uint64, C.c_uint, C.c_uint, C.c_uint]),
     "gp_ransac_estimate_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_align_points": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_void_p]),
+    # fast global registration: correspondences, tuple test and the graduated non-convexity loop (gp_gnc.hip)
+    "gp_gnc_params_default": (None, [C.c_void_p]),
+    "gp_feature_correspondences": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_int),
+                                             C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_void_p]),
+    "gp_gnc_align_correspondences": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_gnc_estimate_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]),
 }
 
 GP_RANSAC_SCORED, GP_RANSAC_SAMPLE_FAILED, GP_RANSAC_INVALID_FEATURE, GP_RANSAC_POLY_REJECTED, GP_RANSAC_TABOO, GP_RANSAC_SKIPPED = 0, 1, 2, 3, 4, 5
@@ -375,6 +382,27 @@ class RansacResult(C.Structure):
 
 
 assert C.sizeof(RansacParams) == 72 and C.sizeof(RansacResult) == 152
+
+
+class GncParams(C.Structure):
+    """gp_gnc_params (include/gtsam_points_hip.h): GNCParams (registration/graduated_non_convexity.hpp:16-36) without verbose and num_threads; inner_iterations is the
+    reference's innter_iterations"""
+
+    _fields_ = [("max_init_samples", C.c_int), ("reciprocal_check", C.c_int), ("tuple_check", C.c_int), ("max_num_tuples", C.c_int), ("tuple_thresh", C.c_double),
+                ("div_factor", C.c_double), ("max_corr_dist", C.c_double), ("inner_iterations", C.c_int), ("max_iterations", C.c_int), ("dof", C.c_int), ("reserved_", C.c_int),
+                ("seed", C.c_uint64)]
+
+
+class GncTrace(C.Structure):
+    _fields_ = [("mu", C.c_void_p), ("sum_weights", C.c_void_p), ("sum_errors", C.c_void_p), ("num_inliers", C.c_void_p), ("poses", C.c_void_p)]
+
+
+class GncResult(C.Structure):
+    _fields_ = [("T_target_source", C.c_double * 16), ("inlier_rate", C.c_double), ("final_mu", C.c_double), ("num_initial", C.c_int), ("num_correspondences", C.c_int),
+                ("num_alignments", C.c_int), ("swapped", C.c_int)]
+
+
+assert C.sizeof(GncParams) == 64 and C.sizeof(GncResult) == 160
 
 GP_POSE_FACTOR_BETWEEN, GP_POSE_FACTOR_PRIOR = 0, 1
 

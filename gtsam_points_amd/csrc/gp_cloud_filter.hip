@@ -4,6 +4,7 @@
 #include <cstdint>
 
 #include "gp_select.hpp"
+#include "gp_sort.hpp"
 
 namespace gp {
 namespace {

@@ -16,6 +16,7 @@
 #include <cstdint>
 
 #include "gp_select.hpp"
+#include "gp_sort.hpp"
 
 struct gp_voxelgrid_plan {
   int n = 0;           // points of the cloud

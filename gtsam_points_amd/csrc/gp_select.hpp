@@ -1,8 +1,9 @@
-// gp_select.hpp -- what the voxel-grid plan (gp_sampling.hip) and the cloud filters (gp_cloud_filter.hip) share: THE compaction of both -- flags -> exclusive scan ->
-// scatter to ascending indices, the count to the host in one wait.
+// gp_select.hpp -- what the voxel-grid plan (gp_sampling.hip), the cloud filters (gp_cloud_filter.hip) and the correspondences of gp_gnc.hip share: THE compaction of
+// all three -- flags -> exclusive scan -> scatter to ascending indices, the count to the host in one wait.  (Only the scan is needed here: a unit that sorts includes
+// gp_sort.hpp itself.)
 #pragma once
 
-#include "gp_sort.hpp"
+#include "gp_scan.hpp"
 
 namespace gp {
 

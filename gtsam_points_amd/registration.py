@@ -1,10 +1,12 @@
-"""Global registration on the device, over the C-ABI (csrc/gp_registration.hip):
+"""Global registration on the device, over the C-ABI (csrc/gp_registration.hip, csrc/gp_gnc.hip):
 
   OccupancyGridGPU           <- ann/fast_occupancy_grid.hpp:51-113 FastOccupancyGrid
   match_features_gpu         <- the 1-NN feature search estimate_pose_ransac runs on its target_features_tree (registration/impl/ransac_impl.hpp:62)
   estimate_pose_ransac_gpu   <- registration/ransac.hpp:41-48 estimate_pose_ransac (impl/ransac_impl.hpp:24-191)
   align_points_se3_gpu       <- registration/alignment.hpp, the weighted N-point overload (alignment.cpp:67-102)
   align_points_4dof_gpu      <- ... (alignment.cpp:104-139)
+  estimate_pose_gnc_gpu      <- registration/graduated_non_convexity.hpp:49-58 estimate_pose_gnc (impl/graduated_non_convexity_impl.hpp:13-201), with its stages alone:
+  find_feature_correspondences_gpu  (impl :27-131: reciprocal matches, tuple test)   gnc_align_correspondences_gpu  (impl :133-198: the loop, one launch)
 
 CPU-only upstream; these are device counterparts, not ports (include/gtsam_points_hip.h states what is and is not reproduced: the occupancy SET and every
 per-hypothesis rule are the reference's, the random numbers and the order in which hypotheses compete are this library's own and deterministic).
@@ -179,6 +181,11 @@ class RegistrationResult:
     best_inliers: int = 0
     num_scored: int = 0
     early_stopped: bool = False
+    num_initial: int = 0  # (these five: estimate_pose_gnc_gpu's)
+    num_correspondences: int = 0
+    num_alignments: int = 0
+    final_mu: float = 0.0
+    swapped: bool = False
 
 
 @dataclass
@@ -298,3 +305,167 @@ def align_points_se3_gpu(target_points, source_points, weights=None, device="cud
 def align_points_4dof_gpu(target_points, source_points, weights=None, device="cuda:0", stream=None):
     """align_points_4dof (alignment.cpp:104-139): translation and a rotation about z only, from the 2x2 block of the weighted cross-covariance"""
     return _align(target_points, source_points, weights, 4, device, stream)
+
+
+@dataclass
+class GNCParams:
+    """GNCParams (registration/graduated_non_convexity.hpp:16-36) with the reference's defaults.  inner_iterations is the reference's `innter_iterations`; its num_threads
+    and verbose have no meaning here (return_trace gives what verbose prints)."""
+
+    max_init_samples: int = 5000
+    reciprocal_check: bool = True
+    tuple_check: bool = False
+    tuple_thresh: float = 0.9
+    max_num_tuples: int = 1000
+    div_factor: float = 1.4
+    max_corr_dist: float = 0.25
+    inner_iterations: int = 3
+    max_iterations: int = 64
+    dof: int = 6
+    seed: int = 5489
+
+
+@dataclass
+class GNCTrace:
+    """one row per alignment, device tensors of num_alignments rows: mu float64, sum_weights float64, sum_errors float64, num_inliers int32 (all at the pose before the
+    alignment), poses float64 [.][16] column-major (the pose after it)"""
+
+    mu: object
+    sum_weights: object
+    sum_errors: object
+    num_inliers: object
+    poses: object
+
+
+def _gnc_params(params, what, matching=True, loop=True):
+    p = params if params is not None else GNCParams()
+    if loop and p.dof not in (4, 6):
+        raise _capi.GPError(f"{what}: dof must be 6 or 4, not {p.dof}")
+    if matching and int(p.max_init_samples) < 1:
+        raise _capi.GPError(f"{what}: max_init_samples must be positive")
+    if matching and p.tuple_check and int(p.max_num_tuples) < 1:
+        raise _capi.GPError(f"{what}: max_num_tuples must be positive with tuple_check")
+    if loop and (not float(p.div_factor) > 1.0 or not float(p.max_corr_dist) > 0.0 or int(p.max_iterations) < 1 or int(p.inner_iterations) < 1):
+        raise _capi.GPError(f"{what}: div_factor must be above 1, max_corr_dist, max_iterations and inner_iterations positive")
+    c = _capi.GncParams(int(p.max_init_samples), int(bool(p.reciprocal_check)), int(bool(p.tuple_check)), int(p.max_num_tuples), float(p.tuple_thresh), float(p.div_factor),
+                        float(p.max_corr_dist), int(p.inner_iterations), int(p.max_iterations), int(p.dof), 0, int(p.seed) & 0xFFFFFFFFFFFFFFFF)
+    return p, c
+
+
+def _gnc_matching_inputs(target, source, target_features, source_features, params, query_indices, what):
+    """(tp, nt, sp, ns, tf, sf, d, query tensor or None, number of queries)"""
+    import torch
+
+    tp, nt = _points(target, what)
+    sp, ns = _points(source, what)
+    if nt < 1 or ns < 1:
+        raise _capi.GPError(f"{what}: an empty cloud")
+    dev = target.device
+    tf = _features(target_features, dev, what)
+    sf = _features(source_features, dev, what)
+    d = int(tf.shape[1])
+    if int(sf.shape[1]) != d:
+        raise _capi.GPError(f"{what}: target features have {d} dimensions, source features {int(sf.shape[1])}")
+    if d < 1 or d > _capi.GP_FEATURE_MAX_DIM:
+        raise _capi.GPError(f"{what}: D = {d} is outside 1 .. {_capi.GP_FEATURE_MAX_DIM}")
+    if int(tf.shape[0]) != nt or int(sf.shape[0]) != ns:
+        raise _capi.GPError(f"{what}: one feature row per point is expected ({int(tf.shape[0])} / {nt} target, {int(sf.shape[0])} / {ns} source)")
+    nq = ns if ns < nt else nt  # the smaller cloud queries
+    q = None
+    k = min(nq, int(params.max_init_samples))
+    if query_indices is not None:
+        q = torch.as_tensor(query_indices).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        k = int(q.shape[0])
+        if k and (int(q.min()) < 0 or int(q.max()) >= nq):
+            raise IndexError(f"{what}: query index out of range")
+        if k > 1 and not bool((q[1:] > q[:-1]).all()):
+            raise _capi.GPError(f"{what}: query_indices must be ascending and distinct")
+    return tp, nt, sp, ns, tf, sf, d, q, k
+
+
+def _gnc_trace(params, return_trace, dev):
+    import torch
+
+    if not return_trace:
+        return None, None
+    rows = int(params.max_iterations) * int(params.inner_iterations)
+    tr = GNCTrace(torch.zeros(rows, dtype=torch.float64, device=dev), torch.zeros(rows, dtype=torch.float64, device=dev), torch.zeros(rows, dtype=torch.float64, device=dev),
+                  torch.zeros(rows, dtype=torch.int32, device=dev), torch.zeros((rows, 16), dtype=torch.float64, device=dev))
+    return tr, _capi.GncTrace(tr.mu.data_ptr(), tr.sum_weights.data_ptr(), tr.sum_errors.data_ptr(), tr.num_inliers.data_ptr(), tr.poses.data_ptr())
+
+
+def _gnc_result(res, tr):
+    T = np.array(list(res.T_target_source), np.float64).reshape(4, 4).T.copy()
+    out = RegistrationResult(float(res.inlier_rate), T, num_initial=int(res.num_initial), num_correspondences=int(res.num_correspondences),
+                             num_alignments=int(res.num_alignments), final_mu=float(res.final_mu), swapped=bool(res.swapped))
+    if tr is not None:
+        n = out.num_alignments
+        tr = GNCTrace(tr.mu[:n], tr.sum_weights[:n], tr.sum_errors[:n], tr.num_inliers[:n], tr.poses[:n])
+    return out, tr
+
+
+def find_feature_correspondences_gpu(target: PointCloudGPU, source: PointCloudGPU, target_features, source_features, params: GNCParams = None, query_indices=None, stream=None):
+    """The correspondences estimate_pose_gnc starts from (impl :27-131): int32 [M][2] device tensor of (target index, source index).  The smaller cloud queries (the
+    source when size(source) < size(target), otherwise the target, the pairs swapped back); more than max_init_samples query rows are subsampled by the library's
+    stratified rule (include/gtsam_points_hip.h), or query_indices (ascending, distinct, inside the query cloud) are taken instead; with reciprocal_check a pair is kept
+    only when the match's own nearest row is the query; with tuple_check and more than 3 max_num_tuples pairs the tuple test follows.  Deterministic for a seed."""
+    import torch
+
+    what = "find_feature_correspondences_gpu"
+    params, p = _gnc_params(params, what, loop=False)
+    tp, nt, sp, ns, tf, sf, d, q, k = _gnc_matching_inputs(target, source, target_features, source_features, params, query_indices, what)
+    pairs = torch.empty((max(k, 1), 2), dtype=torch.int32, device=target.device)
+    m, initial, swapped = C.c_int(0), C.c_int(0), C.c_int(0)
+    torch.cuda.current_stream(target.device).synchronize()
+    _capi.check(_capi.load().gp_feature_correspondences(_ptr(tp), nt, _ptr(sp), ns, _ptr(tf), _ptr(sf), d, C.byref(p), C.c_void_p(q.data_ptr()) if q is not None else None, k,
+                                                        C.c_void_p(pairs.data_ptr()), C.byref(m), C.byref(initial), C.byref(swapped), stream), "gp_feature_correspondences")
+    return pairs[: m.value]
+
+
+def gnc_align_correspondences_gpu(target: PointCloudGPU, source: PointCloudGPU, pairs, params: GNCParams = None, return_trace=False, stream=None):
+    """The graduated non-convexity loop alone (impl :133-198) on given (target index, source index) pairs, [M][2]: one launch of one workgroup, one wait.  Returns
+    RegistrationResult (and GNCTrace with return_trace).  No pairs: the identity, inlier_rate 0, num_alignments 0."""
+    import torch
+
+    what = "gnc_align_correspondences_gpu"
+    params, p = _gnc_params(params, what, matching=False)
+    tp, nt = _points(target, what)
+    sp, ns = _points(source, what)
+    if nt < 1 or ns < 1:
+        raise _capi.GPError(f"{what}: an empty cloud")
+    dev = target.device
+    pr = torch.as_tensor(pairs).to(device=dev, dtype=torch.int32).reshape(-1, 2).contiguous()
+    m = int(pr.shape[0])
+    if m and (int(pr.min()) < 0 or int(pr[:, 0].max()) >= nt or int(pr[:, 1].max()) >= ns):
+        raise IndexError(f"{what}: pair index out of range")
+    tr, ctr = _gnc_trace(params, return_trace, dev)
+    res = _capi.GncResult()
+    torch.cuda.current_stream(dev).synchronize()
+    _capi.check(_capi.load().gp_gnc_align_correspondences(_ptr(tp), nt, _ptr(sp), ns, _ptr(pr), m, C.byref(p), C.byref(ctr) if ctr is not None else None, C.byref(res), stream),
+                "gp_gnc_align_correspondences")
+    out, tr = _gnc_result(res, tr)
+    return (out, tr) if return_trace else out
+
+
+def estimate_pose_gnc_gpu(target: PointCloudGPU, source: PointCloudGPU, target_features, source_features, params: GNCParams = None, query_indices=None, return_trace=False,
+                          return_pairs=False, stream=None):
+    """estimate_pose_gnc (Zhou et al., Fast Global Registration): T_target_source from feature matches -- find_feature_correspondences_gpu, then
+    gnc_align_correspondences_gpu on its pairs, in one call.  Features: torch device tensors or numpy arrays [N][D], 1 <= D <= 128.  The reference's three tree
+    arguments have no counterpart (its target tree is unused there too).  inlier_rate is the share of pairs with |t - T s| < 2 max_corr_dist at the pose BEFORE the last
+    alignment, as in the reference (:187).  return_trace / return_pairs: also GNCTrace / the int32 [M][2] pairs, in this order."""
+    import torch
+
+    what = "estimate_pose_gnc_gpu"
+    params, p = _gnc_params(params, what)
+    tp, nt, sp, ns, tf, sf, d, q, k = _gnc_matching_inputs(target, source, target_features, source_features, params, query_indices, what)
+    dev = target.device
+    pairs = torch.empty((max(k, 1), 2), dtype=torch.int32, device=dev) if return_pairs else None
+    tr, ctr = _gnc_trace(params, return_trace, dev)
+    res = _capi.GncResult()
+    torch.cuda.current_stream(dev).synchronize()
+    _capi.check(_capi.load().gp_gnc_estimate_pose(_ptr(tp), nt, _ptr(sp), ns, _ptr(tf), _ptr(sf), d, C.byref(p), C.c_void_p(q.data_ptr()) if q is not None else None, k,
+                                                  C.c_void_p(pairs.data_ptr()) if pairs is not None else None, C.byref(ctr) if ctr is not None else None, C.byref(res), stream),
+                "gp_gnc_estimate_pose")
+    out, tr = _gnc_result(res, tr)
+    extra = ([tr] if return_trace else []) + ([pairs[: out.num_correspondences]] if return_pairs else [])
+    return (out, *extra) if extra else out

@@ -1137,6 +1137,87 @@ int gp_ransac_estimate_pose(const float* target_points_dev, int num_target, cons
 /* the weighted N-point overloads of align_points_se3 / align_points_4dof (alignment.cpp:67-139): points double[N][3] and weights double[N] on the device, the
  * weighted means and H summed in a fixed tree order (no floating-point atomics), the rotation as above; pose_out: host double[16], column-major.  Waits. */
 int gp_align_points(const double* target_points_dev, const double* source_points_dev, const double* weights_dev, int num_points, int dof, double* pose_out, gp_stream_t stream);
+
+/* ---- fast global registration: graduated non-convexity from feature matches (csrc/gp_gnc.hip) ----
+ * Device counterpart of registration/graduated_non_convexity.hpp and impl/graduated_non_convexity_impl.hpp:27-198 (Zhou et al., "Fast Global Registration");
+ * CPU-only upstream.  Every per-correspondence rule is the reference's; the random numbers are this library's (gp_ransac_sample_index) and deterministic for a
+ * seed.  The reference's three tree arguments have no counterpart (its target_tree is unused there too); num_threads and verbose have no meaning here.
+ *
+ * 1. correspondences (impl:27-84)
+ *   query side   the SMALLER cloud queries: num_source < num_target: the source rows are searched among the target's features; otherwise (equal sizes too) the
+ *                target rows are searched among the source's and the pairs are swapped back (:75-80, result `swapped` = 1).  Pairs are always (target, source).
+ *   subsample    a query cloud of n > max_init_samples rows queries K = max_init_samples of them, in ascending order.  THIS LIBRARY'S RULE (the reference shuffles
+ *                with std::mt19937, :37; parity is neither possible nor wanted): stratified, without a sort or a compaction -- for 0 <= j < K
+ *                  lo = floor(j n / K), hi = floor((j + 1) n / K)  (64-bit integers),  index_j = lo + gp_ransac_sample_index(seed, j, 0, hi - lo),
+ *                exactly K distinct ascending indices.  query_indices_dev (int[num_query_indices], ascending, distinct, inside the query cloud: the CALLER's duty)
+ *                replaces the rule and the limit.
+ *   matching     one gp_feature_nn_search with the query indices as rows (its lowest-index tie rule holds); with reciprocal_check a second one the other way
+ *                round, rows = the forward matches: a pair is kept only where the answer is the query index itself (:61-68).  A query without a match (a NaN row) has
+ *                no pair.  GNC has no invalid-feature rule: all-zero rows match like any other.
+ *   compaction   pairs without a match are removed, the order is kept (:82-84); one host wait for the count.
+ * 2. tuple test (:91-131), only if tuple_check and count > 3 max_num_tuples.  Tuple i < max_num_tuples draws the correspondences
+ *   gp_ransac_sample_index(seed, i, k, count), k = 0, 1, 2 (not necessarily distinct: the reference does not require it); each of the three edges is tested as
+ *   ratio = |t_a - t_b| / |s_a - s_b| (norms and quotient plain f64); the tuple is rejected if a ratio < tuple_thresh or > 1 / tuple_thresh (a 0 / 0 ratio is NaN,
+ *   both comparisons are false, the tuple counts as valid: the reference's behaviour).  The pairs of the valid tuples are sorted by source index and made unique by
+ *   source index (:122-123); where the reference's unstable sort leaves the surviving target unspecified, the LOWEST target index survives.
+ * 3. the loop (:133-198), ONE launch of one workgroup and one host wait.  mu starts as the diagonal of the bounding box of the target's points with three finite
+ *   coordinates (f32 widened to f64, sqrt((dx dx + dy dy) + dz dz); 0 without such a point), T as the identity.  for i < max_iterations { inner_iterations
+ *   alignments; mu /= div_factor; if (mu < max_corr_dist) break; } -- the schedule is computed by the kernel itself, in f64, by the same sequence of divisions
+ *   (the reference spells the field innter_iterations, graduated_non_convexity.hpp:28).  One alignment, for every pair j:
+ *     e = |t - T s|^2, T s as ((r0 x + r1 y) + r2 z) + t per row, e = (dx dx + dy dy) + dz dz, no fused multiply-add;  q = mu / (mu + e), w = q q.
+ *     THE REFERENCE'S SHADOWED VARIABLE IS REPRODUCED: the inner-iteration variable j (:150) is shadowed by the correspondence index j (:158), so `i == 0 && j == 0`
+ *     (:165) forces w = 1 only for correspondence 0, during outer iteration 0, in EVERY inner iteration of it.
+ *     sum of w, w t, w s, of e, and the count of e < (2 max_corr_dist)^2; then H = sum w (t - mean_t)(s - mean_s)^T with w recomputed by the same expression; the
+ *     sums are fixed-order trees in LDS (no floating-point atomics: the same input gives the same bits on every run); the pose by the closed forms of
+ *     gp_align_points (dof 6 / 4).  inlier_rate = that count / N of the LAST alignment, that is, at the pose BEFORE it (:187).
+ *   trace (gp_gnc_trace, each pointer a device array of max_iterations * inner_iterations entries, or NULL; filled up to num_alignments): mu, sum_weights,
+ *   sum_errors, num_inliers and the pose AFTER the alignment (double[16] column-major) -- the reference's `verbose` output.
+ *   No correspondences (the reference divides by zero): identity, inlier_rate 0, num_correspondences 0, num_alignments 0, final_mu 0; no launch, no error.
+ * gp_feature_correspondences: stages 1 - 2; pairs_out_dev int[capacity][2] (target, source) on the device, capacity = the number of queries (num_query_indices,
+ *   or min(n, max_init_samples) of the query cloud); *num_pairs on the host.  The point arrays are read by the tuple test only (NULL without tuple_check).  Waits.
+ * gp_gnc_align_correspondences: stage 3 on the caller's pairs (an index outside its cloud is never read: the pair's points become NaN).  Waits once.
+ * gp_gnc_estimate_pose: all three; pairs_out_dev (as above) and trace may be NULL.
+ * GP_ERROR_INVALID_ARGUMENT before any device work: dof outside {4, 6}, dim outside 1 .. 128, an empty cloud, div_factor <= 1 (or NaN), max_corr_dist,
+ * max_iterations or inner_iterations not positive, max_init_samples < 1, tuple_check with max_num_tuples < 1, NULL arrays. */
+typedef struct gp_gnc_params {
+  int max_init_samples;  /* 5000 */
+  int reciprocal_check;  /* 1 */
+  int tuple_check;       /* 0 */
+  int max_num_tuples;    /* 1000 */
+  double tuple_thresh;   /* 0.9 */
+  double div_factor;     /* 1.4 */
+  double max_corr_dist;  /* 0.25 */
+  int inner_iterations;  /* 3 (the reference's innter_iterations) */
+  int max_iterations;    /* 64 */
+  int dof;               /* 6 (SE3) or 4 (XYZ + RZ) */
+  int reserved_;
+  uint64_t seed;         /* 5489 */
+} gp_gnc_params;
+typedef struct gp_gnc_trace {
+  double* mu;
+  double* sum_weights;
+  double* sum_errors;
+  int* num_inliers;
+  double* poses;
+} gp_gnc_trace;
+typedef struct gp_gnc_result {
+  double T_target_source[16];
+  double inlier_rate;
+  double final_mu;          /* mu behind the last division */
+  int num_initial;          /* queries of stage 1 (0 from gp_gnc_align_correspondences) */
+  int num_correspondences;  /* pairs the loop ran on */
+  int num_alignments;
+  int swapped;              /* 1: the target rows were the queries */
+} gp_gnc_result;
+void gp_gnc_params_default(gp_gnc_params* params);
+int gp_feature_correspondences(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const float* target_features_dev,
+                               const float* source_features_dev, int dim, const gp_gnc_params* params, const int* query_indices_dev, int num_query_indices, int* pairs_out_dev,
+                               int* num_pairs, int* num_initial, int* swapped, gp_stream_t stream);
+int gp_gnc_align_correspondences(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const int* pairs_dev, int num_pairs,
+                                 const gp_gnc_params* params, const gp_gnc_trace* trace, gp_gnc_result* result, gp_stream_t stream);
+int gp_gnc_estimate_pose(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const float* target_features_dev,
+                         const float* source_features_dev, int dim, const gp_gnc_params* params, const int* query_indices_dev, int num_query_indices, int* pairs_out_dev,
+                         const gp_gnc_trace* trace, gp_gnc_result* result, gp_stream_t stream);
 #ifdef __cplusplus
 }
 #endif
