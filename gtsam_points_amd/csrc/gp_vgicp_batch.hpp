@@ -1,8 +1,10 @@
-// gp_vgicp_batch.hpp -- the VGICP factor and batch as both halves of the VGICP path see them: gp_vgicp.hip (kernels and their launches) and gp_vgicp_batch.hip
-// (tables, tuning, the arrival protocol of the fused finalize, the C entry points).
+// gp_vgicp_batch.hpp -- the VGICP factor and batch as every unit of the VGICP path sees them: gp_vgicp.hip (kernels and their launches), gp_vgicp_table.hip (tuning,
+// factor / tile tables, pose staging), gp_vgicp_batch.hip (the entry points the product calls; the arrival protocol of the fused finalize is gp_vgicp_arrival.hpp)
+// and gp_vgicp_debug.hip (check hooks and measurement).
 #pragma once
 
 #include <algorithm>
+#include <cstring>
 #include <memory>
 #include <vector>
 
@@ -23,9 +25,9 @@ struct gp_vgicp_tuning {
   bool xcd_weights_set = false;
   int max_wgs = 1024;             // stream family, one large factor: workgroups of the planned launch (<= one resident round of 1024)
   int tile_chunks = 0;            // stream family, batches: 64-point chunks per wave of a tile (tile = 256 x this many points); 0 = the largest of 4 / 2 / 1 that fills 3/4 of the chip
-  int fused_finalize = 1;       // synchronous single-factor linearise of the stream family: the last tile workgroup of each part sums the part's rows
-                                  // and hands them to the host (InlinePoses: fused finalize) -- no finalize launch.  (The first form of this knob, finalize
-                                  // workgroups on a second stream waiting for the counters, cost +10 us per step: profiles/r03_overlap_finalize.jsonl)
+  int fused_finalize = 1;         // synchronous rigid calls of the stream family, single factors and batches: the last tile workgroup of each part of a large factor,
+                                  // or of each factor, sums the rows and hands them to the host (InlinePoses: fused finalize) -- no finalize launch.  (The first form
+                                  // of this knob, finalize workgroups on a second stream waiting for the counters, cost +10 us per step: profiles/r03_overlap_finalize.jsonl)
   int balance = gp::kDefaultSkewPermille;  // stream kernel, one large factor: how much more a dispatch round takes than the next, in 1/1000 of the mean share (0 = flat)
   int source_mirror = 1;          // stream family: stream the sources' packed mirrors (36 B per point, gp::SourceMirror) when every factor of the batch has one; 0 = the caller's arrays
   int far_pose_ratio = GP_FAR_POSE_RATIO_DEFAULT;  // GP_TUNE_FAR_POSE_RATIO: a rigid pose with |t| > this x the source cloud's extent takes the explicit-J_s sums (0 = none does)
@@ -53,6 +55,31 @@ struct gp_vgicp_factor {
   gp_vgicp_tuning tuning;                // what the self batch is created with (gp_vgicp_factor_set_tuning)
 };
 
+// the arrival state of the fused finalize (gp_vgicp_arrival.hpp): the counters the tile workgroups arrive at, what the host believes they read, and the completion
+// words the host polls
+struct gp_vgicp_arrival {
+  gp::DeviceArray d_arrive;               // by part: 16 monotonic arrival counters, kArriveStride words apart
+  unsigned long long arrived[16] = {0};   // ... what they read once every launch issued so far has finished
+  gp::DeviceArray d_factor_arrive;        // by factor: one counter per factor, kFactorArriveStride words apart, zero between launches
+  size_t factor_arrive_count = 0;
+  bool factor_arrive_dirty = false;       // a by-factor fused launch went out and has not been seen to complete: the zero-reset counters may be anywhere (ADVICE r03)
+  gp::PinnedArray h_done;  // one completion word per factor, written by the finalize kernel behind its record (synchronous calls poll it)
+  void* h_done_dev = nullptr;
+  unsigned long long seq = 0;
+  bool dev_error_fused = false;  // gp_vgicp_batch_issue_compute_error_dev_begin went out in the by-factor fused form
+  const double* dev_error_lin = nullptr;   // ... at these device pose tables: what _end runs the pass again with when the completion words are missing
+  const double* dev_error_eval = nullptr;
+  int drop_error_words = 0;      // test hook (gp_debug_drop_error_words): the next so many fused error evaluations take the "words did not arrive" branch
+};
+
+// what a batch measures about itself (gp_vgicp_debug.hip reads it out).  The events and the trace buffer that the launches themselves touch are the batch's ev / trace.
+struct gp_vgicp_measurement {
+  bool timing = false;  // GP_TUNE_TIMING: the synchronous linearise brackets its two kernels with HIP events (gp_vgicp_batch_last_kernel_ms)
+  float last_tile_ms = 0.f, last_finalize_ms = 0.f;
+  // fused steps: the kernel's own 100 MHz time stamps (gp_vgicp_batch_device_times)
+  double dev_steps = 0.0, dev_stream_ticks = 0.0, dev_kernel_ticks = 0.0;
+};
+
 struct gp_vgicp_batch {
   std::vector<gp_vgicp_factor*> factors;
   hipStream_t stream = nullptr;
@@ -66,17 +93,9 @@ struct gp_vgicp_batch {
   bool planned = false;   // stream kernel, one large factor: the tile list is a balanced StreamPlan (else fixed tiles of tile_points)
   gp::StreamPlan plan{};  // ... how the chunks are dealt (also written into the tile table)
   unsigned long long* trace = nullptr;  // timeline build of the tile kernel: [2048][16] uint64 device buffer (gp_vgicp_batch_set_trace_buffer)
-  // fused finalize (GP_TUNE_FUSED_FINALIZE; synchronous single-factor calls of the stream family)
-  gp::DeviceArray d_arrive;               // 16 monotonic arrival counters, kArriveStride words apart
-  gp::DeviceArray d_factor_arrive;        // fused finalize by factor: one counter per factor, kFactorArriveStride words apart, zero between launches
-  size_t factor_arrive_count = 0;
-  bool factor_arrive_dirty = false;       // a by-factor fused launch went out and has not been seen to complete: the zero-reset counters may be anywhere (ADVICE r03)
-  unsigned long long arrived[16] = {0};   // what the counters read once every launch issued so far has finished
-  bool timing = false;                  // GP_TUNE_TIMING: the synchronous linearise brackets its two kernels with HIP events (gp_vgicp_batch_last_kernel_ms)
-  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-  float last_tile_ms = 0.f, last_finalize_ms = 0.f;
-  // fused steps: the kernel's own 100 MHz time stamps (gp_vgicp_batch_device_times)
-  double dev_steps = 0.0, dev_stream_ticks = 0.0, dev_kernel_ticks = 0.0;
+  hipEvent_t ev[3] = {nullptr, nullptr, nullptr};  // measurement.timing: around the two kernels of a timed linearise (launch_linearize records them)
+  gp_vgicp_arrival arrival;          // fused finalize (GP_TUNE_FUSED_FINALIZE; synchronous rigid calls of the stream family)
+  gp_vgicp_measurement measurement;
   int tile_points = 0;
   int64_t total_points = 0;
   gp::DeviceArray d_factors, d_tiles, d_partials, d_poses;  // d_poses: [2][F][16] (lin, eval)
@@ -91,13 +110,6 @@ struct gp_vgicp_batch {
   hipEvent_t h2d_done = nullptr;  // recorded behind every H2D copy of h_poses; the next staging waits on it
   gp::PinnedArray h_out;  // results land here straight from the finalize kernel (host-mapped, no D2H copy op)
   void* h_out_dev = nullptr;
-  gp::PinnedArray h_done;  // one completion word per factor, written by the finalize kernel behind its record (synchronous calls poll it)
-  void* h_done_dev = nullptr;
-  bool dev_error_fused = false;  // gp_vgicp_batch_issue_compute_error_dev_begin went out in the by-factor fused form
-  const double* dev_error_lin = nullptr;   // ... at these device pose tables: what _end runs the pass again with when the completion words are missing
-  const double* dev_error_eval = nullptr;
-  int drop_error_words = 0;      // test hook (gp_debug_drop_error_words): the next so many fused error evaluations take the "words did not arrive" branch
-  unsigned long long seq = 0;
   bool table_dirty = true;
   std::vector<uint64_t> seen;  // per factor: its generation + its target map's generation when the table was built
 };
@@ -152,5 +164,35 @@ int launch_linearize(gp_vgicp_batch* b, const PoseSource& ps, gp_linearized6* ou
 int launch_error(gp_vgicp_batch* b, const PoseSource& ps, double* out_dev, DoneFlags done = {});
 int launch_finalize_error_parts(hipStream_t stream, const double* partials, int num_rows, int rows_per_part, int parts, double* out_dev, int out_stride, DoneFlags done);
 int launch_source_extent(hipStream_t stream, const float* points, long long count, unsigned* out);  // source_extent_kernel: largest |coordinate| of a cloud (measure_extents)
+
+// what gp_vgicp_table.hip gives the entry-point units (not part of the library's interface)
+#pragma GCC visibility push(hidden)
+int apply_tuning(gp_vgicp_tuning* t, int key, int value);      // one settable GP_TUNE_* key of a factor's or a batch's tuning
+bool read_tuning(const gp_vgicp_tuning& t, int key, int* value);  // ... and one readable key (false: not a readable key of the tuning)
+int build_table(gp_vgicp_batch* b);
+bool table_is_stale(const gp_vgicp_batch* b);
+inline int ensure_table(gp_vgicp_batch* b) { return table_is_stale(b) ? build_table(b) : GP_OK; }
+int ensure_self_batch(gp_vgicp_factor* f);  // the factor's batch of one, its table built
+bool takes_rigid_path(const gp_vgicp_batch* b, const double* poses_host);
+int stage_poses(gp_vgicp_batch* b, const double* lin, const double* eval, PoseSource* ps, bool zero_copy = false);
+// the poses of a single factor in the kernel arguments (table built)
+inline void inline_poses(const gp_vgicp_batch* b, const double* lin, const double* eval, PoseSource* ps) {
+  memcpy(ps->inl.lin, lin, sizeof(double) * 16);
+  if (eval) memcpy(ps->inl.eval, eval, sizeof(double) * 16);
+  ps->inl.factor = b->h_descs[0];
+  ps->inl.tile_points = b->tile_points;
+  ps->inl.use = 1;
+}
+// ... and the poses of any batch in device tables (double[F][16] each; inl.use stays 0)
+inline PoseSource device_poses(const double* lin_dev, const double* eval_dev = nullptr) {
+  PoseSource ps;
+  ps.d_lin = lin_dev, ps.d_eval = eval_dev;
+  return ps;
+}
+// a single rigid factor of at least kFinalizeSplitTiles tiles shares its linearise's finalize among kFinalizeParts workgroups
+inline int linearize_parts(const gp_vgicp_batch* b, bool rigid) {
+  return (b->factors.size() == 1 && rigid && b->num_tiles >= kFinalizeSplitTiles) ? kFinalizeParts : 1;
+}
+#pragma GCC visibility pop
 
 }  // namespace gp

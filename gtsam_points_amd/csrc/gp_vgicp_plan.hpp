@@ -110,6 +110,19 @@ inline int make_stream_plan(int n, int skew_permille, const int* xcd_weights, gp
   return G;
 }
 
+// the tiles of a planned launch in tile-list order (XCD-major), as plan_tile deals them: fn(t, begin, count).  build_table() stores these,
+// gp_debug_stream_plan[_ex] shows them.
+template <class Fn>
+inline void for_each_plan_tile(const gp::StreamPlan& plan, Fn&& fn) {
+  int t = 0;
+  for (int x = 0; x < gp::kNumXCD; x++)
+    for (int q = 0; q < plan.wgs_per_xcd; q++, t++) {
+      int begin = 0, count = 0;
+      gp::plan_tile(gp::plan_fields(plan, x, q), x, q, &begin, &count);
+      fn(t, begin, count);
+    }
+}
+
 // Fixed tiles (every batch, and a single factor below the planning threshold): a factor of n points is cut into tiles of tile_points, the last one partial.
 // build_table() fills the tile table with these, gp_debug_stream_plan_ex shows them.
 inline int fixed_tile_count(int n, int tile_points) { return (n + tile_points - 1) / tile_points; }

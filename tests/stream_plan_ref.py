@@ -2,7 +2,7 @@
 tests/test_stream_edges_gpu.py takes its geometries from CASES).  A helper, not a test.
 
 Restates make_stream_plan (csrc/gp_vgicp_plan.hpp), plan_tile and split_tile (csrc/gp_vgicp_shared.hpp) and the fixed tiles of a factor below the planning
-threshold (build_table, csrc/gp_vgicp_batch.hip).  Written as lists of per-workgroup chunk counts and running sums, not as the closed forms the kernel evaluates:
+threshold (build_table, csrc/gp_vgicp_table.hip).  Written as lists of per-workgroup chunk counts and running sums, not as the closed forms the kernel evaluates:
   * the n // 64 full chunks go to the 8 XCDs in proportion to their weights (whole chunks, largest remainders first);
   * an XCD's gx workgroups come in dispatch rounds of 32: a workgroup of round r in front of the last takes ceil(mean * (1 + skew * ((rounds - 1) / 2 - r))) chunks,
     the last round shares what is left as evenly as it goes (the first ones one more).  A skew that would leave a last round nothing, or less than a third of the
