@@ -358,6 +358,10 @@ _SIGNATURES = {
     "gp_gnc_align_correspondences": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_gnc_estimate_pose": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                        C.c_void_p]),
+    # FPFH descriptors over a fixed-radius search (gp_fpfh.hip)
+    "gp_fpfh_params_default": (None, [C.c_void_p]),
+    "gp_estimate_fpfh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int), C.c_void_p]),
+    "gp_debug_fpfh_phase_times": (C.c_int, [C.c_int, C.POINTER(C.c_double)]),
 }
 
 GP_RANSAC_SCORED, GP_RANSAC_SAMPLE_FAILED, GP_RANSAC_INVALID_FEATURE, GP_RANSAC_POLY_REJECTED, GP_RANSAC_TABOO, GP_RANSAC_SKIPPED = 0, 1, 2, 3, 4, 5
@@ -403,6 +407,16 @@ class GncResult(C.Structure):
 
 
 assert C.sizeof(GncParams) == 64 and C.sizeof(GncResult) == 160
+
+
+class FpfhParams(C.Structure):
+    """gp_fpfh_params (include/gtsam_points_hip.h): FPFHEstimationParams (features/fpfh_estimation.hpp:57-66) without num_threads"""
+
+    _fields_ = [("search_radius", C.c_double), ("max_num_neighbors", C.c_int)]
+
+
+assert C.sizeof(FpfhParams) == 16
+GP_FPFH_DIM = 33
 
 GP_POSE_FACTOR_BETWEEN, GP_POSE_FACTOR_PRIOR = 0, 1
 

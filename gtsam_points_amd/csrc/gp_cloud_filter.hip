@@ -95,7 +95,27 @@ int sort_by_time_once(const float* times, int n, int* indices_out, hipStream_t s
   return GP_OK;
 }
 
+int sort_indices_by_key_once(const unsigned* keys, int n, int key_bits, unsigned* sorted_keys, int* order, hipStream_t s, int classes, bool* fault) {
+  *fault = false;
+  PairSort ps;
+  GP_TRY(ps.alloc(n, s, false));
+  GP_HIP(hipMemcpyAsync(ps.keys_a.ptr, keys, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, s));  // (the passes overwrite their input; a second run needs it again)
+  bool in_b = false;
+  GP_TRY(radix_sort_pairs(ps.keys_a.as<unsigned>(), order, ps.keys_b.as<unsigned>(), ps.vals_b.as<int>(), n, key_bits, true, ps.state.as<unsigned>(), false, false, s, &in_b, classes));
+  GP_HIP(hipMemcpyAsync(sorted_keys, in_b ? ps.keys_b.ptr : ps.keys_a.ptr, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  if (in_b) GP_HIP(hipMemcpyAsync(order, ps.vals_b.ptr, sizeof(int) * (size_t)n, hipMemcpyDeviceToDevice, s));
+  GP_TRY(radix_sort_fault(ps.state.as<unsigned>(), n, key_bits, s, fault));  // (waits)
+  ps.release_on(s);
+  return GP_OK;
+}
+
 }  // namespace
+
+// gp_host.hpp: the stable sort of 0 .. n - 1 by a key array, under the retry rule of every sort here (the voxel-grid plan's hooks govern this one too)
+int sort_indices_by_key(const unsigned* keys_dev, int n, int key_bits, unsigned* sorted_keys_dev, int* order_dev, hipStream_t s, const char* who) {
+  if (n <= 0) return GP_OK;
+  return with_sort_fallback(g_voxelgrid_sort_hooks, s, who, [&](int classes, bool* fault) { return sort_indices_by_key_once(keys_dev, n, key_bits, sorted_keys_dev, order_dev, s, classes, fault); });
+}
 }  // namespace gp
 
 extern "C" {

@@ -427,6 +427,9 @@ struct HostSlots {
 };
 
 void release_side_streams();  // gp_covariance.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
+// gp_cloud_filter.hip, for units that keep the radix sort's kernels out of their own resource remarks (gp_fpfh.hip): order_dev[] = 0 .. n - 1 sorted by the low key_bits
+// (<= 32) of keys_dev[] (read only), stable -- equal keys in ascending index --, sorted_keys_dev[] = the keys in that order; n < 2^30.  Waits for `s`.
+int sort_indices_by_key(const unsigned* keys_dev, int n, int key_bits, unsigned* sorted_keys_dev, int* order_dev, hipStream_t s, const char* who);
 }  // namespace gp
 
 struct gp_point_grid;  // gp_knn_grid.hpp: private to gp_knn.hip and gp_covariance.hip

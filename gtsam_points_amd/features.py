@@ -12,8 +12,10 @@
   IntegratedCTICPFactorGPU / IntegratedCTGICPFactorGPU
                             <- factors/integrated_ct_icp_factor.hpp, integrated_ct_gicp_factor.hpp (CPU-only upstream): two pose keys, one pose per time stamp
   CorrespondenceFactorBatchGPU  any number of the factor types above linearised / evaluated together, the poses in device memory (gp_corr_batch_*)
+  estimate_fpfh_gpu         <- features/fpfh_estimation.hpp:estimate_fpfh (CPU-only upstream): 33-D descriptors over a fixed-radius search, for registration.py
 """
 import ctypes as C
+from dataclasses import dataclass
 
 import numpy as np
 
@@ -124,6 +126,54 @@ def estimate_normals_covariances_gpu(frame: PointCloudGPU, k_neighbors=10, cell_
     frame._host.pop("covs", None)
     _replace_normals(frame, normals)
     return short.value
+
+
+@dataclass
+class FPFHEstimationParams:
+    """FPFHEstimationParams (features/fpfh_estimation.hpp:57-66) with the reference's defaults; num_threads has no meaning here."""
+
+    search_radius: float = 5.0
+    max_num_neighbors: int = 10000
+
+
+def estimate_fpfh_gpu(frame: PointCloudGPU, params: FPFHEstimationParams = None, indices=None, dtype=None, return_spfh=False, stream=None):
+    """estimate_fpfh (features/fpfh_estimation.cpp:196-307) on frame.points_gpu and frame.normals_gpu: a device tensor [M][33], one FPFH row per entry of `indices`
+    (any order, repeats allowed) or per point.  dtype: torch.float32 (the default: what match_features_gpu, estimate_pose_ransac_gpu and estimate_pose_gnc_gpu take,
+    no copy through the host) or torch.float64; the f32 row is the f64 row rounded once.  The neighbourhood is every point strictly within search_radius, the point
+    itself included, cut at max_num_neighbors by the library's walk order (include/gtsam_points_hip.h: the one deviation from the reference's kd-tree order).
+    return_spfh: also (spfh float64 [N][33], num_neighbors int32 [N], num_truncated: the points whose neighbourhood reached max_num_neighbors)."""
+    import torch
+
+    what = "estimate_fpfh_gpu"
+    if frame.points_gpu is None or frame.normals_gpu is None:
+        raise _capi.GPError(f"{what}: the frame has no points or no normals (estimate_normals_gpu)")
+    dtype = torch.float32 if dtype is None else dtype
+    if dtype not in (torch.float32, torch.float64):
+        raise _capi.GPError(f"{what}: dtype must be torch.float32 or torch.float64")
+    p = params if params is not None else FPFHEstimationParams()
+    n = frame.size()
+    if n < 1:
+        raise _capi.GPError(f"{what}: an empty cloud")
+    if not (float(p.search_radius) > 0.0 and np.isfinite(float(p.search_radius))) or int(p.max_num_neighbors) < 1:
+        raise _capi.GPError(f"{what}: search_radius must be finite and positive, max_num_neighbors positive")
+    dev = frame.device
+    idx, m = None, n
+    if indices is not None:
+        idx = torch.as_tensor(indices).to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+        m = int(idx.shape[0])
+        if m and (int(idx.min()) < 0 or int(idx.max()) >= n):
+            raise IndexError(f"{what}: index out of range")
+    out = torch.empty((m, _capi.GP_FPFH_DIM), dtype=dtype, device=dev)
+    spfh = torch.empty((n, _capi.GP_FPFH_DIM), dtype=torch.float64, device=dev) if return_spfh else None
+    num = torch.empty(n, dtype=torch.int32, device=dev) if return_spfh else None
+    cut = C.c_int(0)
+    if m > 0 or return_spfh:
+        cp = _capi.FpfhParams(float(p.search_radius), int(p.max_num_neighbors))
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        GaussianVoxelMapGPU._sync_torch(frame)
+        _capi.check(_capi.load().gp_estimate_fpfh(frame.ptr(frame.points_gpu), frame.ptr(frame.normals_gpu), n, C.byref(cp), ptr(idx), m, ptr(out) if dtype == torch.float64 else None,
+                                                  ptr(out) if dtype == torch.float32 else None, ptr(spfh), ptr(num), C.byref(cut), stream), "gp_estimate_fpfh")
+    return (out, spfh, num, cut.value) if return_spfh else out
 
 
 class IntegratedGICPFactorGPU:

@@ -1218,6 +1218,40 @@ int gp_gnc_align_correspondences(const float* target_points_dev, int num_target,
 int gp_gnc_estimate_pose(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const float* target_features_dev,
                          const float* source_features_dev, int dim, const gp_gnc_params* params, const int* query_indices_dev, int num_query_indices, int* pairs_out_dev,
                          const gp_gnc_trace* trace, gp_gnc_result* result, gp_stream_t stream);
+
+/* ---- FPFH descriptors over a fixed-radius search (csrc/gp_fpfh.hip) ----
+ * Device counterpart of estimate_fpfh (features/fpfh_estimation.hpp:57-66, src/gtsam_points/features/fpfh_estimation.cpp:58-93, :196-307; Rusu et al., "Fast Point
+ * Feature Histograms"); CPU-only upstream.  points_dev, normals_dev: float[n][3] (normals as gp_estimate_normals_* writes them); all arithmetic f64 from there on.
+ *   neighbourhood  every j with d2 = (dx dx + dy dy) + dz dz < search_radius^2, strictly; j = i included.  A point with a non-finite coordinate is nobody's neighbour;
+ *                  its own SPFH / FPFH rows are zero and its num_neighbors is 0.
+ *   truncation     THE ONE DEVIATION from the reference, which keeps the first max_num_neighbors points in its kd-tree's traversal order: here the cell coordinate is
+ *                  floor(coord / search_radius) in f64 (clamped to +-(2^20 - 3)), the 27 cells around the query are walked in ascending (dz, dy, dx) order, dx
+ *                  fastest, the points of a cell in ascending index, and the walk stops after max_num_neighbors accepted points.  Both passes walk by this rule.  It
+ *                  decides anything only where the cap binds.  *num_truncated_out (host, may be NULL): the points with num_neighbors == max_num_neighbors.
+ *   SPFH of k      num_neighbors <= 1: zero.  Otherwise the three 11-bin integer histograms of compute_pair_features(p_k, n_k, p_j, n_j) over every neighbour j != k (by
+ *                  index) -- with its d == 0 zero return, its swap on |angle1| < |angle2| and its zero return when v = (ndp x n1) / |ndp x n1| is not finite --,
+ *                  bin = clamp(floor((f - fmin) / range * 11), 0, 10), fmin = (-pi, -1, -1), range = (2 pi, 2, 2) (a NaN feature: bin 0), times 100.0 / (num_neighbors - 1).
+ *   FPFH of i      num_neighbors <= 1: zero.  Otherwise the sum over the neighbours with d2 != 0 of spfh[j] * (1.0 / d2), times 100.0 / (sum of its first 11 entries):
+ *                  that one normaliser for all 33 entries, as in the reference.  A row whose first 11 entries sum to zero (only coincident copies around) is NaN, as in
+ *                  the reference (0 * inf).  spfh[j] is always j's SPFH over j's own neighbourhood, whether j is requested or not.
+ *   determinism    integer histograms; the f64 sums of the FPFH pass are lane-strided partials added in a fixed tree; no floating-point atomics: the same input gives
+ *                  the same bits.  The sum order is not the reference's (its neighbour order), so rows agree to rounding, not to the bit.
+ * indices_dev: int[num_indices] rows to compute (any order, repeats allowed, inside [0, n): the CALLER's duty), or NULL = all n in order.  Outputs, each a device
+ * array or NULL: fpfh_out_dev double[M][33], fpfh_out_f32_dev float[M][33] (the f64 value rounded once), spfh_out_dev double[n][33], num_neighbors_out_dev int[n].
+ * With both FPFH outputs NULL only the SPFH pass runs.  Waits for the stream before it returns.
+ * GP_ERROR_INVALID_ARGUMENT before any device work: NULL params, points or normals; n < 1 (or >= 2^30); search_radius not finite or <= 0; max_num_neighbors < 1;
+ * num_indices < 0; no output at all. */
+#define GP_FPFH_DIM 33
+typedef struct gp_fpfh_params {
+  double search_radius;  /* 5.0 */
+  int max_num_neighbors; /* 10000 */
+} gp_fpfh_params;
+void gp_fpfh_params_default(gp_fpfh_params* params);
+int gp_estimate_fpfh(const float* points_dev, const float* normals_dev, int n, const gp_fpfh_params* params, const int* indices_dev, int num_indices, double* fpfh_out_dev,
+                     float* fpfh_out_f32_dev, double* spfh_out_dev, int* num_neighbors_out_dev, int* num_truncated_out, gp_stream_t stream);
+/* measurement (scripts/fpfh_time.py): enable != 0 makes this thread's later gp_estimate_fpfh calls time their phases with events; ms_out (double[3] or NULL) receives
+ * the stream time of the grid build, the SPFH pass and the FPFH pass of the last timed call */
+int gp_debug_fpfh_phase_times(int enable, double* ms_out);
 #ifdef __cplusplus
 }
 #endif

@@ -1,7 +1,7 @@
 """Host wall time (every call ends in a synchronisation) of estimate_pose_ransac_gpu on the two golden scans at 5000 iterations, and of its two heavy kernels alone:
 
   target  tests/golden/kitti_00/000000.bin, source 000001.bin (full scans); D = 33 synthetic descriptors: a source row is the row of the nearest target point plus
-          noise for ~60 % of the points, random otherwise (the library takes descriptors as an input; FPFH is out of scope)
+          noise for ~60 % of the points, random otherwise (synthetic, so that the share of good matches is known; real ones come from estimate_fpfh_gpu)
   calls   ransac_5000            RANSACParams() as they are: 5000 iterations in chunks of 1024, early stop at 0.8 of the source
           ransac_5000_no_stop    early_stop_inlier_rate = 2: no chunk is skipped, all 5000 hypotheses are tried
           overlap_batch_1024     OccupancyGridGPU.calc_overlap_batch alone: the source cloud at 1024 poses (one chunk's scoring launch when every hypothesis survives)
