@@ -1,11 +1,11 @@
 // gp_covariance_rows.hpp -- the row-tiled first pass of the covariance estimator (GP_TUNE_KNN_STRUCTURE = 3, an experiment kept with its tests): one wave per
 // occupied cell row scans the rows around it through LDS (covariance_rows_kernel), a second kernel settles the queries whose k nearest are provably among what was
-// kept (covariance_settle_kernel) and lists the rest for the per-lane search.  A part of gp_covariance.hip, which includes it behind covariance_from_neighbours.
+// kept (covariance_settle_kernel) and lists the rest for the per-lane search.  A part of gp_covariance.hip.
 //
 // Replaces (reference, CPU only): the k-NN loop of features/covariance_estimation.cpp:18-53 for the queries it settles.
 #pragma once
 
-#include "gp_knn_search.hpp"
+#include "gp_covariance_point.hpp"
 
 namespace gp {
 

@@ -426,7 +426,14 @@ struct HostSlots {
   }
 };
 
-void release_side_streams();  // gp_covariance.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
+// gp_side_stream.hip (SideStream), for gp_covariance.hip: a stream beside `caller` on the current device whose hardware queue sits on another dispatch pipe (probed once
+// per host thread and device), and the events to fork onto it and join from it.  The handles stay with the library; the caller neither destroys nor keeps them.
+struct SideStreamHandles {
+  hipStream_t stream = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;
+};
+int side_stream_for(hipStream_t caller, SideStreamHandles* out);
+void release_side_streams();  // gp_side_stream.hip (SideStream): what gp_trim_device_cache releases beside the parked blocks
 // gp_cloud_filter.hip, for units that keep the radix sort's kernels out of their own resource remarks (gp_fpfh.hip): order_dev[] = 0 .. n - 1 sorted by the low key_bits
 // (<= 32) of keys_dev[] (read only), stable -- equal keys in ascending index --, sorted_keys_dev[] = the keys in that order; n < 2^30.  Waits for `s`.
 int sort_indices_by_key(const unsigned* keys_dev, int n, int key_bits, unsigned* sorted_keys_dev, int* order_dev, hipStream_t s, const char* who);

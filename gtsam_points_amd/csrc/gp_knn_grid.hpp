@@ -171,6 +171,14 @@ struct gp_point_grid {
     }
     return v;
   }
+  // for an owner that built and searched the structure on `s` alone: every device array goes back to the pool in that stream's order (the destructor returns them in
+  // the order they were allocated with, which is safe only behind a synchronisation of everything that searched: gp_point_grid_destroy)
+  void release_on(hipStream_t s) {
+    for (auto& lv : bin_levels)
+      for (gp::DeviceArray* a : {&lv->bins.blocks, &lv->bins.cell_start, &lv->bins.order, &lv->bins.cell_of, &lv->bins.cell_block, &lv->bins.occ_blocks, &lv->sorted, &lv->super})
+        a->release_on(s);
+    for (auto& lv : levels) lv->arena.release_on(s);
+  }
 };
 
 namespace gp {

@@ -1026,7 +1026,7 @@ int gp_debug_stream_plan_ex(int n, int tile_points, int max_workgroups, int skew
 int gp_debug_multi_gather_plan(const int* shard_of_factor, int num_factors, int num_shards, int width, int64_t* rows_per_shard, int64_t* send_offset_doubles);
 /* gp_estimate_covariances runs its second launch on a low-priority side stream; two streams overlap only when their hardware queues sit on different dispatch pipes, so
  * the library probes (once per host thread and device, beside the first caller stream) up to four candidate streams and keeps the one whose queue does not wait for the caller's grid
- * (gp_covariance.hip, SideStream).  This returns the measured delays in microseconds (< 0 = not probed) and the index of the stream in use beside `caller`. */
+ * (gp_side_stream.hip, SideStream).  This returns the measured delays in microseconds (< 0 = not probed) and the index of the stream in use beside `caller`. */
 int gp_debug_side_stream_probe(gp_stream_t caller, float delays_us[4], int* chosen);
 /* test hooks for the structure builds' sort fallback (gp_sort.hpp / gp_binning.hip; thread-local, no device state): the next `count` builds of this thread (voxel-map
  * insert, k-NN structure) see their first radix sort report "a tile waited for a workgroup that was never started" and must rebuild through the one-class sort;
