@@ -1223,8 +1223,9 @@ int gp_gnc_estimate_pose(const float* target_points_dev, int num_target, const f
  * Device counterpart of estimate_fpfh (features/fpfh_estimation.hpp:57-66, src/gtsam_points/features/fpfh_estimation.cpp:58-93, :196-307; Rusu et al., "Fast Point
  * Feature Histograms"); CPU-only upstream.  points_dev, normals_dev: float[n][3] (normals as gp_estimate_normals_* writes them); all arithmetic f64 from there on.
  *   neighbourhood  every j with d2 = (dx dx + dy dy) + dz dz < search_radius^2, strictly; j = i included.  A point with a non-finite coordinate is nobody's neighbour;
- *                  its own SPFH / FPFH rows are zero and its num_neighbors is 0.
- *   truncation     THE ONE DEVIATION from the reference, which keeps the first max_num_neighbors points in its kd-tree's traversal order: here the cell coordinate is
+ *                  its own SPFH / FPFH rows are zero and its num_neighbors is 0.  That holds for +-inf as for NaN; a finite coordinate of any size (3e38) is an ordinary
+ *                  point, its own only neighbour unless another lies within the radius.
+ *   truncation    THE ONE DEVIATION from the reference, which keeps the first max_num_neighbors points in its kd-tree's traversal order: here the cell coordinate is
  *                  floor(coord / search_radius) in f64 (clamped to +-(2^20 - 3)), the 27 cells around the query are walked in ascending (dz, dy, dx) order, dx
  *                  fastest, the points of a cell in ascending index, and the walk stops after max_num_neighbors accepted points.  Both passes walk by this rule.  It
  *                  decides anything only where the cap binds.  *num_truncated_out (host, may be NULL): the points with num_neighbors == max_num_neighbors.
@@ -1238,7 +1239,9 @@ int gp_gnc_estimate_pose(const float* target_points_dev, int num_target, const f
  *                  the same bits.  The sum order is not the reference's (its neighbour order), so rows agree to rounding, not to the bit.
  * indices_dev: int[num_indices] rows to compute (any order, repeats allowed, inside [0, n): the CALLER's duty), or NULL = all n in order.  Outputs, each a device
  * array or NULL: fpfh_out_dev double[M][33], fpfh_out_f32_dev float[M][33] (the f64 value rounded once), spfh_out_dev double[n][33], num_neighbors_out_dev int[n].
- * With both FPFH outputs NULL only the SPFH pass runs.  Waits for the stream before it returns.
+ * With both FPFH outputs NULL only the SPFH pass runs.  With both set, one call writes both: the f64 array as it would alone, the f32 array those values rounded once.
+ * indices_dev == NULL means all n points whatever num_indices says (0 included): a caller with an empty request passes no FPFH output.
+ * Waits for the stream before it returns.
  * GP_ERROR_INVALID_ARGUMENT before any device work: NULL params, points or normals; n < 1 (or >= 2^30); search_radius not finite or <= 0; max_num_neighbors < 1;
  * num_indices < 0; no output at all. */
 #define GP_FPFH_DIM 33
