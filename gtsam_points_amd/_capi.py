@@ -337,7 +337,7 @@ _SIGNATURES = {
     "gp_ba_factors_feature_hessian": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_debug_sparse_work_lists": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gp_vgicp_batch_time_linearize": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    # FastOccupancyGrid, feature matching, RANSAC and the closed-form alignments (gp_registration.hip)
+    # FastOccupancyGrid (gp_occupancy.hip), feature matching (gp_feature_match.hip), RANSAC and the closed-form alignments (gp_registration.hip)
     "gp_occupancy_grid_create": (C.c_int, [C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_occupancy_grid_destroy": (C.c_int, [C.c_void_p]),
     "gp_occupancy_grid_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(C.c_double)]),

@@ -1,7 +1,8 @@
 // gp_alignment.hpp -- what the registration units (gp_registration.hip: RANSAC and gp_align_points; gp_gnc.hip: graduated non-convexity) share: THE closed forms of
-// align_points_se3 / align_points_4dof (registration/alignment.cpp:11-139) -- rotation_from_H3, rotation_from_H2, pose_from_H --, the outer-product accumulation and
-// the fixed-order tree sum of the weighted N-point alignment, the library's counter-based generator, and the launch of the feature search.  The arithmetic a host
-// restatement reproduces is written without fused multiply-adds: a unit that includes this header switches contraction off first (#pragma clang fp contract(off)).
+// align_points_se3 / align_points_4dof (registration/alignment.cpp:11-139) -- rotation_from_H3, rotation_from_H2, pose_from_H --, the weighted means and the
+// outer-product accumulation of the weighted N-point alignment with its fixed-order tree reduction, the identity pose, and the library's counter-based generator.
+// The arithmetic a host restatement reproduces is written without fused multiply-adds: a unit that includes this header switches contraction off first
+// (#pragma clang fp contract(off)).
 #pragma once
 
 #include <cmath>
@@ -119,7 +120,12 @@ __host__ __device__ inline void pose_from_H(const double* h, const Vec3& mt, con
   pose[15] = 1.0;
 }
 
+__host__ __device__ inline void set_identity16(double* pose) {  // column-major 4x4
+  for (int i = 0; i < 16; i++) pose[i] = i % 5 == 0 ? 1.0 : 0.0;
+}
+
 __device__ __forceinline__ Vec3 point_f64(const float* __restrict__ p, int i) { return {(double)p[3 * (size_t)i], (double)p[3 * (size_t)i + 1], (double)p[3 * (size_t)i + 2]}; }
+__device__ __forceinline__ Vec3 point_f64(const double* __restrict__ p, int i) { return {p[3 * (size_t)i], p[3 * (size_t)i + 1], p[3 * (size_t)i + 2]}; }
 __device__ __forceinline__ Vec3 sub3(const Vec3& a, const Vec3& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
 __device__ __forceinline__ double norm3(const Vec3& a) { return sqrt(dot3(a, a)); }
 __device__ __forceinline__ void add_outer(double* h, double w, const Vec3& t, const Vec3& s) {
@@ -128,19 +134,36 @@ __device__ __forceinline__ void add_outer(double* h, double w, const Vec3& t, co
   h[6] += w * t.z * s.x, h[7] += w * t.z * s.y, h[8] += w * t.z * s.z;
 }
 
-// the tree sum of the one-workgroup alignments (fixed order, no floating-point atomics): lds holds count x kAlignThreads doubles
+// the first pass of a weighted alignment: m[0..6] += w, w t, w s; and the two means from the totals
+__device__ __forceinline__ void add_weighted(double* m, double w, const Vec3& t, const Vec3& s) {
+  m[0] += w;
+  m[1] += w * t.x, m[2] += w * t.y, m[3] += w * t.z;
+  m[4] += w * s.x, m[5] += w * s.y, m[6] += w * s.z;
+}
+struct Means {
+  Vec3 t, s;
+};
+__device__ __forceinline__ Means weighted_means(const double* m) { return {{m[1] / m[0], m[2] / m[0], m[3] / m[0]}, {m[4] / m[0], m[5] / m[0], m[6] / m[0]}}; }
+
+// the tree reduction of the one-workgroup kernels (fixed order, no floating-point atomics): v[count] of every thread -> component k combined over the workgroup by
+// op(k, a, b), in every thread; lds holds count x kAlignThreads doubles
 constexpr int kAlignThreads = 256;
-__device__ __forceinline__ void block_sum(double* lds, double* v, int count) {  // v[count] of every thread -> the totals, in every thread
+template <class Op>
+__device__ __forceinline__ void block_reduce(double* lds, double* v, int count, Op op) {
   __syncthreads();
   for (int k = 0; k < count; k++) lds[k * kAlignThreads + threadIdx.x] = v[k];
   __syncthreads();
   for (int off = kAlignThreads / 2; off > 0; off >>= 1) {
     if ((int)threadIdx.x < off)
-      for (int k = 0; k < count; k++) lds[k * kAlignThreads + threadIdx.x] += lds[k * kAlignThreads + threadIdx.x + off];
+      for (int k = 0; k < count; k++) {
+        const double other = lds[k * kAlignThreads + threadIdx.x + off];
+        lds[k * kAlignThreads + threadIdx.x] = op(k, lds[k * kAlignThreads + threadIdx.x], other);
+      }
     __syncthreads();
   }
   for (int k = 0; k < count; k++) v[k] = lds[k * kAlignThreads];
 }
+__device__ __forceinline__ void block_sum(double* lds, double* v, int count) { block_reduce(lds, v, count, [](int, double a, double b) { return a + b; }); }
 
 // the library's counter-based generator (include/gtsam_points_hip.h, gp_ransac_estimate_pose): draw `draw` of iteration `iteration`, an index below n
 __host__ __device__ __forceinline__ uint64_t ransac_mix(uint64_t z) {
@@ -153,9 +176,5 @@ __host__ __device__ __forceinline__ unsigned ransac_sample_index(uint64_t seed, 
   const uint64_t r = ransac_mix(ransac_mix(seed + G * ((uint64_t)iteration + 1)) + G * ((uint64_t)draw + 1));
   return (unsigned)(((r >> 32) * (uint64_t)n) >> 32);
 }
-
-// gp_registration.hip: one launch of feature_nn_kernel (the contract of gp_feature_nn_search; stop: a device flag read first, or NULL).  Asynchronous on `stream`.
-int launch_feature_nn(const float* target, int nt, const float* query, int num_rows, int dim, const int* rows, int nq, const int* stop, int* out_index, double* out_sq_dist,
-                      hipStream_t stream);
 
 }  // namespace gp

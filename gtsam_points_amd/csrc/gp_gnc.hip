@@ -1,6 +1,6 @@
 // gp_gnc.hip -- fast global registration on the device: reciprocal feature correspondences, the tuple test and the graduated non-convexity loop.  Device counterpart of
 // registration/graduated_non_convexity.hpp and registration/impl/graduated_non_convexity_impl.hpp:27-198; the contract of every entry point is in
-// include/gtsam_points_hip.h.  The matching is gp_registration.hip's feature_nn_kernel, the compaction gp_select.hpp's, the closed forms gp_alignment.hpp's.  f64
+// include/gtsam_points_hip.h.  The matching is gp_feature_match.hip's feature_nn_kernel, the compaction gp_select.hpp's, the closed forms gp_alignment.hpp's.  f64
 // arithmetic on the f32 device points; what a host restatement reproduces to the bit (errors, weights, mu) is written without fused multiply-adds.
 #pragma clang fp contract(off)
 
@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "gp_alignment.hpp"
+#include "gp_feature_match.hpp"
 #include "gp_select.hpp"
 
 namespace gp {
@@ -84,26 +85,18 @@ __global__ __launch_bounds__(256) void gnc_tuple_pairs_kernel(const int* __restr
 // mu's start value: the diagonal of the bounding box of the points with three finite coordinates (:134-140); one workgroup, minima and maxima (any order gives the same)
 __global__ __launch_bounds__(kAlignThreads) void gnc_diameter_kernel(const float* __restrict__ points, int n, double* __restrict__ mu0) {
   __shared__ double lds[6 * kAlignThreads];
-  double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+  double box[6] = {INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  double *lo = box, *hi = box + 3;
   for (int i = threadIdx.x; i < n; i += kAlignThreads) {
     const Vec3 p = point_f64(points, i);
     if (!(fabs(p.x) < INFINITY && fabs(p.y) < INFINITY && fabs(p.z) < INFINITY)) continue;
     lo[0] = fmin(lo[0], p.x), lo[1] = fmin(lo[1], p.y), lo[2] = fmin(lo[2], p.z);
     hi[0] = fmax(hi[0], p.x), hi[1] = fmax(hi[1], p.y), hi[2] = fmax(hi[2], p.z);
   }
-  for (int k = 0; k < 3; k++) lds[k * kAlignThreads + threadIdx.x] = lo[k], lds[(3 + k) * kAlignThreads + threadIdx.x] = hi[k];
-  __syncthreads();
-  for (int off = kAlignThreads / 2; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off)
-      for (int k = 0; k < 3; k++) {
-        lds[k * kAlignThreads + threadIdx.x] = fmin(lds[k * kAlignThreads + threadIdx.x], lds[k * kAlignThreads + threadIdx.x + off]);
-        lds[(3 + k) * kAlignThreads + threadIdx.x] = fmax(lds[(3 + k) * kAlignThreads + threadIdx.x], lds[(3 + k) * kAlignThreads + threadIdx.x + off]);
-      }
-    __syncthreads();
-  }
+  block_reduce(lds, box, 6, [](int k, double a, double b) { return k < 3 ? fmin(a, b) : fmax(a, b); });  // one tree: three minima, three maxima
   if (threadIdx.x == 0) {
-    const double dx = lds[3 * kAlignThreads] - lds[0], dy = lds[4 * kAlignThreads] - lds[kAlignThreads], dz = lds[5 * kAlignThreads] - lds[2 * kAlignThreads];
-    *mu0 = lds[0] <= lds[3 * kAlignThreads] ? sqrt((dx * dx + dy * dy) + dz * dz) : 0.0;
+    const double dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    *mu0 = lo[0] <= hi[0] ? sqrt((dx * dx + dy * dy) + dz * dz) : 0.0;
   }
 }
 
@@ -166,23 +159,21 @@ __global__ __launch_bounds__(kAlignThreads) void gnc_loop_kernel(const float* __
       double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};  // sum w, w t, w s, e, inliers
       for (int c = threadIdx.x; c < n; c += kAlignThreads) {
         const GncPair g = gnc_pair(pairs6, c, r, tr, mu, i == 0 && c == 0);  // (:165: the correspondence index shadows the inner iteration)
-        m[0] += g.w;
-        m[1] += g.w * g.t.x, m[2] += g.w * g.t.y, m[3] += g.w * g.t.z;
-        m[4] += g.w * g.s.x, m[5] += g.w * g.s.y, m[6] += g.w * g.s.z;
+        add_weighted(m, g.w, g.t, g.s);
         m[7] += g.e;
         m[8] += g.e < inlier_thresh_sq ? 1.0 : 0.0;
       }
       block_sum(lds, m, 9);
-      const Vec3 mt{m[1] / m[0], m[2] / m[0], m[3] / m[0]}, ms{m[4] / m[0], m[5] / m[0], m[6] / m[0]};
+      const Means mean = weighted_means(m);
       double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
       for (int c = threadIdx.x; c < n; c += kAlignThreads) {
         const GncPair g = gnc_pair(pairs6, c, r, tr, mu, i == 0 && c == 0);
-        add_outer(h, g.w, sub3(g.t, mt), sub3(g.s, ms));
+        add_outer(h, g.w, sub3(g.t, mean.t), sub3(g.s, mean.s));
       }
       block_sum(lds, h, 9);  // (its first barrier is behind every read of s_pose above)
       rate = m[8] / (double)n;
       if (threadIdx.x == 0) {
-        pose_from_H(h, mt, ms, dof, s_pose);
+        pose_from_H(h, mean.t, mean.s, dof, s_pose);
         if (trace.mu) trace.mu[k] = mu;
         if (trace.sum_weights) trace.sum_weights[k] = m[0];
         if (trace.sum_errors) trace.sum_errors[k] = m[7];
@@ -207,7 +198,7 @@ __global__ __launch_bounds__(kAlignThreads) void gnc_loop_kernel(const float* __
 
 static void identity_result(gp_gnc_result* r) {
   std::memset(r, 0, sizeof(*r));
-  for (int j = 0; j < 16; j += 5) r->T_target_source[j] = 1.0;
+  set_identity16(r->T_target_source);
 }
 
 static int check_clouds(const char* who, int num_target, int num_source, int dof) {

@@ -38,6 +38,9 @@ int hip_fail(hipError_t err, const char* expr, const char* file, int line);
     if (gp_rc__ != GP_OK) return gp_rc__; \
   } while (0)
 
+// workgroups of a one-thread-per-element launch
+inline unsigned blocks_of(size_t elements, unsigned per_block = 256) { return (unsigned)((elements + per_block - 1) / per_block); }
+
 // Per-thread cache of stream-ordered blocks.  hipMallocAsync / hipFreeAsync cost 20-50 us apiece on this stack even when the pool
 // holds the memory, and the structure builds (bin_points, voxel-map insert, k-NN grid) take ~15 scratch arrays each: the allocator
 // calls were 1-2 ms of a 3 ms covariance estimation.  A released block is parked here, tagged with the stream in whose order it

@@ -1,4 +1,4 @@
-// gp_occupancy.hpp -- the occupancy set of gp_registration.hip: device counterpart of FastOccupancyGrid (ann/fast_occupancy_grid.hpp:13-113,
+// gp_occupancy.hpp -- the device side of the occupancy set (gp_occupancy.hip; host side: gp_occupancy_grid.hpp): device counterpart of FastOccupancyGrid (ann/fast_occupancy_grid.hpp:13-113,
 // ann/impl/fast_occupancy_grid_impl.hpp:14-74, src/gtsam_points/ann/fast_occupancy_grid.cpp:12-93).
 //
 // Semantics are the reference's:

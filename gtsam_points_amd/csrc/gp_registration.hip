@@ -1,321 +1,45 @@
-// gp_registration.hip -- global registration on the device: the occupancy set (FastOccupancyGrid), exact feature matching, RANSAC hypotheses and the closed-form
-// alignments.  Device counterparts of ann/fast_occupancy_grid.hpp, registration/impl/ransac_impl.hpp:24-191 and registration/alignment.cpp:11-139; the contract of
-// every entry point is in include/gtsam_points_hip.h.  f64 arithmetic on the f32 device points; the arithmetic a host restatement has to reproduce to the bit (cells,
-// the polygon error, H) is written without fused multiply-adds: contraction is off for the whole unit and fma() is called where one is wanted.
+// gp_registration.hip -- global registration on the device: RANSAC hypotheses and the weighted N-point alignment.  Device counterparts of
+// registration/impl/ransac_impl.hpp:24-191 and registration/alignment.cpp:11-139; the contract of every entry point is in include/gtsam_points_hip.h.  The target's
+// occupancy set is gp_occupancy.hip's (gp_occupancy_grid.hpp), the matching gp_feature_match.hip's, the closed forms and the tree sum gp_alignment.hpp's.  f64
+// arithmetic on the f32 device points; the arithmetic a host restatement has to reproduce to the bit (the polygon error, H) is written without fused multiply-adds:
+// contraction is off for the whole unit and fma() is called where one is wanted.
 #pragma clang fp contract(off)
 
 #include <cmath>
 #include <cstring>
 
 #include "gp_alignment.hpp"
-#include "gp_host.hpp"
-#include "gp_occupancy.hpp"
-
-struct gp_occupancy_grid {
-  double resolution = 1.0;
-  hipStream_t stream = nullptr;
-  gp::DeviceArray keys;      // unsigned long long[slots]
-  gp::DeviceArray words;     // uint32_t[slots][16]
-  gp::DeviceArray counters;  // int[2]: occupied blocks, occupied cells
-  uint32_t slots = 0;
-  int num_blocks = 0;
-  int num_cells = 0;
-  ~gp_occupancy_grid() {  // the arrays are pooled blocks that any stream may take next: the work that reads them finishes first
-    if (keys.ptr) (void)hipStreamSynchronize(stream);
-  }
-  gp::OccupancyView view() const {
-    gp::OccupancyView v;
-    v.keys = keys.as<unsigned long long>();
-    v.words = words.as<uint32_t>();
-    v.mask = slots - 1;
-    v.pad_ = 0;
-    v.inv_resolution = 1.0 / resolution;
-    return v;
-  }
-};
+#include "gp_feature_match.hpp"
+#include "gp_occupancy_grid.hpp"
 
 namespace gp {
 
-static inline unsigned blocks_for(size_t n, unsigned per_block = 256) { return (unsigned)((n + per_block - 1) / per_block); }
+// ---- the weighted N-point alignment ---------------------------------------------------------------------------------------------------------------------------------
 
-struct Pose16 {
-  double m[16];
-};
-static Pose16 pose_or_identity(const double* pose) {
-  Pose16 p;
-  for (int i = 0; i < 16; i++) p.m[i] = pose ? pose[i] : (i % 5 == 0 ? 1.0 : 0.0);
-  return p;
-}
-
-// ---- occupancy set ----------------------------------------------------------------------------------------------------------------------------------------------
-
-// the slot of `key`, claimed if it is new (*claimed = 1); mask + 1 when the table has no room (cannot happen at half load; the caller drops the point)
-__device__ __forceinline__ uint32_t occ_find_or_claim(unsigned long long* keys, uint32_t mask, unsigned long long key, int* claimed) {
-  uint32_t slot = occ_hash(key) & mask;
-  *claimed = 0;
-  for (uint32_t probe = 0; probe <= mask; probe++) {
-    unsigned long long k = keys[slot];
-    if (k == kOccEmpty) {
-      k = atomicCAS(&keys[slot], kOccEmpty, key);
-      if (k == kOccEmpty) {
-        *claimed = 1;
-        return slot;
-      }
-    }
-    if (k == key) return slot;
-    slot = (slot + 1) & mask;
+// in one workgroup: two tree reductions in LDS (fixed order, no floating-point atomics): sum of weights and weighted means, then H
+__global__ __launch_bounds__(kAlignThreads) void align_points_kernel(const double* __restrict__ target, const double* __restrict__ source, const double* __restrict__ weights, int n,
+                                                                     int dof, double* __restrict__ pose_out) {
+  __shared__ double lds[9 * kAlignThreads];
+  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = threadIdx.x; i < n; i += kAlignThreads) add_weighted(m, weights[i], point_f64(target, i), point_f64(source, i));
+  block_sum(lds, m, 7);
+  const Means mean = weighted_means(m);
+  double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+  for (int i = threadIdx.x; i < n; i += kAlignThreads) {
+    const Vec3 t = sub3(point_f64(target, i), mean.t), s = sub3(point_f64(source, i), mean.s);
+    add_outer(h, weights[i], t, s);
   }
-  return mask + 1;
+  block_sum(lds, h, 9);
+  if (threadIdx.x == 0) pose_from_H(h, mean.t, mean.s, dof, pose_out);
 }
 
-__global__ __launch_bounds__(256) void occupancy_insert_kernel(unsigned long long* keys, uint32_t* words, uint32_t mask, double inv_resolution, const float* __restrict__ points,
-                                                               int n, Pose16 pose, int* counters) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const Pose T = load_pose(pose.m);
-  int new_block = 0, new_cell = 0;
-  if (i < n) {
-    unsigned long long key;
-    int bit;
-    if (occ_cell(T, inv_resolution, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], key, bit)) {
-      const uint32_t slot = occ_find_or_claim(keys, mask, key, &new_block);
-      if (slot <= mask) {
-        const uint32_t m = 1u << (bit & 31);
-        new_cell = (atomicOr(&words[(size_t)slot * 16 + (bit >> 5)], m) & m) == 0;
-      }
-    }
-  }
-  const int blocks = wave_sum(new_block), cells = wave_sum(new_cell);
-  if ((threadIdx.x & 63) == 0) {
-    if (blocks) atomicAdd(&counters[0], blocks);
-    if (cells) atomicAdd(&counters[1], cells);
-  }
-}
-
-// moves every block of a table into a larger one (each key is stored once, so a new slot has one writer)
-__global__ __launch_bounds__(256) void occupancy_rehash_kernel(const unsigned long long* __restrict__ old_keys, const uint32_t* __restrict__ old_words, uint32_t old_slots,
-                                                               unsigned long long* keys, uint32_t* words, uint32_t mask) {
-  const uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= old_slots) return;
-  const unsigned long long key = old_keys[i];
-  if (key == kOccEmpty) return;
-  int claimed;
-  const uint32_t slot = occ_find_or_claim(keys, mask, key, &claimed);
-  if (slot > mask) return;
-  for (int w = 0; w < 16; w++) atomicOr(&words[(size_t)slot * 16 + w], old_words[(size_t)i * 16 + w]);
-}
-
-__global__ __launch_bounds__(256) void occupancy_overlaps_kernel(OccupancyView g, const float* __restrict__ points, int n, Pose16 pose, unsigned char* overlaps, int* count) {
-  const int i = blockIdx.x * 256 + threadIdx.x;
-  const Pose T = load_pose(pose.m);
-  int hit = 0;
-  if (i < n) {
-    unsigned long long key;
-    int bit;
-    if (occ_cell(T, g.inv_resolution, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], key, bit)) hit = occ_lookup(g, key, bit);
-    if (overlaps) overlaps[i] = (unsigned char)hit;
-  }
-  if (count) {
-    const int hits = wave_sum(hit);
-    if ((threadIdx.x & 63) == 0 && hits) atomicAdd(count, hits);
-  }
-}
-
-// The scoring kernel: one workgroup = kScorePoints consecutive points of ONE hypothesis; workgroup b serves list slot b / tiles, tile b % tiles.  The pose is a
-// uniform (scalar) load, the cloud (12 B per point) and the table are re-read by every hypothesis from L2 / the infinity cache; the counts are integer atomics,
-// one per wave.  list == NULL: hypothesis = slot.  stop: a device flag read first (RANSAC's early stop); num_list: the number of list entries, on the device.
-constexpr int kScorePoints = 1024;
-__global__ __launch_bounds__(256) void occupancy_overlap_batch_kernel(OccupancyView g, const float* __restrict__ points, int n, const double* __restrict__ poses,
-                                                                      const int* __restrict__ list, const int* __restrict__ num_list, int tiles, const int* __restrict__ stop,
-                                                                      int* __restrict__ counts) {
-  if (stop && *stop) return;
-  const int slot = blockIdx.x / tiles, tile = blockIdx.x - slot * tiles;
-  if (num_list && slot >= *num_list) return;
-  const int h = list ? list[slot] : slot;
-  const Pose T = load_pose(poses + 16 * (size_t)h);
-  int hits = 0;
-#pragma unroll
-  for (int k = 0; k < kScorePoints / 256; k++) {
-    const int i = tile * kScorePoints + k * 256 + threadIdx.x;
-    if (i < n) {
-      unsigned long long key;
-      int bit;
-      if (occ_cell(T, g.inv_resolution, points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], key, bit)) hits += occ_lookup(g, key, bit);
-    }
-  }
-  hits = wave_sum(hits);
-  if ((threadIdx.x & 63) == 0 && hits) atomicAdd(&counts[h], hits);
-}
-
-static int launch_overlap_batch(const gp_occupancy_grid* grid, const float* points, int n, const double* poses_dev, const int* list, const int* num_list, int num_slots,
-                                const int* stop, int* counts, hipStream_t stream) {
-  const int tiles = (n + kScorePoints - 1) / kScorePoints;
-  if ((long long)tiles * num_slots > 0x7fffffffLL) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_overlap_batch: num_poses x ceil(num_points / 1024) exceeds 2^31 - 1");
-  hipLaunchKernelGGL(occupancy_overlap_batch_kernel, dim3((unsigned)(tiles * num_slots)), dim3(256), 0, stream, grid->view(), points, n, poses_dev, list, num_list, tiles, stop,
-                     counts);
-  GP_HIP(hipGetLastError());
-  return GP_OK;
-}
-
-static int grid_reserve(gp_occupancy_grid* g, int extra_points) {
-  const unsigned long long need = 2ull * ((unsigned long long)g->num_blocks + (unsigned long long)extra_points);
-  unsigned long long slots = 64;
-  while (slots < need) slots <<= 1;
-  if (slots <= g->slots) return GP_OK;
-  if (slots > (1ull << 30)) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_insert: the table would exceed 2^30 slots");
-  DeviceArray keys, words;
-  GP_TRY(keys.alloc_pooled(slots * 8, g->stream));
-  GP_TRY(words.alloc_pooled(slots * 64, g->stream));
-  GP_HIP(hipMemsetAsync(keys.ptr, 0xff, slots * 8, g->stream));
-  GP_HIP(hipMemsetAsync(words.ptr, 0, slots * 64, g->stream));
-  if (g->slots && g->num_blocks) {
-    hipLaunchKernelGGL(occupancy_rehash_kernel, dim3(blocks_for(g->slots)), dim3(256), 0, g->stream, g->keys.as<unsigned long long>(), g->words.as<uint32_t>(), g->slots,
-                       keys.as<unsigned long long>(), words.as<uint32_t>(), (uint32_t)(slots - 1));
-    GP_HIP(hipGetLastError());
-  }
-  if (g->slots) GP_HIP(hipStreamSynchronize(g->stream));  // the old table is freed below
-  g->keys.swap(keys);
-  g->words.swap(words);
-  g->slots = (uint32_t)slots;
-  return GP_OK;
-}
-
-// wait: read the counts back (one synchronisation); without it the insert is only queued and num_blocks / num_cells stay as they were
-static int grid_insert(gp_occupancy_grid* g, const float* points, int n, const double* pose, bool wait = true) {
-  if (n == 0) return GP_OK;
-  GP_TRY(grid_reserve(g, n));
-  hipLaunchKernelGGL(occupancy_insert_kernel, dim3(blocks_for(n)), dim3(256), 0, g->stream, g->keys.as<unsigned long long>(), g->words.as<uint32_t>(), g->slots - 1,
-                     1.0 / g->resolution, points, n, pose_or_identity(pose), g->counters.as<int>());
-  GP_HIP(hipGetLastError());
-  if (!wait) return GP_OK;
-  int c[2] = {0, 0};
-  GP_HIP(hipMemcpyAsync(c, g->counters.ptr, sizeof(c), hipMemcpyDeviceToHost, g->stream));
-  GP_HIP(hipStreamSynchronize(g->stream));
-  g->num_blocks = c[0];
-  g->num_cells = c[1];
-  return GP_OK;
-}
-
-static int grid_init(gp_occupancy_grid* g, double resolution, hipStream_t stream, int reserve_points = 0) {
-  g->resolution = resolution;
-  g->stream = stream;
-  GP_TRY(g->counters.alloc_pooled(16, stream));
-  GP_HIP(hipMemsetAsync(g->counters.ptr, 0, 16, stream));
-  return grid_reserve(g, reserve_points);
-}
-
-// ---- feature matching ---------------------------------------------------------------------------------------------------------------------------------------------
-
-// One workgroup = kMatchQueries queries (four per wave), every target row.  The target rows pass through LDS in tiles of 64 (row stride dim | 1 words: the lanes of a
-// wave read one column of 64 rows without bank conflicts for any dim); lane t of each wave holds target t of the tile against its wave's four queries, so a target
-// element read from LDS serves four sums.  Each lane keeps its best (strict <, ascending index: the lowest index among its ties); the wave's 64 are reduced by
-// shuffles, equal distances to the lower index.
-constexpr int kMatchQueries = 16;
-constexpr int kMatchTile = 64;
-__global__ __launch_bounds__(256) void feature_nn_kernel(const float* __restrict__ target, int nt, const float* __restrict__ query, int num_rows, int dim,
-                                                         const int* __restrict__ rows, int nq, const int* __restrict__ stop, int* __restrict__ out_index,
-                                                         double* __restrict__ out_sq_dist) {
-  __shared__ float q_lds[kMatchQueries * GP_FEATURE_MAX_DIM];
-  __shared__ float t_lds[kMatchTile * (GP_FEATURE_MAX_DIM + 1)];
-  if (stop && *stop) return;
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int stride = dim | 1;
-  const int q0 = blockIdx.x * kMatchQueries;
-  for (int q = wave; q < kMatchQueries; q += 4) {
-    const int qi = q0 + q;
-    int row = -1;
-    if (qi < nq) row = rows ? rows[qi] : qi;
-    if (row >= num_rows) row = -1;
-    for (int c = lane; c < dim; c += 64) q_lds[q * GP_FEATURE_MAX_DIM + c] = row >= 0 ? query[(size_t)row * dim + c] : __builtin_nanf("");
-  }
-  double best[4];
-  int best_i[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    best[k] = INFINITY;
-    best_i[k] = -1;
-  }
-  for (int t0 = 0; t0 < nt; t0 += kMatchTile) {
-    __syncthreads();  // the queries are in; the previous tile has been read
-    const int rows_here = min(kMatchTile, nt - t0);
-    for (int r = wave; r < rows_here; r += 4)
-      for (int c = lane; c < dim; c += 64) t_lds[r * stride + c] = target[(size_t)(t0 + r) * dim + c];
-    __syncthreads();
-    if (lane < rows_here) {
-      double acc0 = 0.0, acc1 = 0.0, acc2 = 0.0, acc3 = 0.0;
-      const float* tr = t_lds + lane * stride;
-      const float* qr = q_lds + wave * 4 * GP_FEATURE_MAX_DIM;
-      for (int j = 0; j < dim; j++) {
-        const double tv = (double)tr[j];
-        const double d0 = (double)qr[j] - tv, d1 = (double)qr[GP_FEATURE_MAX_DIM + j] - tv, d2 = (double)qr[2 * GP_FEATURE_MAX_DIM + j] - tv,
-                     d3 = (double)qr[3 * GP_FEATURE_MAX_DIM + j] - tv;
-        acc0 = fma(d0, d0, acc0);
-        acc1 = fma(d1, d1, acc1);
-        acc2 = fma(d2, d2, acc2);
-        acc3 = fma(d3, d3, acc3);
-      }
-      const int ti = t0 + lane;
-      if (acc0 < best[0]) best[0] = acc0, best_i[0] = ti;
-      if (acc1 < best[1]) best[1] = acc1, best_i[1] = ti;
-      if (acc2 < best[2]) best[2] = acc2, best_i[2] = ti;
-      if (acc3 < best[3]) best[3] = acc3, best_i[3] = ti;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; k++) {
-    double d = best[k];
-    int bi = best_i[k];
-    for (int off = 32; off > 0; off >>= 1) {
-      const double od = __shfl_xor(d, off);
-      const int oi = __shfl_xor(bi, off);
-      if (oi >= 0 && (bi < 0 || od < d || (od == d && oi < bi))) d = od, bi = oi;
-    }
-    const int qi = q0 + wave * 4 + k;
-    if (lane == 0 && qi < nq) {
-      out_index[qi] = bi;
-      out_sq_dist[qi] = bi >= 0 ? d : (double)INFINITY;
-    }
-  }
-}
-
-int launch_feature_nn(const float* target, int nt, const float* query, int num_rows, int dim, const int* rows, int nq, const int* stop, int* out_index, double* out_sq_dist,
-                      hipStream_t stream) {  // (declared in gp_alignment.hpp: gp_gnc.hip matches with the same kernel)
-  hipLaunchKernelGGL(feature_nn_kernel, dim3(blocks_for(nq, kMatchQueries)), dim3(256), 0, stream, target, nt, query, num_rows, dim, rows, nq, stop, out_index, out_sq_dist);
-  GP_HIP(hipGetLastError());
-  return GP_OK;
-}
-
-// ---- the closed-form alignments (their closed forms and the tree sum: gp_alignment.hpp) ---------------------------------------------------------------------------------
+// ---- RANSAC -------------------------------------------------------------------------------------------------------------------------------------------------------
 
 // one edge of the polygon pre-rejection (ransac_impl.hpp:81-83)
 __device__ __forceinline__ double poly_edge_error(const Vec3& ta, const Vec3& tb, const Vec3& sa, const Vec3& sb) {
   const double dt = norm3(sub3(ta, tb)), ds = norm3(sub3(sa, sb));
   return fabs(dt - ds) / fmax(fmax(dt, ds), 1e-6);
 }
-
-// the weighted N-point alignment in one workgroup: three tree reductions in LDS (fixed order, no floating-point atomics): sum of weights and weighted means, then H
-__global__ __launch_bounds__(kAlignThreads) void align_points_kernel(const double* __restrict__ target, const double* __restrict__ source, const double* __restrict__ weights, int n,
-                                                                     int dof, double* __restrict__ pose_out) {
-  __shared__ double lds[9 * kAlignThreads];
-  double m[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < n; i += kAlignThreads) {
-    const double w = weights[i];
-    m[0] += w;
-    m[1] += w * target[3 * (size_t)i], m[2] += w * target[3 * (size_t)i + 1], m[3] += w * target[3 * (size_t)i + 2];
-    m[4] += w * source[3 * (size_t)i], m[5] += w * source[3 * (size_t)i + 1], m[6] += w * source[3 * (size_t)i + 2];
-  }
-  block_sum(lds, m, 7);
-  const Vec3 mt{m[1] / m[0], m[2] / m[0], m[3] / m[0]}, ms{m[4] / m[0], m[5] / m[0], m[6] / m[0]};
-  double h[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
-  for (int i = threadIdx.x; i < n; i += kAlignThreads) {
-    const Vec3 t{target[3 * (size_t)i] - mt.x, target[3 * (size_t)i + 1] - mt.y, target[3 * (size_t)i + 2] - mt.z};
-    const Vec3 s{source[3 * (size_t)i] - ms.x, source[3 * (size_t)i + 1] - ms.y, source[3 * (size_t)i + 2] - ms.z};
-    add_outer(h, weights[i], t, s);
-  }
-  block_sum(lds, h, 9);
-  if (threadIdx.x == 0) pose_from_H(h, mt, ms, dof, pose_out);
-}
-
-// ---- RANSAC -------------------------------------------------------------------------------------------------------------------------------------------------------
 
 struct RansacState {
   int stop;        // set behind the chunk whose scored hypotheses cross the early-stop rate
@@ -445,7 +169,9 @@ __global__ __launch_bounds__(256) void ransac_hypothesis_kernel(RansacState* sta
   list[atomicAdd(&state->num_list, 1)] = it;
 }
 
-// behind the chunk's scoring kernel, one workgroup: the chunk's best scored hypothesis (most inliers, lowest iteration) against the best so far, and the early stop
+// behind the chunk's scoring kernel, one workgroup: the chunk's best scored hypothesis (most inliers, lowest iteration) against the best so far, and the early stop.
+// (Its tree is its own: an integer arg-max whose tie rule -- the lowest iteration -- is the comparison below, beside an integer sum and an or; gp_alignment.hpp's
+// block_reduce combines doubles one by one.)
 __global__ __launch_bounds__(256) void ransac_select_kernel(RansacState* state, RansacArrays a, int begin, int count, double stop_above) {
   __shared__ int s_inl[256], s_it[256], s_scored[256], s_stop[256];
   if (state->stop) return;
@@ -480,87 +206,128 @@ __global__ __launch_bounds__(256) void ransac_select_kernel(RansacState* state, 
   }
 }
 
+// ---- host: gp_ransac_estimate_pose in its stages ----------------------------------------------------------------------------------------------------------------------
+
+static int check_ransac(const float* target_points, int num_target, const float* source_points, int num_source, const float* target_features, const float* source_features, int dim,
+                        const gp_ransac_params* p, const gp_ransac_result* result) {
+  if (!p || !result) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: params or result is NULL");
+  if (p->dof != 6 && p->dof != 4) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: dof must be 6 or 4");
+  if (num_source < (p->dof == 6 ? 3 : 2)) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: fewer source points than samples");
+  if (num_target < 1) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: the target is empty");
+  if (dim < 1 || dim > GP_FEATURE_MAX_DIM) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: dim must be 1 .. 128");
+  if (p->num_taboo < 0 || p->num_taboo > GP_RANSAC_MAX_TABOO || (p->num_taboo > 0 && !p->taboo_poses))
+    return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: at most 64 taboo poses");
+  if (p->max_iterations < 1 || p->chunk_iterations < 1) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: max_iterations and chunk_iterations must be positive");
+  if (!(p->inlier_voxel_resolution > 0.0) || !std::isfinite(p->inlier_voxel_resolution))
+    return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: the resolution must be positive and finite");
+  if (!target_points || !source_points || !target_features || !source_features) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: NULL array");
+  return GP_OK;
+}
+
+// what the stages hand on.  The grid comes first: it is destroyed last, and its destructor waits for the stream every array below was used on.
+struct RansacRun {
+  const float *target_points, *source_points, *target_features, *source_features;
+  int num_target, num_source, dim;
+  const gp_ransac_params* params;
+  hipStream_t stream;
+  int H, chunk;  // iterations in all and per chunk
+  gp_occupancy_grid grid;
+  RansacArrays a;  // the caller's arrays, or own[] in the same order
+  DeviceArray own[5], state, rows, matched, dists, list, taboo;
+  RansacState init;               // (the sources of the two queued uploads live as long as the call)
+  std::vector<double> taboo_inv;
+};
+
+template <typename T>
+static int caller_or_own(T* given, size_t count, DeviceArray& own, hipStream_t s, T** out) {
+  if (!given) {
+    GP_TRY(own.alloc_async(sizeof(T) * count, s));
+    given = own.as<T>();
+  }
+  *out = given;
+  return GP_OK;
+}
+
+// stage 1: the per-iteration arrays, each the caller's or the call's own; one chunk's scratch; the state as it is before the first chunk
+static int ransac_arrays(RansacRun& r, const gp_ransac_hypotheses* given) {
+  const gp_ransac_hypotheses g = given ? *given : gp_ransac_hypotheses{};  // (none given: five NULLs)
+  const size_t H = (size_t)r.H, chunk = (size_t)r.chunk;
+  GP_TRY(caller_or_own(g.status, H, r.own[0], r.stream, &r.a.status));
+  GP_TRY(caller_or_own(g.source_indices, 3 * H, r.own[1], r.stream, &r.a.source_indices));
+  GP_TRY(caller_or_own(g.target_indices, 3 * H, r.own[2], r.stream, &r.a.target_indices));
+  GP_TRY(caller_or_own(g.poses, 16 * H, r.own[3], r.stream, &r.a.poses));
+  GP_TRY(caller_or_own(g.inliers, H, r.own[4], r.stream, &r.a.inliers));
+  GP_TRY(r.state.alloc_async(sizeof(RansacState), r.stream));
+  GP_TRY(r.rows.alloc_async(sizeof(int) * 3 * chunk, r.stream));
+  GP_TRY(r.matched.alloc_async(sizeof(int) * 3 * chunk, r.stream));
+  GP_TRY(r.dists.alloc_async(sizeof(double) * 3 * chunk, r.stream));
+  GP_TRY(r.list.alloc_async(sizeof(int) * chunk, r.stream));
+  GP_TRY(r.taboo.alloc_async(sizeof(double) * 16 * (size_t)std::max(r.params->num_taboo, 1), r.stream));
+  std::memset(&r.init, 0, sizeof(r.init));
+  r.init.best_inliers = -1;
+  r.init.best_iteration = -1;
+  set_identity16(r.init.best_pose);
+  GP_HIP(hipMemcpyAsync(r.state.ptr, &r.init, sizeof(r.init), hipMemcpyHostToDevice, r.stream));
+  return GP_OK;
+}
+
+// stage 2: the inverses of the taboo poses, to the device
+static int ransac_taboo_inverses(RansacRun& r) {
+  const int num_taboo = r.params->num_taboo;
+  r.taboo_inv.assign(16 * (size_t)std::max(num_taboo, 1), 0.0);
+  for (int b = 0; b < num_taboo; b++) {  // Isometry3d::inverse(): R^T, -R^T t
+    const double* T = r.params->taboo_poses + 16 * b;
+    double* q = r.taboo_inv.data() + 16 * b;
+    for (int i = 0; i < 3; i++)
+      for (int c = 0; c < 3; c++) q[4 * c + i] = T[4 * i + c];
+    for (int i = 0; i < 3; i++) q[12 + i] = -((q[i] * T[12] + q[4 + i] * T[13]) + q[8 + i] * T[14]);
+    q[15] = 1.0;
+  }
+  if (num_taboo) GP_HIP(hipMemcpyAsync(r.taboo.ptr, r.taboo_inv.data(), sizeof(double) * 16 * num_taboo, hipMemcpyHostToDevice, r.stream));
+  return GP_OK;
+}
+
+// stage 3: per chunk six launches in stream order -- sample, rows, match, hypothesis, score, select
+static int ransac_chunks(RansacRun& r, const int* sample_indices) {
+  const gp_ransac_params* p = r.params;
+  const int samples = p->dof == 6 ? 3 : 2;
+  RansacState* state = r.state.as<RansacState>();
+  const double stop_above = (double)r.num_source * p->early_stop_inlier_rate;
+  for (int begin = 0; begin < r.H; begin += r.chunk) {
+    const int count = std::min(r.chunk, r.H - begin);
+    hipLaunchKernelGGL(ransac_sample_kernel, dim3(blocks_of(count)), dim3(256), 0, r.stream, state, r.a, begin, count, samples, r.num_source, p->seed, sample_indices,
+                       r.source_features, r.dim);
+    hipLaunchKernelGGL(ransac_rows_kernel, dim3(blocks_of(3 * (size_t)count)), dim3(256), 0, r.stream, state, r.a, begin, count, r.rows.as<int>());
+    GP_HIP(hipGetLastError());
+    GP_TRY(launch_feature_nn(r.target_features, r.num_target, r.source_features, r.num_source, r.dim, r.rows.as<int>(), 3 * count, &state->stop, r.matched.as<int>(),
+                             r.dists.as<double>(), r.stream));
+    hipLaunchKernelGGL(ransac_hypothesis_kernel, dim3(blocks_of(count)), dim3(256), 0, r.stream, state, r.a, begin, count, samples, r.target_points, r.source_points,
+                       r.matched.as<int>(), p->poly_error_thresh, r.taboo.as<double>(), p->num_taboo, p->taboo_thresh_rot, p->taboo_thresh_trans, r.list.as<int>());
+    GP_HIP(hipGetLastError());
+    GP_TRY(launch_overlap_batch(&r.grid, r.source_points, r.num_source, r.a.poses, r.list.as<int>(), &state->num_list, count, &state->stop, r.a.inliers, r.stream));
+    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, r.stream, state, r.a, begin, count, stop_above);
+    GP_HIP(hipGetLastError());
+  }
+  return GP_OK;
+}
+
+// stage 4: the one download, the call's one wait, the result
+static int ransac_result(RansacRun& r, gp_ransac_result* result) {
+  RansacState fin;
+  GP_HIP(hipMemcpyAsync(&fin, r.state.ptr, sizeof(fin), hipMemcpyDeviceToHost, r.stream));
+  GP_HIP(hipStreamSynchronize(r.stream));
+  std::memcpy(result->T_target_source, fin.best_pose, sizeof(fin.best_pose));
+  result->best_inliers = std::max(fin.best_inliers, 0);
+  result->best_iteration = fin.best_iteration;
+  result->num_scored = fin.num_scored;
+  result->early_stopped = fin.stop;
+  result->inlier_rate = (double)result->best_inliers / (double)r.num_target;
+  return GP_OK;
+}
+
 }  // namespace gp
 
 extern "C" {
-
-int gp_occupancy_grid_create(double resolution, gp_stream_t stream, gp_occupancy_grid_t** out) {
-  if (!out) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_create: out is NULL");
-  *out = nullptr;
-  if (!(resolution > 0.0) || !std::isfinite(resolution)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_create: the resolution must be positive and finite");
-  auto* g = new gp_occupancy_grid();
-  const int rc = gp::grid_init(g, resolution, (hipStream_t)stream);
-  if (rc != GP_OK) {
-    delete g;
-    return rc;
-  }
-  *out = g;
-  return GP_OK;
-}
-
-int gp_occupancy_grid_destroy(gp_occupancy_grid_t* grid) {
-  delete grid;  // (waits for the grid's stream)
-  return GP_OK;
-}
-
-int gp_occupancy_grid_insert(gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose) {
-  if (!grid || num_points < 0 || (num_points > 0 && !points_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_insert: bad arguments");
-  return gp::grid_insert(grid, points_dev, num_points, pose);
-}
-
-int gp_occupancy_grid_overlap(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose, int* num_overlap) {
-  if (!grid || !num_overlap || num_points < 0 || (num_points > 0 && !points_dev)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_overlap: bad arguments");
-  *num_overlap = 0;
-  if (num_points == 0) return GP_OK;
-  gp::DeviceArray count;
-  GP_TRY(count.alloc_async(16, grid->stream));
-  GP_HIP(hipMemsetAsync(count.ptr, 0, 16, grid->stream));
-  hipLaunchKernelGGL(gp::occupancy_overlaps_kernel, dim3(gp::blocks_for(num_points)), dim3(256), 0, grid->stream, grid->view(), points_dev, num_points, gp::pose_or_identity(pose),
-                     (unsigned char*)nullptr, count.as<int>());
-  GP_HIP(hipGetLastError());
-  GP_HIP(hipMemcpyAsync(num_overlap, count.ptr, sizeof(int), hipMemcpyDeviceToHost, grid->stream));
-  GP_HIP(hipStreamSynchronize(grid->stream));
-  return GP_OK;
-}
-
-int gp_occupancy_grid_get_overlaps(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* pose, unsigned char* overlaps_out_dev) {
-  if (!grid || num_points < 0 || (num_points > 0 && (!points_dev || !overlaps_out_dev))) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_get_overlaps: bad arguments");
-  if (num_points == 0) return GP_OK;
-  hipLaunchKernelGGL(gp::occupancy_overlaps_kernel, dim3(gp::blocks_for(num_points)), dim3(256), 0, grid->stream, grid->view(), points_dev, num_points, gp::pose_or_identity(pose),
-                     overlaps_out_dev, (int*)nullptr);
-  GP_HIP(hipGetLastError());
-  return GP_OK;
-}
-
-int gp_occupancy_grid_overlap_batch(const gp_occupancy_grid_t* grid, const float* points_dev, int num_points, const double* poses_dev, int num_poses, int* counts_out_dev) {
-  if (!grid || num_points < 0 || num_poses < 0 || (num_points > 0 && !points_dev) || (num_poses > 0 && (!poses_dev || !counts_out_dev)))
-    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_overlap_batch: bad arguments");
-  if (num_poses == 0) return GP_OK;
-  GP_HIP(hipMemsetAsync(counts_out_dev, 0, sizeof(int) * (size_t)num_poses, grid->stream));
-  if (num_points == 0) return GP_OK;
-  return gp::launch_overlap_batch(grid, points_dev, num_points, poses_dev, nullptr, nullptr, num_poses, nullptr, counts_out_dev, grid->stream);
-}
-
-int gp_occupancy_grid_num_occupied_cells(const gp_occupancy_grid_t* grid) { return grid ? grid->num_cells : 0; }
-
-int gp_occupancy_grid_info(const gp_occupancy_grid_t* grid, int* num_slots, int* num_blocks) {
-  if (!grid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_occupancy_grid_info: grid is NULL");
-  if (num_slots) *num_slots = (int)grid->slots;
-  if (num_blocks) *num_blocks = grid->num_blocks;
-  return GP_OK;
-}
-
-int gp_feature_nn_search(const float* target_features_dev, int num_target, const float* query_features_dev, int num_query_rows, int dim, const int* rows_dev, int num_queries,
-                         int* indices_out_dev, double* sq_dists_out_dev, gp_stream_t stream) {
-  if (dim < 1 || dim > GP_FEATURE_MAX_DIM) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_feature_nn_search: dim must be 1 .. 128");
-  if (num_target < 1 || !target_features_dev) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_feature_nn_search: no target features");
-  if (num_queries < 0 || num_query_rows < 0 || (num_queries > 0 && (!query_features_dev || !indices_out_dev || !sq_dists_out_dev)))
-    return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_feature_nn_search: bad arguments");
-  if (!rows_dev && num_queries > num_query_rows) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_feature_nn_search: more queries than query rows");
-  if (num_queries == 0) return GP_OK;
-  return gp::launch_feature_nn(target_features_dev, num_target, query_features_dev, num_query_rows, dim, rows_dev, num_queries, nullptr, indices_out_dev, sq_dists_out_dev,
-                               (hipStream_t)stream);
-}
 
 void gp_ransac_params_default(gp_ransac_params* p) {
   if (!p) return;
@@ -581,90 +348,22 @@ unsigned gp_ransac_sample_index(uint64_t seed, unsigned iteration, unsigned draw
 
 int gp_ransac_estimate_pose(const float* target_points_dev, int num_target, const float* source_points_dev, int num_source, const float* target_features_dev,
                             const float* source_features_dev, int dim, const gp_ransac_params* params, const int* sample_indices_dev, const gp_ransac_hypotheses* hypotheses,
-                            gp_ransac_result* result, gp_stream_t stream_) {
+                            gp_ransac_result* result, gp_stream_t stream) {
   using namespace gp;
-  if (!params || !result) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: params or result is NULL");
-  if (params->dof != 6 && params->dof != 4) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: dof must be 6 or 4");
-  const int samples = params->dof == 6 ? 3 : 2;
-  if (num_source < samples) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: fewer source points than samples");
-  if (num_target < 1) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: the target is empty");
-  if (dim < 1 || dim > GP_FEATURE_MAX_DIM) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: dim must be 1 .. 128");
-  if (params->num_taboo < 0 || params->num_taboo > GP_RANSAC_MAX_TABOO || (params->num_taboo > 0 && !params->taboo_poses))
-    return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: at most 64 taboo poses");
-  if (params->max_iterations < 1 || params->chunk_iterations < 1) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: max_iterations and chunk_iterations must be positive");
-  if (!(params->inlier_voxel_resolution > 0.0) || !std::isfinite(params->inlier_voxel_resolution))
-    return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: the resolution must be positive and finite");
-  if (!target_points_dev || !source_points_dev || !target_features_dev || !source_features_dev) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_ransac_estimate_pose: NULL array");
-  hipStream_t stream = (hipStream_t)stream_;
-  const int H = params->max_iterations, chunk = std::min(params->chunk_iterations, H);
-
+  GP_TRY(check_ransac(target_points_dev, num_target, source_points_dev, num_source, target_features_dev, source_features_dev, dim, params, result));
+  RansacRun r;
+  r.target_points = target_points_dev, r.source_points = source_points_dev, r.target_features = target_features_dev, r.source_features = source_features_dev;
+  r.num_target = num_target, r.num_source = num_source, r.dim = dim;
+  r.params = params;
+  r.stream = (hipStream_t)stream;
+  r.H = params->max_iterations, r.chunk = std::min(params->chunk_iterations, r.H);
   // the target's occupancy set (:35-36), sized for the target at once and only queued: the download of the result is the call's one wait
-  gp_occupancy_grid grid;
-  GP_TRY(grid_init(&grid, params->inlier_voxel_resolution, stream, num_target));
-  GP_TRY(grid_insert(&grid, target_points_dev, num_target, nullptr, false));
-
-  DeviceArray own[5], state_d, rows_d, matched_d, dists_d, list_d, taboo_d;
-  RansacArrays a;
-  const size_t sizes[5] = {sizeof(int) * (size_t)H, sizeof(int) * 3 * (size_t)H, sizeof(int) * 3 * (size_t)H, sizeof(double) * 16 * (size_t)H, sizeof(int) * (size_t)H};
-  void* given[5] = {hypotheses ? hypotheses->status : nullptr, hypotheses ? hypotheses->source_indices : nullptr, hypotheses ? hypotheses->target_indices : nullptr,
-                    hypotheses ? hypotheses->poses : nullptr, hypotheses ? hypotheses->inliers : nullptr};
-  for (int i = 0; i < 5; i++)
-    if (!given[i]) {
-      GP_TRY(own[i].alloc_async(sizes[i], stream));
-      given[i] = own[i].ptr;
-    }
-  a.status = (int*)given[0], a.source_indices = (int*)given[1], a.target_indices = (int*)given[2], a.poses = (double*)given[3], a.inliers = (int*)given[4];
-  GP_TRY(state_d.alloc_async(sizeof(RansacState), stream));
-  GP_TRY(rows_d.alloc_async(sizeof(int) * 3 * (size_t)chunk, stream));
-  GP_TRY(matched_d.alloc_async(sizeof(int) * 3 * (size_t)chunk, stream));
-  GP_TRY(dists_d.alloc_async(sizeof(double) * 3 * (size_t)chunk, stream));
-  GP_TRY(list_d.alloc_async(sizeof(int) * (size_t)chunk, stream));
-  GP_TRY(taboo_d.alloc_async(sizeof(double) * 16 * (size_t)std::max(params->num_taboo, 1), stream));
-  RansacState init;
-  std::memset(&init, 0, sizeof(init));
-  init.best_inliers = -1;
-  init.best_iteration = -1;
-  for (int j = 0; j < 16; j += 5) init.best_pose[j] = 1.0;
-  GP_HIP(hipMemcpyAsync(state_d.ptr, &init, sizeof(init), hipMemcpyHostToDevice, stream));
-  std::vector<double> taboo_inv(16 * (size_t)std::max(params->num_taboo, 1), 0.0);
-  for (int b = 0; b < params->num_taboo; b++) {  // Isometry3d::inverse(): R^T, -R^T t
-    const double* T = params->taboo_poses + 16 * b;
-    double* q = taboo_inv.data() + 16 * b;
-    for (int r = 0; r < 3; r++)
-      for (int c = 0; c < 3; c++) q[4 * c + r] = T[4 * r + c];
-    for (int r = 0; r < 3; r++) q[12 + r] = -((q[r] * T[12] + q[4 + r] * T[13]) + q[8 + r] * T[14]);
-    q[15] = 1.0;
-  }
-  if (params->num_taboo) GP_HIP(hipMemcpyAsync(taboo_d.ptr, taboo_inv.data(), sizeof(double) * 16 * params->num_taboo, hipMemcpyHostToDevice, stream));
-
-  RansacState* state = state_d.as<RansacState>();
-  const double stop_above = (double)num_source * params->early_stop_inlier_rate;
-  for (int begin = 0; begin < H; begin += chunk) {
-    const int count = std::min(chunk, H - begin);
-    hipLaunchKernelGGL(ransac_sample_kernel, dim3(blocks_for(count)), dim3(256), 0, stream, state, a, begin, count, samples, num_source, params->seed, sample_indices_dev,
-                       source_features_dev, dim);
-    hipLaunchKernelGGL(ransac_rows_kernel, dim3(blocks_for(3 * (size_t)count)), dim3(256), 0, stream, state, a, begin, count, rows_d.as<int>());
-    GP_HIP(hipGetLastError());
-    GP_TRY(launch_feature_nn(target_features_dev, num_target, source_features_dev, num_source, dim, rows_d.as<int>(), 3 * count, &state->stop, matched_d.as<int>(),
-                             dists_d.as<double>(), stream));
-    hipLaunchKernelGGL(ransac_hypothesis_kernel, dim3(blocks_for(count)), dim3(256), 0, stream, state, a, begin, count, samples, target_points_dev, source_points_dev,
-                       matched_d.as<int>(), params->poly_error_thresh, taboo_d.as<double>(), params->num_taboo, params->taboo_thresh_rot, params->taboo_thresh_trans,
-                       list_d.as<int>());
-    GP_HIP(hipGetLastError());
-    GP_TRY(launch_overlap_batch(&grid, source_points_dev, num_source, a.poses, list_d.as<int>(), &state->num_list, count, &state->stop, a.inliers, stream));
-    hipLaunchKernelGGL(ransac_select_kernel, dim3(1), dim3(256), 0, stream, state, a, begin, count, stop_above);
-    GP_HIP(hipGetLastError());
-  }
-  RansacState fin;
-  GP_HIP(hipMemcpyAsync(&fin, state_d.ptr, sizeof(fin), hipMemcpyDeviceToHost, stream));
-  GP_HIP(hipStreamSynchronize(stream));
-  std::memcpy(result->T_target_source, fin.best_pose, sizeof(fin.best_pose));
-  result->best_inliers = std::max(fin.best_inliers, 0);
-  result->best_iteration = fin.best_iteration;
-  result->num_scored = fin.num_scored;
-  result->early_stopped = fin.stop;
-  result->inlier_rate = (double)result->best_inliers / (double)num_target;
-  return GP_OK;
+  GP_TRY(grid_init(&r.grid, params->inlier_voxel_resolution, r.stream, num_target));
+  GP_TRY(grid_insert(&r.grid, target_points_dev, num_target, nullptr, false));
+  GP_TRY(ransac_arrays(r, hypotheses));
+  GP_TRY(ransac_taboo_inverses(r));
+  GP_TRY(ransac_chunks(r, sample_indices_dev));
+  return ransac_result(r, result);
 }
 
 int gp_align_points(const double* target_points_dev, const double* source_points_dev, const double* weights_dev, int num_points, int dof, double* pose_out, gp_stream_t stream_) {

@@ -7,8 +7,6 @@
 
 namespace gp {
 
-inline unsigned blocks_of(size_t elements) { return (unsigned)((elements + 255) / 256); }
-
 // the flag is a function of the position that the scan and the scatter both evaluate: a stored array (ScanArrayInput, gp_scan.hpp), or computed from other arrays
 template <typename Flag>
 __global__ void __launch_bounds__(256) select_scatter_kernel(const Flag flag, const int* __restrict__ scan, int n, int* __restrict__ indices_out) {

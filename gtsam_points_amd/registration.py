@@ -1,4 +1,4 @@
-"""Global registration on the device, over the C-ABI (csrc/gp_registration.hip, csrc/gp_gnc.hip):
+"""Global registration on the device, over the C-ABI (csrc/gp_occupancy.hip, csrc/gp_feature_match.hip, csrc/gp_registration.hip, csrc/gp_gnc.hip):
 
   OccupancyGridGPU           <- ann/fast_occupancy_grid.hpp:51-113 FastOccupancyGrid
   match_features_gpu         <- the 1-NN feature search estimate_pose_ransac runs on its target_features_tree (registration/impl/ransac_impl.hpp:62)

@@ -1042,7 +1042,7 @@ int gp_debug_drop_error_words(gp_vgicp_batch_t* batch, int count);
  * synchronous call); NULL disables */
 int gp_vgicp_batch_set_trace_buffer(gp_vgicp_batch_t* batch, void* dev_buffer);
 
-/* ---- global registration: FastOccupancyGrid, feature matching, RANSAC, closed-form alignment (csrc/gp_registration.hip, csrc/gp_occupancy.hpp) ----
+/* ---- global registration: FastOccupancyGrid, feature matching, RANSAC, closed-form alignment (csrc/gp_occupancy.hip, csrc/gp_feature_match.hip, csrc/gp_registration.hip) ----
  * Device counterparts of ann/fast_occupancy_grid.hpp, registration/ransac.hpp + impl/ransac_impl.hpp and registration/alignment.hpp; CPU-only upstream.  f64
  * arithmetic on the f32 device points throughout.
  *

@@ -2,6 +2,7 @@
 of gp_gnc_params; and the argument refusals that are made on the host before any device work."""
 import ctypes as C
 import os
+import re
 
 from test_icp_build_cpu import ROOT, _assert_no_scratch
 
@@ -16,6 +17,13 @@ def test_every_kernel_of_the_unit_uses_no_scratch():
         assert sum(name in k for k in ks) == 1, name
     assert sum("scan_onepass_kernel" in k for k in ks) == 2 and sum("select_scatter_kernel" in k for k in ks) == 2  # the one compaction, for its two flags
     _assert_no_scratch(ks)
+    # the two one-workgroup kernels that reduce through gp_alignment.hpp: SGPRs, VGPRs, LDS (bytes per workgroup) of the build before they did, as upper bounds
+    for frag, (sgprs, vgprs, lds) in {"gnc_loop_kernel": (82, 126, 18560), "gnc_diameter_kernel": (20, 25, 12288)}.items():
+        (name,) = [k for k in ks if frag in k]
+        get = lambda key: int(re.search(re.escape(key) + r":\s+(\d+)", ks[name]).group(1))  # noqa: E731
+        got = dict(sgprs=get("TotalSGPRs"), vgprs=get("    VGPRs"), lds=get("LDS Size [bytes/block]"))
+        print(name, got)
+        assert got["sgprs"] <= sgprs and got["vgprs"] <= vgprs and got["lds"] <= lds, (name, got)
 
 
 def test_defaults_are_the_reference_values():

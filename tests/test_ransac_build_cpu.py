@@ -1,31 +1,60 @@
-"""CPU checks of the registration unit's build products: RANSAC's scoring kernel and the feature-search kernel as the compiler's resource remarks list them, neither
-with scratch or spills; and the argument refusals that are made on the host before any device work."""
+"""CPU checks of the three registration units' build products (csrc/gp_registration.hip: RANSAC and the N-point alignment; csrc/gp_occupancy.hip: the occupancy set;
+csrc/gp_feature_match.hip: the exact feature search): each unit emits exactly its kernels, as the compiler's resource remarks list them, none with scratch or spills,
+and each kernel stays within the registers and LDS of the build before the one unit was split into three; and the argument refusals that are made on the host before
+any device work.
+
+The bounds are the figures of the unsplit gp_registration.hip (HIP 7.2 / AMD clang 22, gfx950): upper bounds on SGPRs, VGPRs and LDS (bytes per workgroup).  The build
+this test came with sits ON every figure: its kernels are the unsplit unit's instruction for instruction (align_points_kernel up to the names of two registers)."""
 import ctypes as C
 import os
+import re
 
 from test_icp_build_cpu import ROOT, _assert_no_scratch
 
-RES = os.path.join(ROOT, "gtsam_points_amd", "csrc", "gp_registration.resources.txt")
+# unit -> kernel -> SGPRs, VGPRs, LDS
+UNITS = {
+    "gp_registration": {"align_points_kernel": (36, 68, 18432), "ransac_sample_kernel": (50, 16, 0), "ransac_rows_kernel": (16, 6, 0),
+                        "ransac_hypothesis_kernel": (44, 112, 0), "ransac_select_kernel": (24, 14, 4096)},
+    "gp_occupancy": {"occupancy_insert_kernel": (36, 22, 0), "occupancy_rehash_kernel": (26, 20, 0), "occupancy_overlaps_kernel": (42, 22, 0),
+                     "occupancy_overlap_batch_kernel": (58, 22, 0)},
+    "gp_feature_match": {"feature_nn_kernel": (55, 76, 41216)},
+}
+HELPERS = ("host_flag_kernel",)  # what gp_host.hpp instantiates in every unit
 
 
-def _kernels():
-    assert os.path.exists(RES), "build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')"
-    return {b.split()[0]: b for b in open(RES).read().split("remark: Function Name: ")[1:]}
+def _kernels(unit):
+    res = os.path.join(ROOT, "gtsam_points_amd", "csrc", unit + ".resources.txt")
+    assert os.path.exists(res), "build the HIP library first (python -c 'import __graft_entry__ as g; g.build()')"
+    return {b.split()[0]: b for b in open(res).read().split("remark: Function Name: ")[1:]}
 
 
 def test_scoring_and_feature_search_kernels_use_no_scratch():
-    ks = _kernels()
-    hot = {k: v for k, v in ks.items() if "occupancy_overlap_batch_kernel" in k or "feature_nn_kernel" in k}
-    assert len(hot) == 2, sorted(ks)
-    _assert_no_scratch(hot)
+    ks = {**_kernels("gp_occupancy"), **_kernels("gp_feature_match")}
+    for name in ("occupancy_overlap_batch_kernel", "feature_nn_kernel"):
+        assert sum(name in k for k in ks) == 1, (name, sorted(ks))
+    assert not any("occupancy_overlap_batch_kernel" in k or "feature_nn_kernel" in k for k in _kernels("gp_registration"))
+    _assert_no_scratch({k: v for k, v in ks.items() if "occupancy_overlap_batch_kernel" in k or "feature_nn_kernel" in k})
 
 
 def test_every_kernel_of_the_unit_uses_no_scratch():
-    ks = _kernels()
-    for name in ("occupancy_insert_kernel", "occupancy_rehash_kernel", "occupancy_overlaps_kernel", "align_points_kernel", "ransac_sample_kernel", "ransac_rows_kernel",
-                 "ransac_hypothesis_kernel", "ransac_select_kernel"):
-        assert sum(name in k for k in ks) == 1, name
-    _assert_no_scratch(ks)
+    for unit, want in UNITS.items():
+        ks = _kernels(unit)
+        own = [k for k in ks if not any(h in k for h in HELPERS)]
+        for name in want:
+            assert sum(name in k for k in own) == 1, (unit, name)
+        assert len(own) == len(want), (unit, sorted(own))  # nothing else: each kernel is compiled in one unit only
+        _assert_no_scratch(ks)
+
+
+def test_every_kernel_keeps_within_the_figures_of_the_unsplit_unit():
+    for unit, want in UNITS.items():
+        ks = _kernels(unit)
+        for frag, (sgprs, vgprs, lds) in want.items():
+            (name,) = [k for k in ks if frag in k]
+            get = lambda key: int(re.search(re.escape(key) + r":\s+(\d+)", ks[name]).group(1))  # noqa: E731
+            got = dict(sgprs=get("TotalSGPRs"), vgprs=get("    VGPRs"), lds=get("LDS Size [bytes/block]"))
+            print(name, got)
+            assert got["sgprs"] <= sgprs and got["vgprs"] <= vgprs and got["lds"] <= lds, (name, got)
 
 
 def test_entry_points_refuse_bad_arguments_without_a_device():
