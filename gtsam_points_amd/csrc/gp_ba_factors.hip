@@ -298,29 +298,18 @@ struct gp_ba_factors {
   }
 };
 
-namespace gp {
-
-template <typename T>
-static int ba_upload(DeviceArray& d, const std::vector<T>& h) {
-  GP_TRY(d.alloc(sizeof(T) * h.size()));
-  if (!h.empty()) GP_HIP(hipMemcpy(d.ptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
-  return GP_OK;
-}
-
-}  // namespace gp
-
 int gp_ba_factors::ensure_device() {
   if (on_device) return GP_OK;
-  GP_TRY(gp::ba_upload(d_points, h_points));
-  GP_TRY(gp::ba_upload(d_point_seg, h_point_seg));
-  GP_TRY(gp::ba_upload(d_seg_pose, seg_pose));
-  GP_TRY(gp::ba_upload(d_seg_points, h_seg_points));
-  GP_TRY(gp::ba_upload(d_feat_points, h_feat_points));
-  GP_TRY(gp::ba_upload(d_kinds, h_kinds));
-  GP_TRY(gp::ba_upload(d_scales, h_scales));
-  GP_TRY(gp::ba_upload(d_rec_begin, h_rec_begin));
-  GP_TRY(gp::ba_upload(d_rec_pair, h_rec_pair));
-  GP_TRY(gp::ba_upload(d_contribs, h_contribs));
+  GP_TRY(gp::upload(d_points, h_points));
+  GP_TRY(gp::upload(d_point_seg, h_point_seg));
+  GP_TRY(gp::upload(d_seg_pose, seg_pose));
+  GP_TRY(gp::upload(d_seg_points, h_seg_points));
+  GP_TRY(gp::upload(d_feat_points, h_feat_points));
+  GP_TRY(gp::upload(d_kinds, h_kinds));
+  GP_TRY(gp::upload(d_scales, h_scales));
+  GP_TRY(gp::upload(d_rec_begin, h_rec_begin));
+  GP_TRY(gp::upload(d_rec_pair, h_rec_pair));
+  GP_TRY(gp::upload(d_contribs, h_contribs));
   GP_TRY(d_seg_table.alloc(sizeof(double) * gp::kBaRow * (size_t)S));
   GP_TRY(d_feat_table.alloc(sizeof(double) * gp::kBaFeat * (size_t)F));
   for (auto* v : {&h_point_seg, &h_seg_points, &h_feat_points, &h_kinds, &h_rec_begin, &h_rec_pair}) std::vector<int>().swap(*v);

@@ -68,6 +68,10 @@ __global__ void __launch_bounds__(256) intensity_gradient_kernel(const float* __
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 
+int gp_colored_gicp_factor::run_pass(const double* pose_lin, const double* pose_eval, void* out_host) {
+  return gp_corr_factor_core::run_pass(term, pose_lin, pose_eval, out_host);
+}
+
 extern "C" {
 
 // ---- intensity gradients ----------------------------------------------------------------------------------------------
@@ -131,12 +135,7 @@ int gp_colored_gicp_factor_create(const gp_point_grid_t* grid, const float* targ
   return GP_OK;
 }
 
-int gp_colored_gicp_factor_destroy(gp_colored_gicp_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (the grid is the caller's)
-  return GP_OK;
-}
+int gp_colored_gicp_factor_destroy(gp_colored_gicp_factor_t* f) { return gp_corr_destroy(f); }  // (the grid is the caller's)
 
 int gp_colored_gicp_factor_set_photometric_term_weight(gp_colored_gicp_factor_t* f, double weight) {
   if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_set_photometric_term_weight: null");
@@ -153,33 +152,19 @@ int gp_colored_gicp_factor_set_max_correspondence_distance(gp_colored_gicp_facto
 }
 
 int gp_colored_gicp_factor_set_correspondence_update_tolerance(gp_colored_gicp_factor_t* f, double angle, double trans) {
-  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_set_correspondence_update_tolerance: null");
-  f->tol_rot = angle;
-  f->tol_trans = trans;
-  return GP_OK;
+  return gp_corr_set_update_tolerance(f ? &f->upd : nullptr, angle, trans, "gp_colored_gicp_factor_set_correspondence_update_tolerance");
 }
 
-int gp_colored_gicp_factor_num_correspondences(const gp_colored_gicp_factor_t* f) { return f ? f->num_correspondences : 0; }
+int gp_colored_gicp_factor_num_correspondences(const gp_colored_gicp_factor_t* f) { return f ? f->num_inliers : 0; }
 
 int gp_colored_gicp_factor_linearize(gp_colored_gicp_factor_t* f, const double pose[16], gp_linearized6* out_host) {
   if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_linearize: null");
-  if (f->num_tiles > 0 && !keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, pose)) GP_TRY(f->search(pose));
-  memcpy(f->lin_pose, pose, sizeof(double) * 16);
-  f->lin_valid = true;
-  GP_TRY(f->run_pass(f->term, pose, nullptr, out_host));
-  f->num_correspondences = (int)out_host->num_inliers;
-  return GP_OK;
+  return corr_factor_linearize(f, pose, out_host);
 }
 
 int gp_colored_gicp_factor_compute_error(gp_colored_gicp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
   if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_compute_error: null");
-  // the stored correspondences serve when pose_lin is the pose of the last linearise (which may itself have kept older ones) or the pose they were searched at
-  const bool stored = f->corr_valid && ((f->lin_valid && memcmp(f->lin_pose, pose_lin, sizeof(double) * 16) == 0) || f->searched_at(pose_lin));
-  if (f->num_tiles > 0 && !stored) {
-    GP_TRY(f->search(pose_lin));
-    f->lin_valid = false;
-  }
-  return f->run_pass(f->term, pose_lin, pose_eval, out_host);
+  return corr_factor_compute_error(f, pose_lin, pose_eval, out_host);
 }
 
 }  // extern "C"

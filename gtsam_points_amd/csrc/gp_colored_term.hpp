@@ -147,8 +147,5 @@ struct ColoredGicpTerm {
 
 struct gp_colored_gicp_factor : gp_corr_factor_core {  // (the grid is BORROWED, as the ICP factor's)
   gp::ColoredGicpTerm term{};
-  double lin_pose[16] = {0};  // the pose of the last linearise (which may have kept older correspondences: the update tolerances)
-  bool lin_valid = false;
-  double tol_rot = 0.0, tol_trans = 0.0;  // correspondence_update_tolerance_rot / _trans (:103-110)
-  int num_correspondences = 0;
+  int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_colored_factors.hip)
 };

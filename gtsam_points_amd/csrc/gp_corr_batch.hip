@@ -68,31 +68,6 @@ __device__ __forceinline__ TERM batch_term(const ColoredBatchDesc& d) {
   return d.term;
 }
 
-// corr_tile_kernel (gp_corr_factors.hip) with the tile, the factor and the poses looked up: workgroup b takes tile tiles[b], lane t of 256 its points t, t + 256, ...
-// DESC: CorrBatchDesc (GICP, ICP) or ColoredBatchDesc (colored GICP)
-template <int MODE, class TERM, class DESC>
-__global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const DESC* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
-                                                               const double* __restrict__ poses_eval, const int set, double* __restrict__ partials) {
-  constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
-  constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
-  const CorrTile t = tiles[blockIdx.x];
-  const DESC& d = descs[t.factor];  // (read in place: a private copy of the larger table's entry would go to scratch for the set-indexed corr[])
-  const TERM f = batch_term<TERM>(d);
-  const Pose Tl = load_pose(poses_lin + 16 * (size_t)t.factor);
-  const Pose Te = MODE == MODE_ERR ? load_pose(poses_eval + 16 * (size_t)t.factor) : Tl;
-  double acc[NREG];
-#pragma unroll
-  for (int k = 0; k < NREG; k++) acc[k] = 0.0;
-  const int* __restrict__ corr = d.corr[set];
-  const int end = t.begin + t.count;
-  for (int i = t.begin + threadIdx.x; i < end; i += 256) {
-    const int c = corr[i];
-    if (c < 0) continue;
-    f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
-  }
-  store_tile_sums_row<MODE>(acc, partials + (size_t)t.row * STRIDE);
-}
-
 // what the LOAM tile kernels and the validation read of part t.factor (a table of its own beside CorrBatchDesc, which the GICP / ICP kernels keep as it is)
 struct LoamBatchDesc {
   const float* points;         // [n][3] source
@@ -104,15 +79,24 @@ struct LoamBatchDesc {
   int pad_;
 };
 
-// corr_batch_tiles_kernel for the LOAM terms: the same tile, lanes and reduction; a term is handed corr + i and the stride n (gp_corr_factors.hpp)
-template <int MODE, class TERM>
-__global__ void __launch_bounds__(256) loam_batch_tiles_kernel(const LoamBatchDesc* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
+template <class TERM>
+__device__ __forceinline__ TERM batch_term(const LoamBatchDesc& d) {
+  static_assert(TERM::kNeighbours > 1, "LoamBatchDesc serves the LOAM terms only");
+  return TERM{LoamDesc{d.points, d.target_points}};
+}
+
+// corr_tile_kernel (gp_corr_tile.hpp) with the tile, the factor and the poses looked up: workgroup b takes tile tiles[b], lane t of 256 its points t, t + 256, ...
+// DESC: CorrBatchDesc (GICP, ICP), ColoredBatchDesc (colored GICP) or LoamBatchDesc (LOAM edge, plane: a term is handed corr + i and the stride n, gp_corr_factors.hpp)
+template <int MODE, class TERM, class DESC>
+__global__ void __launch_bounds__(256) corr_batch_tiles_kernel(const DESC* __restrict__ descs, const CorrTile* __restrict__ tiles, const double* __restrict__ poses_lin,
                                                                const double* __restrict__ poses_eval, const int set, double* __restrict__ partials) {
   constexpr int NREG = MODE == MODE_LIN_GENERAL ? ACCG_SIZE : (MODE == MODE_ERR ? TERM::kErrRegs : 32);
   constexpr int STRIDE = MODE == MODE_LIN_GENERAL ? ACCG_STRIDE : ACC_STRIDE;
   const CorrTile t = tiles[blockIdx.x];
-  const LoamBatchDesc d = descs[t.factor];
-  const TERM f{LoamDesc{d.points, d.target_points}};
+  // the two larger tables' entries are read in place (a private copy would go to scratch for the set-indexed corr[]); the LOAM table's 48 bytes are copied, as the
+  // kernel they had to themselves copied them
+  const std::conditional_t<TERM::kNeighbours == 1, const DESC&, const DESC> d = descs[t.factor];
+  const TERM f = batch_term<TERM>(d);
   const Pose Tl = load_pose(poses_lin + 16 * (size_t)t.factor);
   const Pose Te = MODE == MODE_ERR ? load_pose(poses_eval + 16 * (size_t)t.factor) : Tl;
   double acc[NREG];
@@ -121,8 +105,12 @@ __global__ void __launch_bounds__(256) loam_batch_tiles_kernel(const LoamBatchDe
   const int* __restrict__ corr = d.corr[set];
   const int end = t.begin + t.count;
   for (int i = t.begin + threadIdx.x; i < end; i += 256) {
-    if (corr[i] < 0) continue;
-    f.template accumulate<MODE>(i, corr + i, (size_t)d.n, Tl, Te, acc);
+    const int c = corr[i];
+    if (c < 0) continue;
+    if constexpr (TERM::kNeighbours == 1)
+      f.template accumulate<MODE>(i, (size_t)c, Tl, Te, acc);
+    else  // (int[K][n], slot 0 the anchor)
+      f.template accumulate<MODE>(i, corr + i, (size_t)d.n, Tl, Te, acc);
   }
   store_tile_sums_row<MODE>(acc, partials + (size_t)t.row * STRIDE);
 }
@@ -182,31 +170,30 @@ struct gp_corr_batch {
   gp::DeviceArray d_partials_lin, d_partials_err;             // [num_tiles][ACCG_STRIDE] | [num_tiles][ACC_STRIDE]
   bool set_valid[2] = {false, false};
   // the synchronous host-pose forms and the LM graph's error evaluation: pose staging, results and completion words in host-mapped pinned memory
-  gp::PinnedArray h_poses, h_out, h_done;
-  void *h_out_dev = nullptr, *h_done_dev = nullptr;
+  gp::PinnedArray h_poses;
+  gp::MappedResults res;  // F records (or errors) and F completion words
   gp::DeviceArray d_poses[2];
-  unsigned long long seq = 0;
 
   long spin_us() const { return 200 + total_points / 500; }  // (the search is ~1 ns per point; the wait falls back to the stream behind it)
+
+  // the tile launch of one kind, over that kind's stretch of the tile list (TERM: its per-point term, descs: the table the term is made from)
+  template <int MODE, class TERM, class DESC>
+  void launch_kind(Kind kind, const DESC* descs, const double* lin, const double* eval, int set, double* partials) {
+    if (kind_count[kind] > 0)
+      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, TERM, DESC>), dim3(kind_count[kind]), dim3(256), 0, stream, descs, d_tiles.as<gp::CorrTile>() + kind_begin[kind], lin, eval, set,
+                         partials);
+  }
 
   template <int MODE>
   int launch_tiles(const double* lin, const double* eval, int set, double* partials) {
     const gp::CorrBatchDesc* descs = d_descs.as<gp::CorrBatchDesc>();
-    const gp::CorrTile* tiles = d_tiles.as<gp::CorrTile>();
-    if (kind_count[GICP] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::GicpTerm, gp::CorrBatchDesc>), dim3(kind_count[GICP]), dim3(256), 0, stream, descs, tiles + kind_begin[GICP], lin, eval, set, partials);
-    if (kind_count[ICP_POINT] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<false>, gp::CorrBatchDesc>), dim3(kind_count[ICP_POINT]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_POINT], lin, eval, set, partials);
-    if (kind_count[ICP_PLANE] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::IcpTerm<true>, gp::CorrBatchDesc>), dim3(kind_count[ICP_PLANE]), dim3(256), 0, stream, descs, tiles + kind_begin[ICP_PLANE], lin, eval, set, partials);
-    if (kind_count[COLORED] > 0)
-      hipLaunchKernelGGL((gp::corr_batch_tiles_kernel<MODE, gp::ColoredGicpTerm, gp::ColoredBatchDesc>), dim3(kind_count[COLORED]), dim3(256), 0, stream,
-                         d_colored_descs.as<gp::ColoredBatchDesc>(), tiles + kind_begin[COLORED], lin, eval, set, partials);
     const gp::LoamBatchDesc* ldescs = d_loam_descs.as<gp::LoamBatchDesc>();
-    if (kind_count[LOAM_EDGE] > 0)
-      hipLaunchKernelGGL((gp::loam_batch_tiles_kernel<MODE, gp::LoamEdgeTerm>), dim3(kind_count[LOAM_EDGE]), dim3(256), 0, stream, ldescs, tiles + kind_begin[LOAM_EDGE], lin, eval, set, partials);
-    if (kind_count[LOAM_PLANE] > 0)
-      hipLaunchKernelGGL((gp::loam_batch_tiles_kernel<MODE, gp::LoamPlaneTerm>), dim3(kind_count[LOAM_PLANE]), dim3(256), 0, stream, ldescs, tiles + kind_begin[LOAM_PLANE], lin, eval, set, partials);
+    launch_kind<MODE, gp::GicpTerm>(GICP, descs, lin, eval, set, partials);
+    launch_kind<MODE, gp::IcpTerm<false>>(ICP_POINT, descs, lin, eval, set, partials);
+    launch_kind<MODE, gp::IcpTerm<true>>(ICP_PLANE, descs, lin, eval, set, partials);
+    launch_kind<MODE, gp::ColoredGicpTerm>(COLORED, d_colored_descs.as<gp::ColoredBatchDesc>(), lin, eval, set, partials);
+    launch_kind<MODE, gp::LoamEdgeTerm>(LOAM_EDGE, ldescs, lin, eval, set, partials);
+    launch_kind<MODE, gp::LoamPlaneTerm>(LOAM_PLANE, ldescs, lin, eval, set, partials);
     GP_HIP(hipGetLastError());
     return GP_OK;
   }
@@ -258,6 +245,14 @@ struct gp_corr_batch {
     return combine_parts(d_part_errors.as<double>(), 1, out, done);
   }
 
+  // where the host-pose forms stage their poses and every synchronous form finds its results
+  int alloc_staging() {
+    const size_t pb = sizeof(double) * 16 * (size_t)F;
+    for (int k = 0; k < 2; k++) GP_TRY(d_poses[k].alloc(pb));
+    GP_TRY(h_poses.ensure(2 * pb));
+    return res.ensure(sizeof(gp_linearized6) * (size_t)F, (size_t)F);
+  }
+
   // host poses [F][16] -> d_poses[k] (through the pinned staging block; in stream order in front of the kernels that read them)
   int stage_poses(const double* poses_host, int k) {
     const size_t bytes = sizeof(double) * 16 * (size_t)F;
@@ -273,17 +268,143 @@ namespace gp {
 int corr_batch_error_begin(gp_corr_batch* b, int set, const double* poses_lin_dev, const double* poses_eval_dev) {
   if (!b || !poses_lin_dev || !poses_eval_dev || (set != 0 && set != 1)) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch: error evaluation: null / set must be 0 or 1");
   if (!b->set_valid[set]) return fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch: error evaluation on a correspondence set that was never linearised");
-  const DoneFlags done{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq};
-  return b->issue_error(set, poses_lin_dev, poses_eval_dev, static_cast<double*>(b->h_out_dev), done);
+  return b->issue_error(set, poses_lin_dev, poses_eval_dev, static_cast<double*>(b->res.out_dev), b->res.next());
 }
 
 int corr_batch_error_end(gp_corr_batch* b, double* out_host, long extra_spin_us) {
-  GP_TRY(wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), (size_t)b->F, b->seq, b->stream, b->spin_us() + extra_spin_us));
-  memcpy(out_host, b->h_out.ptr, sizeof(double) * (size_t)b->F);
+  GP_TRY(wait_done(b->res.words(), (size_t)b->F, b->res.seq, b->stream, b->spin_us() + extra_spin_us));
+  memcpy(out_host, b->res.out.ptr, sizeof(double) * (size_t)b->F);
   return GP_OK;
 }
 
 }  // namespace gp
+
+// The host tables of a batch under construction, in the stages gp_corr_batch_create_ex2 runs them: the parts list, the rows and the kind-ordered tile list, the
+// per-part tables, the uploads.
+struct BatchTables {
+  // the parts in record order: a GICP / ICP / colored GICP member is one, a LOAM member its edge part and / or its plane part, in that order
+  struct Part {
+    const gp_corr_factor_core* core;
+    int kind, member, k;
+    const gp_loam_factor* loam;
+  };
+  std::vector<Part> parts;
+  std::vector<int2> member_parts;  // [F] first part, number of parts
+  // rows (= tiles) in part order, a part's rows contiguous; the tile LIST ordered by kind
+  std::vector<gp::FactorDesc> rows;
+  std::vector<long> corr_offset;
+  std::vector<int> part_member;
+  std::vector<gp::CorrTile> tiles;
+  long total_corr = 0;
+  std::vector<char> search;
+  std::vector<gp::CorrBatchDesc> descs;
+  std::vector<gp::LoamBatchDesc> ldescs;
+  std::vector<gp::ColoredBatchDesc> cdescs;
+
+  // the members of one kind, in record order behind those already there: push_parts(member, record index) appends the member's parts
+  template <class F, class PUSH>
+  int add_members(const F* const* members, int count, const char* what, const char* a_what, PUSH&& push_parts) {
+    for (int i = 0; i < count; i++) {
+      const F* f = members[i];
+      if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, std::string("gp_corr_batch_create: null ") + what + " factor");
+      // the keep-or-search decision of the update tolerances is host logic on a host pose: in a batch every linearise searches (the reference's default)
+      if (f->upd.tol_rot != 0.0 || f->upd.tol_trans != 0.0)
+        return gp::fail(GP_ERROR_INVALID_ARGUMENT, std::string("gp_corr_batch_create: ") + a_what + " factor with non-zero correspondence-update tolerances cannot join a batch");
+      const int first = (int)parts.size();
+      push_parts(f, (int)member_parts.size());
+      member_parts.push_back(make_int2(first, (int)parts.size() - first));
+    }
+    return GP_OK;
+  }
+
+  int lay_out(gp_corr_batch* b) {
+    const int P = (int)parts.size();
+    b->F = (int)member_parts.size();
+    b->P = P;
+    b->combine = P != b->F;
+    rows.assign((size_t)P, gp::FactorDesc{});
+    corr_offset.resize((size_t)P);
+    part_member.resize((size_t)P);
+    std::vector<gp::CorrTile> by_kind[gp_corr_batch::NUM_KINDS];
+    int row = 0;
+    for (int p = 0; p < P; p++) {
+      const Part& part = parts[(size_t)p];
+      const int n = part.core->n;
+      part_member[(size_t)p] = part.member;
+      corr_offset[(size_t)p] = total_corr;
+      total_corr += (long)part.k * n;
+      b->total_points += n;
+      b->validate = b->validate || (part.loam && part.loam->validation);
+      rows[(size_t)p].n = n;
+      rows[(size_t)p].tile_begin = row;
+      for (int begin = 0; begin < n; begin += gp::kTilePoints) by_kind[part.kind].push_back(gp::CorrTile{p, begin, std::min(gp::kTilePoints, n - begin), row++});
+      rows[(size_t)p].tile_count = row - rows[(size_t)p].tile_begin;
+    }
+    b->num_tiles = row;
+    for (int k = 0; k < gp_corr_batch::NUM_KINDS; k++) {
+      b->kind_begin[k] = (int)tiles.size();
+      b->kind_count[k] = (int)by_kind[k].size();
+      tiles.insert(tiles.end(), by_kind[k].begin(), by_kind[k].end());
+    }
+    b->tiles_1nn = b->kind_begin[gp_corr_batch::LOAM_EDGE];
+    b->tiles_knn = (int)tiles.size() - b->tiles_1nn;
+    if (b->tiles_knn == 0) b->validate = false;
+    if (total_corr > 0x7fffffffl) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: more than 2^31 - 1 correspondences in one batch");
+    return GP_OK;
+  }
+
+  // the correspondence sets and the partial rows, then what the search and each kind's tile kernel read of part p (three tables [P] indexed by t.factor; a part
+  // fills the entry of its own kind's table)
+  int describe_parts(gp_corr_batch* b) {
+    const int P = b->P;
+    for (int k = 0; k < 2; k++) GP_TRY(b->d_corr[k].alloc(sizeof(int) * (size_t)std::max(total_corr, 1l)));
+    GP_TRY(b->d_partials_lin.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(b->num_tiles, 1)));
+    GP_TRY(b->d_partials_err.alloc(sizeof(double) * gp::ACC_STRIDE * (size_t)std::max(b->num_tiles, 1)));
+    search.resize(gp::corr_search_desc_bytes() * (size_t)P);
+    descs.assign((size_t)P, gp::CorrBatchDesc{});
+    ldescs.assign((size_t)P, gp::LoamBatchDesc{});
+    cdescs.assign((size_t)P, gp::ColoredBatchDesc{});
+    for (int p = 0; p < P; p++) {
+      const Part& part = parts[(size_t)p];
+      const gp_corr_factor_core* c = part.core;
+      int* c0 = b->d_corr[0].as<int>() + corr_offset[(size_t)p];
+      int* c1 = b->d_corr[1].as<int>() + corr_offset[(size_t)p];
+      gp::fill_corr_search_desc(search.data(), p, c->grid, c->points, c->n, c->max_sq_dist, c0, c1, part.k);
+      gp::CorrBatchDesc& d = descs[(size_t)p];
+      if (part.kind == gp_corr_batch::COLORED) {
+        cdescs[(size_t)p] = gp::ColoredBatchDesc{static_cast<const gp_colored_gicp_factor*>(c)->term, {c0, c1}};  // (the weight as it stands now; the cut-off went into the search table)
+      } else if (part.kind == gp_corr_batch::GICP) {
+        const gp::GicpTerm& t = static_cast<const gp_gicp_factor*>(c)->term;
+        d.points = t.points, d.covs = t.covs, d.target_points = t.target_points, d.target_covs = t.target_covs;
+      } else if (part.loam) {
+        const gp::LoamDesc& t = static_cast<const gp_loam_part*>(c)->desc;
+        ldescs[(size_t)p] = gp::LoamBatchDesc{t.points, t.target_points, {c0, c1}, c->n, part.k, part.loam->validation ? 1 : 0, 0};
+      } else {
+        const gp::IcpDesc& t = static_cast<const gp_icp_factor*>(c)->desc;
+        d.points = t.points, d.target_points = t.target_points, d.target_normals = t.target_normals;
+      }
+      d.corr[0] = c0, d.corr[1] = c1;
+    }
+    return GP_OK;
+  }
+
+  int upload(gp_corr_batch* b) {
+    GP_TRY(gp::upload(b->d_search, search));
+    GP_TRY(gp::upload(b->d_descs, descs));
+    GP_TRY(gp::upload(b->d_loam_descs, ldescs));
+    GP_TRY(gp::upload(b->d_colored_descs, cdescs));
+    GP_TRY(gp::upload(b->d_tiles, tiles));
+    GP_TRY(gp::upload(b->d_rows, rows));
+    GP_TRY(gp::upload(b->d_part_member, part_member));
+    GP_TRY(gp::upload(b->d_member_parts, member_parts));
+    if (b->combine) {
+      for (int k = 0; k < 2; k++) GP_TRY(b->d_part_poses[k].alloc(sizeof(double) * 16 * (size_t)b->P));
+      GP_TRY(b->d_part_records.alloc(sizeof(gp_linearized6) * (size_t)b->P));
+      GP_TRY(b->d_part_errors.alloc(sizeof(double) * (size_t)b->P));
+    }
+    return GP_OK;
+  }
+};
 
 extern "C" {
 
@@ -304,160 +425,30 @@ int gp_corr_batch_create_ex2(const gp_gicp_factor_t* const* gicp, int num_gicp, 
       (num_colored > 0 && !colored))
     return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: bad arguments");
   if (num_gicp + num_icp + num_loam + num_colored == 0) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an empty batch");
-  const int F = num_gicp + num_icp + num_loam + num_colored;
-  // the parts in record order: a GICP / ICP / colored GICP member is one, a LOAM member its edge part and / or its plane part, in that order
-  struct Part {
-    const gp_corr_factor_core* core;
-    int kind, member, k;
-    const gp_loam_factor* loam;
-  };
-  std::vector<Part> parts;
-  std::vector<int2> member_parts((size_t)F);
-  for (int i = 0; i < num_gicp; i++) {
-    if (!gicp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null GICP factor");
-    member_parts[(size_t)i] = make_int2((int)parts.size(), 1);
-    parts.push_back({gicp[i], gp_corr_batch::GICP, i, 1, nullptr});
-  }
-  for (int i = 0; i < num_icp; i++) {
-    if (!icp[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null ICP factor");
-    // the keep-or-search decision of the update tolerances is host logic on a host pose: in a batch every linearise searches (the reference's default)
-    if (icp[i]->tol_rot != 0.0 || icp[i]->tol_trans != 0.0)
-      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: an ICP factor with non-zero correspondence-update tolerances cannot join a batch");
-    member_parts[(size_t)(num_gicp + i)] = make_int2((int)parts.size(), 1);
-    parts.push_back({icp[i], icp[i]->plane ? gp_corr_batch::ICP_PLANE : gp_corr_batch::ICP_POINT, num_gicp + i, 1, nullptr});
-  }
-  bool validate = false;
-  for (int i = 0; i < num_loam; i++) {
-    const gp_loam_factor* l = loam[i];
-    if (!l) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null LOAM factor");
-    if (l->tol_rot != 0.0 || l->tol_trans != 0.0)
-      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: a LOAM factor with non-zero correspondence-update tolerances cannot join a batch");
-    const int m = num_gicp + num_icp + i;
-    member_parts[(size_t)m] = make_int2((int)parts.size(), (l->edge ? 1 : 0) + (l->plane ? 1 : 0));
-    if (l->edge) parts.push_back({l->edge.get(), gp_corr_batch::LOAM_EDGE, m, 2, l});
-    if (l->plane) parts.push_back({l->plane.get(), gp_corr_batch::LOAM_PLANE, m, 3, l});
-    validate = validate || l->validation;
-  }
-  for (int i = 0; i < num_colored; i++) {
-    if (!colored[i]) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: null colored GICP factor");
-    if (colored[i]->tol_rot != 0.0 || colored[i]->tol_trans != 0.0)
-      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: a colored GICP factor with non-zero correspondence-update tolerances cannot join a batch");
-    const int m = num_gicp + num_icp + num_loam + i;
-    member_parts[(size_t)m] = make_int2((int)parts.size(), 1);
-    parts.push_back({colored[i], gp_corr_batch::COLORED, m, 1, nullptr});
-  }
-  for (const Part& p : parts)
+
+  BatchTables t;
+  using B = gp_corr_batch;
+  GP_TRY(t.add_members(gicp, num_gicp, "GICP", "a GICP", [&](const gp_gicp_factor* f, int m) { t.parts.push_back({f, B::GICP, m, 1, nullptr}); }));
+  GP_TRY(t.add_members(icp, num_icp, "ICP", "an ICP", [&](const gp_icp_factor* f, int m) { t.parts.push_back({f, f->plane ? B::ICP_PLANE : B::ICP_POINT, m, 1, nullptr}); }));
+  GP_TRY(t.add_members(loam, num_loam, "LOAM", "a LOAM", [&](const gp_loam_factor* l, int m) {
+    if (l->edge) t.parts.push_back({l->edge.get(), B::LOAM_EDGE, m, 2, l});
+    if (l->plane) t.parts.push_back({l->plane.get(), B::LOAM_PLANE, m, 3, l});
+  }));
+  GP_TRY(t.add_members(colored, num_colored, "colored GICP", "a colored GICP", [&](const gp_colored_gicp_factor* f, int m) { t.parts.push_back({f, B::COLORED, m, 1, nullptr}); }));
+  for (const BatchTables::Part& p : t.parts)
     if (p.core->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
-  const int P = (int)parts.size();
 
   auto b = std::make_unique<gp_corr_batch>();
   b->stream = (hipStream_t)stream;
-  b->F = F;
-  b->P = P;
-  b->combine = P != F;
-  b->validate = validate;
-  // rows (= tiles) in part order, a part's rows contiguous; the tile LIST ordered by kind
-  std::vector<gp::FactorDesc> rows((size_t)P);
-  std::vector<long> corr_offset((size_t)P);
-  std::vector<int> part_member((size_t)P);
-  std::vector<gp::CorrTile> by_kind[gp_corr_batch::NUM_KINDS];
-  long total_corr = 0;
-  int row = 0;
-  for (int p = 0; p < P; p++) {
-    const int n = parts[(size_t)p].core->n;
-    part_member[(size_t)p] = parts[(size_t)p].member;
-    corr_offset[(size_t)p] = total_corr;
-    total_corr += (long)parts[(size_t)p].k * n;
-    b->total_points += n;
-    rows[(size_t)p] = gp::FactorDesc{};
-    rows[(size_t)p].n = n;
-    rows[(size_t)p].tile_begin = row;
-    for (int begin = 0; begin < n; begin += gp::kTilePoints) by_kind[parts[(size_t)p].kind].push_back(gp::CorrTile{p, begin, std::min(gp::kTilePoints, n - begin), row++});
-    rows[(size_t)p].tile_count = row - rows[(size_t)p].tile_begin;
-  }
-  b->num_tiles = row;
-  std::vector<gp::CorrTile> tiles;
-  for (int k = 0; k < gp_corr_batch::NUM_KINDS; k++) {
-    b->kind_begin[k] = (int)tiles.size();
-    b->kind_count[k] = (int)by_kind[k].size();
-    tiles.insert(tiles.end(), by_kind[k].begin(), by_kind[k].end());
-  }
-  b->tiles_1nn = b->kind_begin[gp_corr_batch::LOAM_EDGE];
-  b->tiles_knn = (int)tiles.size() - b->tiles_1nn;
-  if (b->tiles_knn == 0) b->validate = false;
-  if (total_corr > 0x7fffffffl) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: more than 2^31 - 1 correspondences in one batch");
-
-  for (int k = 0; k < 2; k++) GP_TRY(b->d_corr[k].alloc(sizeof(int) * (size_t)std::max(total_corr, 1l)));
-  GP_TRY(b->d_partials_lin.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(b->num_tiles, 1)));
-  GP_TRY(b->d_partials_err.alloc(sizeof(double) * gp::ACC_STRIDE * (size_t)std::max(b->num_tiles, 1)));
-  std::vector<char> search(gp::corr_search_desc_bytes() * (size_t)P);
-  std::vector<gp::CorrBatchDesc> descs((size_t)P);
-  std::vector<gp::LoamBatchDesc> ldescs((size_t)P);
-  std::vector<gp::ColoredBatchDesc> cdescs((size_t)P);
-  for (int p = 0; p < P; p++) {
-    const Part& part = parts[(size_t)p];
-    const gp_corr_factor_core* c = part.core;
-    int* c0 = b->d_corr[0].as<int>() + corr_offset[(size_t)p];
-    int* c1 = b->d_corr[1].as<int>() + corr_offset[(size_t)p];
-    gp::fill_corr_search_desc(search.data(), p, c->grid, c->points, c->n, c->max_sq_dist, c0, c1, part.k);
-    gp::CorrBatchDesc& d = descs[(size_t)p];
-    d = gp::CorrBatchDesc{};
-    ldescs[(size_t)p] = gp::LoamBatchDesc{};
-    cdescs[(size_t)p] = gp::ColoredBatchDesc{};
-    if (part.kind == gp_corr_batch::COLORED) {
-      cdescs[(size_t)p] = gp::ColoredBatchDesc{static_cast<const gp_colored_gicp_factor*>(c)->term, {c0, c1}};  // (the weight as it stands now; the cut-off went into the search table)
-    } else if (part.kind == gp_corr_batch::GICP) {
-      const gp::GicpTerm& t = static_cast<const gp_gicp_factor*>(c)->term;
-      d.points = t.points, d.covs = t.covs, d.target_points = t.target_points, d.target_covs = t.target_covs;
-    } else if (part.loam) {
-      const gp::LoamDesc& t = static_cast<const gp_loam_part*>(c)->desc;
-      ldescs[(size_t)p] = gp::LoamBatchDesc{t.points, t.target_points, {c0, c1}, c->n, part.k, part.loam->validation ? 1 : 0, 0};
-    } else {
-      const gp::IcpDesc& t = static_cast<const gp_icp_factor*>(c)->desc;
-      d.points = t.points, d.target_points = t.target_points, d.target_normals = t.target_normals;
-    }
-    d.corr[0] = c0, d.corr[1] = c1;
-  }
-  GP_TRY(b->d_search.alloc(search.size()));
-  GP_TRY(b->d_descs.alloc(sizeof(gp::CorrBatchDesc) * (size_t)P));
-  GP_TRY(b->d_loam_descs.alloc(sizeof(gp::LoamBatchDesc) * (size_t)P));
-  GP_TRY(b->d_colored_descs.alloc(sizeof(gp::ColoredBatchDesc) * (size_t)P));
-  GP_TRY(b->d_tiles.alloc(sizeof(gp::CorrTile) * std::max(tiles.size(), (size_t)1)));
-  GP_TRY(b->d_rows.alloc(sizeof(gp::FactorDesc) * (size_t)P));
-  GP_TRY(b->d_part_member.alloc(sizeof(int) * (size_t)P));
-  GP_TRY(b->d_member_parts.alloc(sizeof(int2) * (size_t)F));
-  GP_HIP(hipMemcpy(b->d_search.ptr, search.data(), search.size(), hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_descs.ptr, descs.data(), sizeof(gp::CorrBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_loam_descs.ptr, ldescs.data(), sizeof(gp::LoamBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_colored_descs.ptr, cdescs.data(), sizeof(gp::ColoredBatchDesc) * (size_t)P, hipMemcpyHostToDevice));
-  if (!tiles.empty()) GP_HIP(hipMemcpy(b->d_tiles.ptr, tiles.data(), sizeof(gp::CorrTile) * tiles.size(), hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_rows.ptr, rows.data(), sizeof(gp::FactorDesc) * (size_t)P, hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_part_member.ptr, part_member.data(), sizeof(int) * (size_t)P, hipMemcpyHostToDevice));
-  GP_HIP(hipMemcpy(b->d_member_parts.ptr, member_parts.data(), sizeof(int2) * (size_t)F, hipMemcpyHostToDevice));
-  if (b->combine) {
-    for (int k = 0; k < 2; k++) GP_TRY(b->d_part_poses[k].alloc(sizeof(double) * 16 * (size_t)P));
-    GP_TRY(b->d_part_records.alloc(sizeof(gp_linearized6) * (size_t)P));
-    GP_TRY(b->d_part_errors.alloc(sizeof(double) * (size_t)P));
-  }
-
-  const size_t pb = sizeof(double) * 16 * (size_t)F;
-  for (int k = 0; k < 2; k++) GP_TRY(b->d_poses[k].alloc(pb));
-  GP_TRY(b->h_poses.ensure(2 * pb));
-  GP_TRY(b->h_out.ensure(sizeof(gp_linearized6) * (size_t)F));
-  GP_HIP(hipHostGetDevicePointer(&b->h_out_dev, b->h_out.ptr, 0));
-  GP_TRY(b->h_done.ensure(sizeof(unsigned long long) * (size_t)F));
-  memset(b->h_done.ptr, 0, b->h_done.bytes);
-  GP_HIP(hipHostGetDevicePointer(&b->h_done_dev, b->h_done.ptr, 0));
+  GP_TRY(t.lay_out(b.get()));
+  GP_TRY(t.describe_parts(b.get()));
+  GP_TRY(t.upload(b.get()));
+  GP_TRY(b->alloc_staging());
   *out = b.release();
   return GP_OK;
 }
 
-int gp_corr_batch_destroy(gp_corr_batch_t* b) {
-  if (!b) return GP_OK;
-  (void)hipStreamSynchronize(b->stream);
-  delete b;  // (the factors are the caller's)
-  return GP_OK;
-}
+int gp_corr_batch_destroy(gp_corr_batch_t* b) { return gp_corr_destroy(b); }  // (the factors are the caller's)
 
 int gp_corr_batch_size(const gp_corr_batch_t* b) { return b ? b->F : 0; }
 
@@ -490,10 +481,10 @@ int gp_corr_batch_issue_compute_error_dev(gp_corr_batch_t* b, int set, const dou
 int gp_corr_batch_linearize(gp_corr_batch_t* b, const double* poses_host, int rigid, gp_linearized6* out_host) {
   if (!b || !poses_host || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_linearize: null");
   GP_TRY(b->stage_poses(poses_host, 0));
-  const gp::DoneFlags done{static_cast<unsigned long long*>(b->h_done_dev), ++b->seq};
-  GP_TRY(b->issue_linearize(b->d_poses[0].as<double>(), rigid != 0, 0, static_cast<gp_linearized6*>(b->h_out_dev), done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(b->h_done.ptr), (size_t)b->F, done.seq, b->stream, b->spin_us()));
-  memcpy(out_host, b->h_out.ptr, sizeof(gp_linearized6) * (size_t)b->F);
+  const gp::DoneFlags done = b->res.next();
+  GP_TRY(b->issue_linearize(b->d_poses[0].as<double>(), rigid != 0, 0, static_cast<gp_linearized6*>(b->res.out_dev), done));
+  GP_TRY(gp::wait_done(b->res.words(), (size_t)b->F, done.seq, b->stream, b->spin_us()));
+  memcpy(out_host, b->res.out.ptr, sizeof(gp_linearized6) * (size_t)b->F);
   return GP_OK;
 }
 

@@ -27,9 +27,9 @@ __global__ void __launch_bounds__(256) loam_validate_kernel(const float* __restr
 // host side
 // ---------------------------------------------------------------------------------------------------------------
 
-// (the handles: gp_corr_factors.hpp)
+// (the handles: gp_corr_factors.hpp; the tile kernel, the synchronous pass over the stored correspondences and the update rule around it: gp_corr_tile.hpp)
 
-// (the tile kernel and the synchronous pass over the stored correspondences: gp_corr_tile.hpp)
+int gp_gicp_factor::run_pass(const double* pose_lin, const double* pose_eval, void* out_host) { return gp_corr_factor_core::run_pass(term, pose_lin, pose_eval, out_host); }
 
 int gp_icp_factor::run_pass(const double* pose_lin, const double* pose_eval, void* out_host) {
   if (plane) return gp_corr_factor_core::run_pass(gp::IcpTerm<true>{desc}, pose_lin, pose_eval, out_host);
@@ -48,16 +48,13 @@ int gp_loam_part::validate() {
   return GP_OK;
 }
 
-static bool icp_keep_correspondences(const gp_icp_factor* f, const double* delta) { return keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, delta); }
-
 // ---- LOAM factor: what the entry points share ----
 
 // the searches of both parts at `pose`, with the validation behind them when it is enabled
 static int loam_search(gp_loam_factor* f, const double* pose) {
   for (gp_loam_part* p : {f->edge.get(), f->plane.get()})
     if (p && p->num_tiles > 0) GP_TRY(p->search_k(p->k, pose));
-  memcpy(f->corr_pose, pose, sizeof(double) * 16);
-  f->corr_valid = true;
+  f->upd.note_search(pose);
   return GP_OK;
 }
 
@@ -91,26 +88,17 @@ int gp_gicp_factor_create_ex(const float* target_points_dev, const float* target
   return GP_OK;
 }
 
-int gp_gicp_factor_destroy(gp_gicp_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (and its grid)
-  return GP_OK;
-}
+int gp_gicp_factor_destroy(gp_gicp_factor_t* f) { return gp_corr_destroy(f); }  // (and its grid)
 
-// A linearise always searches (IntegratedGICPFactor_::linearize calls update_correspondences every time, the default update tolerances being zero); an error
-// evaluation re-uses the stored correspondences when they belong to its linearisation pose -- the reference's error() evaluates on the correspondences of the
-// last linearise (impl.hpp:183-185).
+// (the update rule with zero tolerances: a linearise always searches, an error evaluation at the pose of the last search does not -- gp_corr_tile.hpp)
 int gp_gicp_factor_linearize(gp_gicp_factor_t* f, const double pose[16], gp_linearized6* out_host) {
   if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_gicp_factor_linearize: null");
-  if (f->num_tiles > 0) GP_TRY(f->search(pose));
-  return f->run_pass(f->term, pose, nullptr, out_host);
+  return corr_factor_linearize(f, pose, out_host);
 }
 
 int gp_gicp_factor_compute_error(gp_gicp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
   if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_gicp_factor_compute_error: null");
-  if (f->num_tiles > 0 && !f->searched_at(pose_lin)) GP_TRY(f->search(pose_lin));
-  return f->run_pass(f->term, pose_lin, pose_eval, out_host);
+  return corr_factor_compute_error(f, pose_lin, pose_eval, out_host);
 }
 
 // ---- ICP factor -----------------------------------------------------------------------------------------------------
@@ -128,41 +116,22 @@ int gp_icp_factor_create(const gp_point_grid_t* grid, const float* target_points
   return GP_OK;
 }
 
-int gp_icp_factor_destroy(gp_icp_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (the grid is the caller's)
-  return GP_OK;
-}
+int gp_icp_factor_destroy(gp_icp_factor_t* f) { return gp_corr_destroy(f); }  // (the grid is the caller's)
 
 int gp_icp_factor_set_correspondence_update_tolerance(gp_icp_factor_t* f, double angle, double trans) {
-  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_set_correspondence_update_tolerance: null");
-  f->tol_rot = angle;
-  f->tol_trans = trans;
-  return GP_OK;
+  return gp_corr_set_update_tolerance(f ? &f->upd : nullptr, angle, trans, "gp_icp_factor_set_correspondence_update_tolerance");
 }
 
-int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f) { return f ? f->num_correspondences : 0; }
+int gp_icp_factor_num_correspondences(const gp_icp_factor_t* f) { return f ? f->num_inliers : 0; }
 
 int gp_icp_factor_linearize(gp_icp_factor_t* f, const double pose[16], gp_linearized6* out_host) {
   if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_linearize: null");
-  if (f->num_tiles > 0 && !icp_keep_correspondences(f, pose)) GP_TRY(f->search(pose));
-  memcpy(f->lin_pose, pose, sizeof(double) * 16);
-  f->lin_valid = true;
-  GP_TRY(f->run_pass(pose, nullptr, out_host));
-  f->num_correspondences = (int)out_host->num_inliers;
-  return GP_OK;
+  return corr_factor_linearize(f, pose, out_host);
 }
 
 int gp_icp_factor_compute_error(gp_icp_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
   if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_icp_factor_compute_error: null");
-  // the stored correspondences serve when pose_lin is the pose of the last linearise (which may itself have kept older ones) or the pose they were searched at
-  const bool stored = f->corr_valid && ((f->lin_valid && memcmp(f->lin_pose, pose_lin, sizeof(double) * 16) == 0) || f->searched_at(pose_lin));
-  if (f->num_tiles > 0 && !stored) {
-    GP_TRY(f->search(pose_lin));
-    f->lin_valid = false;
-  }
-  return f->run_pass(pose_lin, pose_eval, out_host);
+  return corr_factor_compute_error(f, pose_lin, pose_eval, out_host);
 }
 
 // ---- LOAM factor ----------------------------------------------------------------------------------------------------
@@ -196,12 +165,7 @@ int gp_loam_factor_create(const gp_point_grid_t* edge_grid, const float* target_
   return GP_OK;
 }
 
-int gp_loam_factor_destroy(gp_loam_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (the grids are the caller's)
-  return GP_OK;
-}
+int gp_loam_factor_destroy(gp_loam_factor_t* f) { return gp_corr_destroy(f); }  // (the grids are the caller's)
 
 int gp_loam_factor_set_max_correspondence_distance(gp_loam_factor_t* f, double dist_edge, double dist_plane) {
   if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_max_correspondence_distance: null");
@@ -218,10 +182,7 @@ int gp_loam_factor_set_enable_correspondence_validation(gp_loam_factor_t* f, int
 }
 
 int gp_loam_factor_set_correspondence_update_tolerance(gp_loam_factor_t* f, double angle, double trans) {
-  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_set_correspondence_update_tolerance: null");
-  f->tol_rot = angle;
-  f->tol_trans = trans;
-  return GP_OK;
+  return gp_corr_set_update_tolerance(f ? &f->upd : nullptr, angle, trans, "gp_loam_factor_set_correspondence_update_tolerance");
 }
 
 int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, int* planes) {
@@ -233,7 +194,7 @@ int gp_loam_factor_num_correspondences(const gp_loam_factor_t* f, int* edges, in
 
 int gp_loam_factor_get_correspondences(const gp_loam_factor_t* f, int* edges_host, int* planes_host) {
   if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_get_correspondences: null");
-  if (!f->corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_get_correspondences: no correspondences are stored (never linearised)");
+  if (!f->upd.corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_get_correspondences: no correspondences are stored (never linearised)");
   GP_HIP(hipStreamSynchronize(f->stream));
   if (edges_host && f->edge && f->edge->n > 0) GP_HIP(hipMemcpy(edges_host, f->edge->corr.as<int>(), sizeof(int) * 2 * (size_t)f->edge->n, hipMemcpyDeviceToHost));
   if (planes_host && f->plane && f->plane->n > 0) GP_HIP(hipMemcpy(planes_host, f->plane->corr.as<int>(), sizeof(int) * 3 * (size_t)f->plane->n, hipMemcpyDeviceToHost));
@@ -248,10 +209,9 @@ static void loam_add(const double* edge, const double* plane, double* out, size_
 
 int gp_loam_factor_linearize(gp_loam_factor_t* f, const double pose[16], gp_linearized6* out_host) {
   if (!f || !pose || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_linearize: null");
-  if (!keep_correspondences(f->corr_valid, f->corr_pose, f->tol_rot, f->tol_trans, pose)) GP_TRY(loam_search(f, pose));
+  if (!f->upd.keep(pose)) GP_TRY(loam_search(f, pose));
   GP_TRY(loam_validate(f));  // (also behind kept correspondences, as update_correspondences :444-449 does: it is idempotent)
-  memcpy(f->lin_pose, pose, sizeof(double) * 16);
-  f->lin_valid = true;
+  f->upd.note_linearize(pose);
   gp_linearized6 e{}, p{};
   if (f->edge) GP_TRY(f->edge->run_pass(pose, nullptr, &e));
   if (f->plane) GP_TRY(f->plane->run_pass(pose, nullptr, &p));
@@ -265,11 +225,9 @@ int gp_loam_factor_linearize(gp_loam_factor_t* f, const double pose[16], gp_line
 
 int gp_loam_factor_compute_error(gp_loam_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host) {
   if (!f || !pose_lin || !pose_eval || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_loam_factor_compute_error: null");
-  const bool stored = f->corr_valid && ((f->lin_valid && memcmp(f->lin_pose, pose_lin, sizeof(double) * 16) == 0) || memcmp(f->corr_pose, pose_lin, sizeof(double) * 16) == 0);
-  if (!stored) {
+  if (!f->upd.stored(pose_lin)) {
     GP_TRY(loam_search(f, pose_lin));
     GP_TRY(loam_validate(f));
-    f->lin_valid = false;
   }
   double e = 0.0, p = 0.0;
   if (f->edge) GP_TRY(f->edge->run_pass(pose_lin, pose_eval, &e));

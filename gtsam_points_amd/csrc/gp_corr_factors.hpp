@@ -1,10 +1,12 @@
-// gp_corr_factors.hpp -- what the single-factor entry points of the matching-cost factors (gp_corr_factors.hip) share with their batch (gp_corr_batch.hip): the
-// per-point terms of GICP and ICP, the reduction of a tile's sums into its partial row, and the factor handles the batch borrows.
+// gp_corr_factors.hpp -- what the single-factor entry points of the matching-cost factors (gp_corr_factors.hip, gp_colored_factors.hip, gp_ct_factors.hip) share with
+// their batch (gp_corr_batch.hip): the per-point terms of GICP, ICP and LOAM, the reduction of a tile's sums into its partial row, the core every factor handle is
+// built on (with the tail of a synchronous pass and the mapped result block) and the handles the batch borrows.
 #pragma once
 #include <cmath>
 #include <cstring>
 #include <memory>
 
+#include "gp_corr_update.hpp"
 #include "gp_host.hpp"
 #include "gp_vgicp_tile.hpp"
 
@@ -241,7 +243,29 @@ __device__ __forceinline__ void store_tile_sums(double* acc, double* __restrict_
 // host side: the factor handles
 // ---------------------------------------------------------------------------------------------------------------
 
-// what both factors keep: the search's inputs, the stored correspondences and the pose they belong to, the tile geometry and where a pass leaves its result
+namespace gp {
+
+// where a synchronous call's kernels leave its result: a block and its completion words (gp_vgicp_shared.hpp: DoneFlags) in host-mapped pinned memory, with the
+// device's pointers to both and the call's sequence number.  The single factors keep one record and one word, their batch one of each per member.
+struct MappedResults {
+  PinnedArray out, done;
+  void *out_dev = nullptr, *done_dev = nullptr;
+  unsigned long long seq = 0;
+  int ensure(size_t out_bytes, size_t words) {
+    GP_TRY(out.ensure(out_bytes));
+    GP_HIP(hipHostGetDevicePointer(&out_dev, out.ptr, 0));
+    GP_TRY(done.ensure(sizeof(unsigned long long) * words));
+    memset(done.ptr, 0, done.bytes);
+    GP_HIP(hipHostGetDevicePointer(&done_dev, done.ptr, 0));
+    return GP_OK;
+  }
+  DoneFlags next() { return DoneFlags{static_cast<unsigned long long*>(done_dev), ++seq}; }
+  const unsigned long long* words() const { return static_cast<const unsigned long long*>(done.ptr); }
+};
+
+}  // namespace gp
+
+// what every factor keeps: the search's inputs, the stored correspondences and the pose they belong to, the tile geometry and where a pass leaves its result
 struct gp_corr_factor_core {
   const gp_point_grid* grid = nullptr;  // the search structure over the target (the cut-off ends every search, whatever cell size it was built with)
   const float* points = nullptr;        // [n][3] source
@@ -251,13 +275,9 @@ struct gp_corr_factor_core {
   int tile_points = 1024;
   int num_tiles = 0;
   gp::DeviceArray partials, corr;  // corr: [n] correspondences of the last correspondence pass
-  gp::PinnedArray h_out;
-  void* h_out_dev = nullptr;
-  gp::PinnedArray h_done;  // completion word of the synchronous calls (gp_vgicp_shared.hpp: DoneFlags)
-  void* h_done_dev = nullptr;
-  unsigned long long seq = 0;
-  double corr_pose[16] = {0};  // last_correspondence_point: the pose the stored correspondences were searched at
-  bool corr_valid = false;
+  gp::MappedResults res;           // one record (or one error) and the completion word of the synchronous calls
+  gp_corr_update upd;              // (a LOAM part leaves its own unused: gp_loam_factor keeps one for both parts)
+  int num_inliers = 0;             // of the last linearise
 
   int prepare(const gp_point_grid* grid_, const float* points_dev, int n_, double max_sq_dist_, hipStream_t stream_) {
     grid = grid_;
@@ -268,21 +288,13 @@ struct gp_corr_factor_core {
     num_tiles = (n + tile_points - 1) / tile_points;
     GP_TRY(partials.alloc(sizeof(double) * gp::ACCG_STRIDE * (size_t)std::max(num_tiles, 1)));
     GP_TRY(corr.alloc(sizeof(int) * (size_t)std::max(n, 1)));
-    GP_TRY(h_out.ensure(sizeof(gp_linearized6)));
-    GP_HIP(hipHostGetDevicePointer(&h_out_dev, h_out.ptr, 0));
-    GP_TRY(h_done.ensure(sizeof(unsigned long long)));
-    memset(h_done.ptr, 0, h_done.bytes);
-    GP_HIP(hipHostGetDevicePointer(&h_done_dev, h_done.ptr, 0));
-    return GP_OK;
+    return res.ensure(sizeof(gp_linearized6), 1);
   }
-
-  bool searched_at(const double* pose) const { return corr_valid && memcmp(corr_pose, pose, sizeof(double) * 16) == 0; }
 
   // the correspondence pass at pose_lin (n > 0)
   int search(const double* pose_lin) {
     GP_TRY(gp::launch_nearest_correspondences(grid, points, n, pose_lin, max_sq_dist, corr.as<int>(), stream));
-    memcpy(corr_pose, pose_lin, sizeof(double) * 16);
-    corr_valid = true;
+    upd.note_search(pose_lin);
     return GP_OK;
   }
 
@@ -292,27 +304,44 @@ struct gp_corr_factor_core {
   // One synchronous pass over the stored correspondences (gp_corr_tile.hpp: defined there for the units that instantiate it with their terms).
   template <class TERM>
   int run_pass(const TERM& term, const double* pose_lin, const double* pose_eval, void* out_host);
+
+  // The tail of a synchronous pass, behind the tile kernel: the partial rows finalised into the mapped block -- the error (out_host a double), or the record at
+  // pose_lin (a gp_linearized6; general: the rows hold the 92 explicit sums, whose expansion does not read the pose) --, the wait for the completion word, the copy out.
+  int finish_pass(bool error, const double* pose_lin, bool general, void* out_host) {
+    const gp::DoneFlags done = res.next();
+    if (error)
+      GP_TRY(gp::launch_finalize_error_single(stream, partials.as<double>(), num_tiles, reinterpret_cast<double*>(res.out_dev), done));
+    else
+      GP_TRY(gp::launch_finalize_single(stream, nullptr, pose_lin, partials.as<double>(), num_tiles, reinterpret_cast<gp_linearized6*>(res.out_dev), general, done));
+    GP_TRY(gp::wait_done(res.words(), 1, done.seq, stream, 100 + (long)num_tiles * (long)tile_points / 1000));  // spin budget ~4x the kernel (0.2 ns per point)
+    memcpy(out_host, res.out.ptr, error ? sizeof(double) : sizeof(gp_linearized6));
+    return GP_OK;
+  }
 };
 
-// update_correspondences' decision (integrated_icp_factor_impl.hpp:129-137, integrated_loam_factor_impl.hpp:81-88, :236-243) on two column-major 4x4 poses:
-// diff = delta^-1 * last (the isometry inverse, R^T and -R^T t), its rotation angle and the norm of its translation against the tolerances, both strict
-inline bool keep_correspondences(bool corr_valid, const double* last, double tol_rot, double tol_trans, const double* delta) {
-  if (!corr_valid || !(tol_trans > 0.0 || tol_rot > 0.0)) return false;
-  double D[3][3], t[3];
-  for (int r = 0; r < 3; r++) {
-    for (int c = 0; c < 3; c++) D[r][c] = delta[4 * r] * last[4 * c] + delta[4 * r + 1] * last[4 * c + 1] + delta[4 * r + 2] * last[4 * c + 2];
-    t[r] = delta[4 * r] * (last[12] - delta[12]) + delta[4 * r + 1] * (last[13] - delta[13]) + delta[4 * r + 2] * (last[14] - delta[14]);
-  }
-  // angle in [0, pi] from sin (the skew part) and cos (the trace): what Eigen::AngleAxisd(diff.linear()).angle() gives for a rotation
-  const double sx = 0.5 * (D[2][1] - D[1][2]), sy = 0.5 * (D[0][2] - D[2][0]), sz = 0.5 * (D[1][0] - D[0][1]);
-  const double diff_rot = std::atan2(std::sqrt(sx * sx + sy * sy + sz * sz), 0.5 * (D[0][0] + D[1][1] + D[2][2] - 1.0));
-  const double diff_trans = std::sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
-  return diff_rot < tol_rot && diff_trans < tol_trans;
+// what every gp_*_destroy of this family does: the handle's stream runs dry, then the handle goes (a borrowed grid or member stays the caller's)
+template <class HANDLE>
+int gp_corr_destroy(HANDLE* h) {
+  if (!h) return GP_OK;
+  (void)hipStreamSynchronize(h->stream);
+  delete h;
+  return GP_OK;
 }
 
-struct gp_gicp_factor : gp_corr_factor_core {
-  gp_point_grid* own_grid = nullptr;  // OWNED: the factor's target 1-NN structure
+// set_correspondence_update_tolerance of the factor `who` (u: its update rule, null for a null handle)
+inline int gp_corr_set_update_tolerance(gp_corr_update* u, double angle, double trans, const char* who) {
+  if (!u) return gp::fail(GP_ERROR_INVALID_ARGUMENT, std::string(who) + ": null");
+  u->tol_rot = angle;
+  u->tol_trans = trans;
+  return GP_OK;
+}
+
+// The single factors on ONE nearest neighbour: the core, the per-point term and the pass that picks its tile kernel (each defined in the unit that instantiates the
+// kernels).  gp_corr_tile.hpp's corr_factor_linearize / _compute_error drive all three.
+struct gp_gicp_factor : gp_corr_factor_core {  // (zero update tolerances, never set: every linearise searches)
+  gp_point_grid* own_grid = nullptr;            // OWNED: the factor's target 1-NN structure
   gp::GicpTerm term{};
+  int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_corr_factors.hip)
   ~gp_gicp_factor() {
     if (own_grid) gp_point_grid_destroy(own_grid);
   }
@@ -321,10 +350,6 @@ struct gp_gicp_factor : gp_corr_factor_core {
 struct gp_icp_factor : gp_corr_factor_core {  // (the grid is BORROWED: the reference's target_tree, shared between factors)
   gp::IcpDesc desc{};
   bool plane = false;
-  double lin_pose[16] = {0};  // the pose of the last linearise (which may have kept older correspondences: the update tolerances)
-  bool lin_valid = false;
-  double tol_rot = 0.0, tol_trans = 0.0;  // correspondence_update_tolerance_rot / _trans (:32-33)
-  int num_correspondences = 0;
   int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_corr_factors.hip)
 };
 
@@ -342,8 +367,6 @@ struct gp_loam_factor {
   std::unique_ptr<gp_loam_part> edge, plane;
   hipStream_t stream = nullptr;
   bool validation = false;  // enable_correspondence_validation (off by default, :385)
-  double tol_rot = 0.0, tol_trans = 0.0;
-  double corr_pose[16] = {0}, lin_pose[16] = {0};
-  bool corr_valid = false, lin_valid = false;
+  gp_corr_update upd;
   int num_edges = 0, num_planes = 0;  // inliers of the last linearise, per part
 };

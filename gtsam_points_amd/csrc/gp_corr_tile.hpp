@@ -1,5 +1,5 @@
-// gp_corr_tile.hpp -- the tile kernel over stored correspondences and the synchronous pass that launches it, for the translation units that instantiate them with
-// their terms: gp_corr_factors.hip (GICP, ICP, LOAM) and gp_colored_factors.hip (colored GICP).  A unit's kernel-resource remarks list its own instantiations only.
+// gp_corr_tile.hpp -- the tile kernel over stored correspondences, the synchronous pass that launches it and the single factors' update rule around that pass, for
+// the translation units that instantiate them with their terms: gp_corr_factors.hip (GICP, ICP, LOAM) and gp_colored_factors.hip (colored GICP).  A unit's kernel-resource remarks list its own instantiations only.
 #pragma once
 #include "gp_corr_factors.hpp"
 
@@ -48,12 +48,24 @@ int gp_corr_factor_core::run_pass(const TERM& term, const double* pose_lin, cons
       hipLaunchKernelGGL((gp::corr_tile_kernel<gp::MODE_LIN_GENERAL, TERM>), dim3(num_tiles), dim3(256), 0, stream, term, P, n, tile_points, partials.as<double>(), corr.as<int>());
     GP_HIP(hipGetLastError());
   }
-  const gp::DoneFlags done{static_cast<unsigned long long*>(h_done_dev), ++seq};
-  if (pose_eval)
-    GP_TRY(gp::launch_finalize_error_single(stream, partials.as<double>(), num_tiles, reinterpret_cast<double*>(h_out_dev), done));
-  else
-    GP_TRY(gp::launch_finalize_single(stream, nullptr, pose_lin, partials.as<double>(), num_tiles, reinterpret_cast<gp_linearized6*>(h_out_dev), !rigid, done));
-  GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(h_done.ptr), 1, done.seq, stream, 100 + (long)num_tiles * (long)tile_points / 1000));  // spin budget ~4x the kernel (0.2 ns per point)
-  memcpy(out_host, h_out.ptr, pose_eval ? sizeof(double) : sizeof(gp_linearized6));
+  return finish_pass(pose_eval != nullptr, pose_lin, !rigid, out_host);
+}
+
+// The update rule of the single factors on one nearest neighbour (GICP, ICP, colored GICP; F: the handle), gp_corr_update deciding.  A linearise searches unless the
+// update tolerances keep the stored correspondences (GICP's are zero: it always searches -- IntegratedGICPFactor_::linearize calls update_correspondences every
+// time); an error evaluation re-uses the stored correspondences when they belong to its linearisation pose -- the reference's error() evaluates on those of the
+// last linearise (integrated_gicp_factor_impl.hpp:183-185) -- and searches at pose_lin otherwise.
+template <class F>
+int corr_factor_linearize(F* f, const double* pose, gp_linearized6* out_host) {
+  if (f->num_tiles > 0 && !f->upd.keep(pose)) GP_TRY(f->search(pose));
+  f->upd.note_linearize(pose);
+  GP_TRY(f->run_pass(pose, nullptr, out_host));
+  f->num_inliers = (int)out_host->num_inliers;
   return GP_OK;
+}
+
+template <class F>
+int corr_factor_compute_error(F* f, const double* pose_lin, const double* pose_eval, double* out_host) {
+  if (f->num_tiles > 0 && !f->upd.stored(pose_lin)) GP_TRY(f->search(pose_lin));
+  return f->run_pass(pose_lin, pose_eval, out_host);
 }

@@ -313,7 +313,6 @@ struct gp_ct_factor : gp_corr_factor_core {  // (the grid is BORROWED, as the IC
   std::vector<int> time_indices;
   gp::DeviceArray d_times, d_indices;   // double[bins], int[n]
   gp::DeviceArray table_lin, table_eval;  // double[bins][kCtPoseRow]: of the stored correspondences (T, D0, D1) / of the call in hand (T only)
-  int num_inliers = 0;
 
   int bins() const { return (int)time_table.size(); }
 
@@ -339,7 +338,7 @@ struct gp_ct_factor : gp_corr_factor_core {  // (the grid is BORROWED, as the IC
     s.max_sq_dist = max_sq_dist;
     hipLaunchKernelGGL(gp::ct_nearest_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, s, corr.as<int>());
     GP_HIP(hipGetLastError());
-    corr_valid = true;
+    upd.corr_valid = true;  // (of the update rule, a two-pose factor keeps this one word: a linearise always searches, an error evaluation only when nothing is stored)
     return GP_OK;
   }
 
@@ -365,14 +364,7 @@ struct gp_ct_factor : gp_corr_factor_core {  // (the grid is BORROWED, as the IC
       }
       GP_HIP(hipGetLastError());
     }
-    const gp::DoneFlags done{static_cast<unsigned long long*>(h_done_dev), ++seq};
-    if (error)
-      GP_TRY(gp::launch_finalize_error_single(stream, partials.as<double>(), num_tiles, reinterpret_cast<double*>(h_out_dev), done));
-    else  // (the general finalize is a plain expansion of the 92 sums: its pose argument is not read)
-      GP_TRY(gp::launch_finalize_single(stream, nullptr, pose0, partials.as<double>(), num_tiles, reinterpret_cast<gp_linearized6*>(h_out_dev), true, done));
-    GP_TRY(gp::wait_done(static_cast<const unsigned long long*>(h_done.ptr), 1, done.seq, stream, 100 + (long)num_tiles * (long)tile_points / 1000));
-    memcpy(out_host, h_out.ptr, error ? sizeof(double) : sizeof(gp_linearized6));
-    return GP_OK;
+    return finish_pass(error, pose0, true, out_host);  // (a two-pose factor has the 92 sums only: pose0 is not read)
   }
 };
 
@@ -426,12 +418,7 @@ int gp_ct_factor_create(const gp_point_grid_t* grid, const float* target_points_
   return GP_OK;
 }
 
-int gp_ct_factor_destroy(gp_ct_factor_t* f) {
-  if (!f) return GP_OK;
-  (void)hipStreamSynchronize(f->stream);
-  delete f;  // (the grid is the caller's)
-  return GP_OK;
-}
+int gp_ct_factor_destroy(gp_ct_factor_t* f) { return gp_corr_destroy(f); }  // (the grid is the caller's)
 
 // update_poses + update_correspondences + the sums (:132-199): a linearise always searches
 int gp_ct_factor_linearize(gp_ct_factor_t* f, const double pose0[16], const double pose1[16], gp_linearized6* out_host) {
@@ -446,7 +433,7 @@ int gp_ct_factor_linearize(gp_ct_factor_t* f, const double pose0[16], const doub
 int gp_ct_factor_compute_error(gp_ct_factor_t* f, const double pose0[16], const double pose1[16], double* out_host) {
   if (!f || !pose0 || !pose1 || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_compute_error: null");
   if (f->num_tiles > 0) {
-    if (!f->corr_valid) GP_TRY(f->search_at(pose0, pose1));
+    if (!f->upd.corr_valid) GP_TRY(f->search_at(pose0, pose1));
     GP_TRY(f->pose_table(pose0, pose1, false, f->table_eval.as<double>()));
   }
   return f->run(true, pose0, out_host);
@@ -480,7 +467,7 @@ int gp_ct_factor_time_table(const gp_ct_factor_t* f, double* table_host, int* in
 int gp_ct_factor_pose_table(gp_ct_factor_t* f, double* out_host) {
   if (!f || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_pose_table: null");
   if (f->n == 0) return GP_OK;
-  if (!f->corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_pose_table: no linearise or error evaluation yet");
+  if (!f->upd.corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_pose_table: no linearise or error evaluation yet");
   GP_HIP(hipMemcpyAsync(out_host, f->table_lin.ptr, sizeof(double) * gp::kCtPoseRow * (size_t)f->bins(), hipMemcpyDeviceToHost, f->stream));
   GP_HIP(hipStreamSynchronize(f->stream));
   return GP_OK;
@@ -489,7 +476,7 @@ int gp_ct_factor_pose_table(gp_ct_factor_t* f, double* out_host) {
 int gp_ct_factor_correspondences(gp_ct_factor_t* f, int* out_host) {
   if (!f || !out_host) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_correspondences: null");
   if (f->n == 0) return GP_OK;
-  if (!f->corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_correspondences: no linearise or error evaluation yet");
+  if (!f->upd.corr_valid) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_ct_factor_correspondences: no linearise or error evaluation yet");
   GP_HIP(hipMemcpyAsync(out_host, f->corr.ptr, sizeof(int) * (size_t)f->n, hipMemcpyDeviceToHost, f->stream));
   GP_HIP(hipStreamSynchronize(f->stream));
   return GP_OK;

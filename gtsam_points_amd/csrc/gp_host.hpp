@@ -240,6 +240,14 @@ struct DeviceArray {
   }
 };
 
+// a host table into a fresh device array of its size: hipMalloc and ONE synchronous hipMemcpy, so the host vector may go when the call returns
+template <typename T>
+int upload(DeviceArray& d, const std::vector<T>& h) {
+  GP_TRY(d.alloc(sizeof(T) * h.size()));
+  if (!h.empty()) GP_HIP(hipMemcpy(d.ptr, h.data(), sizeof(T) * h.size(), hipMemcpyHostToDevice));
+  return GP_OK;
+}
+
 struct PinnedArray {
   void* ptr = nullptr;
   size_t bytes = 0;

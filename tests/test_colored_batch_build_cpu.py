@@ -3,6 +3,7 @@
 (test_colored_build_cpu.py), and the batched form only adds the look-up of the tile, the descriptor and the poses in front of the point loop."""
 import ctypes as C
 import os
+import re
 
 from test_icp_build_cpu import ROOT, _assert_no_scratch
 
@@ -27,6 +28,31 @@ def test_other_batch_tile_kernels_are_still_instantiated():
     assert len([k for k in tiles if "IcpTerm" in k]) == 6
     assert len([k for k in tiles if "Loam" in k]) == 6
     assert len(tiles) == 18
+
+
+# The six LOAM instantiations of corr_batch_tiles_kernel<MODE, TERM, LoamBatchDesc> against the figures of loam_batch_tiles_kernel<MODE, TERM>, the kernel they were
+# before they joined the template (HIP 7.2 / AMD clang 22, gfx950), as upper bounds: (MODE, term) -> SGPRs (the remarks' TotalSGPRs), VGPRs, AGPRs, LDS bytes per workgroup; scratch and spills none.
+# The build this came with sits on every figure: the merged kernels are the separate ones instruction for instruction.
+LOAM_BOUNDS = {
+    (0, "LoamEdgeTerm"): (50, 118, 0, 13312),
+    (0, "LoamPlaneTerm"): (52, 124, 0, 13312),
+    (1, "LoamEdgeTerm"): (50, 46, 0, 13312),
+    (1, "LoamPlaneTerm"): (52, 60, 0, 13312),
+    (2, "LoamEdgeTerm"): (50, 256, 24, 15360),
+    (2, "LoamPlaneTerm"): (50, 256, 40, 15360),
+}
+
+
+def test_loam_batch_tile_kernels_keep_the_figures_of_their_own_kernel():
+    ks = _kernels()
+    assert not any("loam_batch_tiles_kernel" in k for k in ks)  # one template
+    for (mode, term), (sgprs, vgprs, agprs, lds) in LOAM_BOUNDS.items():
+        (name,) = [k for k in ks if f"corr_batch_tiles_kernelILi{mode}ENS_{len(term)}{term}ENS_13LoamBatchDescE" in k]
+        get = lambda key: int(re.search(re.escape(key) + r":\s+(\d+)", ks[name]).group(1))  # noqa: E731
+        got = (get("TotalSGPRs"), get("    VGPRs"), get("    AGPRs"), get("LDS Size [bytes/block]"))
+        print(name, got)
+        assert got[0] <= sgprs and got[1] <= vgprs and got[2] <= agprs and got[3] <= lds, (name, got)
+        _assert_no_scratch({name: ks[name]})
 
 
 def test_create_with_colored_members_refuses_bad_arguments_without_a_device():
