@@ -1,5 +1,6 @@
 // gp_damped_step.hpp -- the pieces of the damped step that the dense system (gp_solver.hip) and the block-sparse system (gp_sparse.hip, gp_sparse_multi.hpp, gp_sparse_small.hip) share: the gather of A and b
-// out of the factors' gp_linearized6 records, the error sum, the damping, the pivot rule, the host-side contribution lists and the pinned step hand-off.  Both
+// out of the factors' gp_linearized6 records, the error sum, the damping, the pivot rule, the host-side contribution lists (the pinned step hand-off and the seam the
+// two systems share towards their callers are gp_host.hpp's: StepHandoff, DampedSystem).  Both
 // systems call THESE, so a change to the step is made once and the two cannot drift apart.
 #pragma once
 #include <cstring>
@@ -128,35 +129,5 @@ void contribution_lists(const int* factor_slots, int num_factors, const std::vec
     contribs->insert(contribs->end(), kv.second.begin(), kv.second.end());
   }
 }
-
-// ---- the step hand-off ----------------------------------------------------------------------------------------------------------------------------------------------
-
-// gp_*_system_step in ONE synchronisation: the step's last kernels leave x [n] | b [n] | c | status in a pinned block that the host reads behind the stream.  A step in
-// flight owns that block and the system's device buffers until finish_step / collect_step: a second issue is refused, not queued over it.  `api` names the entry
-// points in the messages ("gp_dense_system", "gp_sparse_system").
-struct StepHandoff {
-  PinnedArray pinned;
-  bool in_flight = false;  // issue_step went out, finish_step / collect_step has not collected it
-
-  // in front of an issue: the block for n unknowns, or the refusal while a step is in flight
-  int begin(const char* api, size_t n) {
-    if (in_flight) return fail(GP_ERROR_INVALID_ARGUMENT, std::string(api) + "_issue_step: a step is in flight (finish it first)");
-    return pinned.ensure(sizeof(double) * (2 * n + 2));
-  }
-  double* host() { return pinned.as<double>(); }
-
-  // finish_step (wait = true) / collect_step (the caller has SEEN the stream pass the step): b and c handed over also when the system is indeterminate, x only when not
-  int finish(const char* api, hipStream_t stream, size_t n, bool wait, double* x_host, double* b_host, double* c_host) {
-    if (!in_flight) return fail(GP_ERROR_INVALID_ARGUMENT, std::string(api) + "_finish_step: no step was issued");
-    const double* h = pinned.as<double>();
-    in_flight = false;
-    if (wait) GP_HIP(hipStreamSynchronize(stream));
-    if (b_host) memcpy(b_host, h + n, sizeof(double) * n);
-    if (c_host) *c_host = h[2 * n];
-    if (h[2 * n + 1] != 0.0) return fail(GP_ERROR_INDETERMINATE, std::string(api) + "_step: the system is not positive definite (indeterminate linear system)");
-    if (x_host) memcpy(x_host, h, sizeof(double) * n);
-    return GP_OK;
-  }
-};
 
 }  // namespace gp

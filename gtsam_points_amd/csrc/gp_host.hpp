@@ -7,6 +7,7 @@
 #include <atomic>
 #include <memory>
 #include <chrono>
+#include <cstring>
 #include <mutex>
 #include <string>
 #include <unordered_map>
@@ -477,6 +478,89 @@ int launch_nearest_correspondences_batch(const void* table_dev, const CorrTile* 
 // the same over tiles of table entries with k = 2 or 3
 int launch_nearest_k_correspondences_batch(const void* table_dev, const CorrTile* tiles_dev, int num_tiles, const double* poses_dev, int set, hipStream_t stream);
 }  // namespace gp
+
+// ---- the damped step's seam: what the dense system (gp_solver.hip) and the block-sparse one (gp_sparse.hip) are to a caller that steps them (gp_lm.hip) -----------
+namespace gp {
+
+// buildDampedSystem's four scalars (levenberg_marquardt_ext.cpp:146-161): A + lambda I, or A + lambda clamp(diag A, min_diag, max_diag) with `diagonal`
+struct Damping {
+  double lambda;
+  int diagonal;
+  double min_diag, max_diag;
+};
+
+// gp_*_system_step in ONE synchronisation: the step's last kernels leave x [n] | b [n] | c | status in a pinned block that the host reads behind the stream.  A step in
+// flight owns that block and the system's device buffers until finish_step / collect_step: a second issue is refused, not queued over it.  `api` names the entry
+// points in the messages ("gp_dense_system", "gp_sparse_system").
+struct StepHandoff {
+  PinnedArray pinned;
+  bool in_flight = false;  // issue_step went out, finish_step / collect_step has not collected it
+
+  // in front of an issue: the block for n unknowns, or the refusal while a step is in flight
+  int begin(const char* api, size_t n) {
+    if (in_flight) return fail(GP_ERROR_INVALID_ARGUMENT, std::string(api) + "_issue_step: a step is in flight (finish it first)");
+    return pinned.ensure(sizeof(double) * (2 * n + 2));
+  }
+  double* host() { return pinned.as<double>(); }
+
+  // finish_step (wait = true) / collect_step (the caller has SEEN the stream pass the step): b and c handed over also when the system is indeterminate, x only when not
+  int finish(const char* api, hipStream_t stream, size_t n, bool wait, double* x_host, double* b_host, double* c_host) {
+    if (!in_flight) return fail(GP_ERROR_INVALID_ARGUMENT, std::string(api) + "_finish_step: no step was issued");
+    const double* h = pinned.as<double>();
+    in_flight = false;
+    if (wait) GP_HIP(hipStreamSynchronize(stream));
+    if (b_host) memcpy(b_host, h + n, sizeof(double) * n);
+    if (c_host) *c_host = h[2 * n];
+    if (h[2 * n + 1] != 0.0) return fail(GP_ERROR_INDETERMINATE, std::string(api) + "_step: the system is not positive definite (indeterminate linear system)");
+    if (x_host) memcpy(x_host, h, sizeof(double) * n);
+    return GP_OK;
+  }
+};
+
+struct LmPoseView;  // gp_lm_poses.hpp
+
+// gp_dense_system and gp_sparse_system derive from this; the graph of gp_lm.hip owns one through it and never asks which
+struct DampedSystem {
+  const char* const api;  // "gp_dense_system" / "gp_sparse_system", for the messages
+  int n = 0, num_factors = 0;
+  hipStream_t stream = nullptr;
+  StepHandoff step;  // x [n] | b [n] | c | status, written by the step's last kernel
+  bool built = false;
+  explicit DampedSystem(const char* api_name) : api(api_name) {}
+  virtual ~DampedSystem() = default;
+  // the step's device work, queued on the system's stream (nothing waits here).  epi: the LM trial's retract (gp_lm_poses.hpp), run as the step's epilogue where the step
+  // is one launch -- *fused (may be null) says whether it was; else the caller launches lm_poses_kernel behind the step itself
+  virtual int issue_step(const gp_linearized6* records_dev, const Damping& damping, const double* prior_diag_host, const LmPoseView* epi, bool* fused) = 0;
+  virtual int set_one_launch(int enable) = 0;  // as gp_*_system_set_one_launch
+  // where an issued step leaves x (slot order) and its status word on the device
+  virtual void device_solution(const double** x_dev, const int** status_dev) = 0;
+  // finish_step (wait) / collect_step (the caller has SEEN the stream pass the step: no wait of its own)
+  int finish(bool wait, double* x_host, double* b_host, double* c_host) { return step.finish(api, stream, (size_t)n, wait, x_host, b_host, c_host); }
+};
+DampedSystem* as_damped_system(gp_dense_system_t* s);   // gp_solver.hip
+DampedSystem* as_damped_system(gp_sparse_system_t* s);  // gp_sparse.hip
+
+}  // namespace gp
+
+// the six step entry points of gp_<prefix>_*, the same for both systems (T derives from gp::DampedSystem)
+#define GP_DAMPED_SYSTEM_STEP_API(prefix, T)                                                                                                                              \
+  int prefix##_issue_step(T* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal, const double* prior) {  \
+    if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, #prefix "_step: null system");                                                                                    \
+    return s->issue_step(records_dev, gp::Damping{lambda, diagonal_damping, min_diagonal, max_diagonal}, prior, nullptr, nullptr);                                        \
+  }                                                                                                                                                                       \
+  int prefix##_finish_step(T* s, double* x, double* b, double* c) { return s ? s->finish(true, x, b, c) : gp::fail(GP_ERROR_INVALID_ARGUMENT, #prefix "_finish_step: no step was issued"); }  \
+  int prefix##_collect_step(T* s, double* x, double* b, double* c) { return s ? s->finish(false, x, b, c) : gp::fail(GP_ERROR_INVALID_ARGUMENT, #prefix "_finish_step: no step was issued"); } \
+  int prefix##_step(T* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal, const double* prior, double* x, double* b,       \
+                    double* c) {                                                                                                                                          \
+    GP_TRY(prefix##_issue_step(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior));                                                             \
+    return s->finish(true, x, b, c);                                                                                                                                      \
+  }                                                                                                                                                                       \
+  int prefix##_set_one_launch(T* s, int enable) { return s ? s->set_one_launch(enable) : 0; }                                                                             \
+  int prefix##_device_solution(T* s, const double** x_dev, const int** status_dev) {                                                                                      \
+    if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, #prefix "_device_solution: null system");                                                                          \
+    s->device_solution(x_dev, status_dev);                                                                                                                                \
+    return GP_OK;                                                                                                                                                         \
+  }
 
 // the correspondence-factor batch as the LM graph drives it (gp_corr_batch.hip; gp_lm.hip): the error evaluation in two halves, like gp_vgicp_batch_issue_compute_error_dev_begin / _end
 struct gp_corr_batch;

@@ -116,11 +116,4 @@ __device__ __forceinline__ void lm_poses_thread(const LmPoseView& v, const int i
   }
 }
 
-// the damped step with the retract as its epilogue (gp_sparse.hip + gp_sparse_small.hip / gp_solver.hip): as gp_*_system_issue_step; *fused = the step ran as one launch and the epilogue
-// with it (else the caller launches lm_poses_kernel behind the step itself)
-int sparse_issue_step_with_poses(gp_sparse_system_t* sys, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                                 const LmPoseView& poses, bool* fused);
-int dense_issue_step_with_poses(gp_dense_system_t* sys, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                                const LmPoseView& poses, bool* fused);
-
 }  // namespace gp

@@ -281,16 +281,25 @@ __global__ void __launch_bounds__(64) dense_one_pose_step_kernel(const BlockDest
 
 constexpr int kMaxSlots = 2048;  // 12288 unknowns: 96 KB of LDS for the substitution vector, 1.2 GB for the dense matrix
 
-struct gp_dense_system {
-  int num_slots = 0, num_factors = 0, n = 0;
-  hipStream_t stream = nullptr;
+struct gp_dense_system : gp::DampedSystem {
+  gp_dense_system() : gp::DampedSystem("gp_dense_system") {}
+  int num_slots = 0;
   std::vector<gp::BlockDest> dests;
   std::vector<gp::Contribution> contribs;
   gp::DeviceArray d_dests, d_contribs, A, b, c, x, status, prior, Ldiag, diag0;  // diag0 [n]: the damped assembled diagonal (the pivots' scale)
-  gp::StepHandoff step;  // gp_dense_system_step: x [n] | b [n] | c | status, written by the step's last kernel
-  bool built = false;
   bool one_launch = true;       // a system of ONE pose runs its step as one launch (dense_one_pose_step_kernel); gp_dense_system_set_one_launch(sys, 0): the multi-launch form
+  int issue_step(const gp_linearized6* records_dev, const gp::Damping& damping, const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) override;
+  // 0: a one-pose system's step takes the multi-launch path too (the bit-identity test, A/B timing); returns what the next step of this system runs (1: one launch)
+  int set_one_launch(int enable) override {
+    one_launch = enable != 0;
+    return (one_launch && num_slots == 1) ? 1 : 0;
+  }
+  void device_solution(const double** x_dev, const int** status_dev) override {
+    if (x_dev) *x_dev = x.as<double>();
+    if (status_dev) *status_dev = status.as<int>();
+  }
 };
+gp::DampedSystem* gp::as_damped_system(gp_dense_system_t* s) { return s; }
 
 extern "C" {
 
@@ -427,72 +436,32 @@ int gp_dense_system_solve(gp_dense_system_t* s, double* x_host, double* x_dev_ou
 // without the waits and copies between them; x, b, c and the status arrive through one pinned block written by the last kernel.  Bit-identical to the three calls.
 // b_host / c_host are valid also when the system is indeterminate.
 // the step's device work, queued on the system's stream (a prior diagonal is uploaded by gp_dense_system_build: its own synchronisation)
-static int issue_step_impl(gp_dense_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                           const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) {
+int gp_dense_system::issue_step(const gp_linearized6* records_dev, const gp::Damping& d, const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) {
   if (fused) *fused = false;
-  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: null system");
-  GP_TRY(s->step.begin("gp_dense_system", (size_t)s->n));
-  if (s->num_slots == 1 && !prior_diag_host && s->one_launch) {
-    if ((!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: bad arguments");
-    hipLaunchKernelGGL(gp::dense_one_pose_step_kernel, dim3(1), dim3(64), 0, s->stream, s->d_dests.as<gp::BlockDest>(), s->d_contribs.as<gp::Contribution>(),
-                       reinterpret_cast<const double*>(records_dev), s->num_factors, lambda, diagonal_damping, min_diagonal, max_diagonal, s->A.as<double>(), s->b.as<double>(),
-                       s->c.as<double>(), s->x.as<double>(), s->Ldiag.as<double>(), s->status.as<int>(), s->step.host(), epi ? *epi : gp::LmPoseView{}, epi ? 1 : 0);
+  GP_TRY(step.begin(api, (size_t)n));
+  if (num_slots == 1 && !prior_diag_host && one_launch) {
+    if ((!records_dev && num_factors > 0) || !(d.lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_step: bad arguments");
+    hipLaunchKernelGGL(gp::dense_one_pose_step_kernel, dim3(1), dim3(64), 0, stream, d_dests.as<gp::BlockDest>(), d_contribs.as<gp::Contribution>(),
+                       reinterpret_cast<const double*>(records_dev), num_factors, d.lambda, d.diagonal, d.min_diag, d.max_diag, A.as<double>(), b.as<double>(),
+                       c.as<double>(), x.as<double>(), Ldiag.as<double>(), status.as<int>(), step.host(), epi ? *epi : gp::LmPoseView{}, epi ? 1 : 0);
     if (fused) *fused = epi != nullptr;
     GP_HIP(hipGetLastError());
-    s->built = false;
-    s->step.in_flight = true;
+    built = false;
+    step.in_flight = true;
     return GP_OK;
   }
-  GP_TRY(gp_dense_system_build(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host));
-  GP_TRY(launch_dense_solve(s));
-  hipLaunchKernelGGL(gp::dense_step_end_kernel, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, (const double*)s->x.as<double>(), (const double*)s->b.as<double>(),
-                     (const double*)s->c.as<double>(), (const int*)s->status.as<int>(), s->n, s->step.host());
+  GP_TRY(gp_dense_system_build(this, records_dev, d.lambda, d.diagonal, d.min_diag, d.max_diag, prior_diag_host));
+  GP_TRY(launch_dense_solve(this));
+  hipLaunchKernelGGL(gp::dense_step_end_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const double*)x.as<double>(), (const double*)b.as<double>(),
+                     (const double*)c.as<double>(), (const int*)status.as<int>(), n, step.host());
   GP_HIP(hipGetLastError());
-  s->built = false;
-  s->step.in_flight = true;
+  built = false;
+  step.in_flight = true;
   return GP_OK;
 }
 
-int gp_dense_system_issue_step(gp_dense_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                               const double* prior_diag_host) {
-  return issue_step_impl(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host, nullptr, nullptr);
-}
-
-static int finish_step(gp_dense_system_t* s, double* x_host, double* b_host, double* c_host, bool wait) {
-  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_finish_step: no step was issued");
-  return s->step.finish("gp_dense_system", s->stream, (size_t)s->n, wait, x_host, b_host, c_host);
-}
-
-int gp_dense_system_finish_step(gp_dense_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, true); }
-// ... for a caller that has SEEN the stream pass the step (a completion word of work it queued behind the step on the same stream): no wait of its own
-int gp_dense_system_collect_step(gp_dense_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, false); }
-
-int gp_dense_system_step(gp_dense_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                         const double* prior_diag_host, double* x_host, double* b_host, double* c_host) {
-  GP_TRY(gp_dense_system_issue_step(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host));
-  return gp_dense_system_finish_step(s, x_host, b_host, c_host);
-}
-
-// 0: a one-pose system's step takes the multi-launch path too (the bit-identity test, A/B timing); returns what the next step of this system runs (1: one launch)
-int gp_dense_system_set_one_launch(gp_dense_system_t* s, int enable) {
-  if (!s) return 0;
-  s->one_launch = enable != 0;
-  return (s->one_launch && s->num_slots == 1) ? 1 : 0;
-}
-
-// gp_sparse_system_device_solution's dense form
-int gp_dense_system_device_solution(gp_dense_system_t* s, const double** x_dev, const int** status_dev) {
-  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_dense_system_device_solution: null system");
-  if (x_dev) *x_dev = s->x.as<double>();
-  if (status_dev) *status_dev = s->status.as<int>();
-  return GP_OK;
-}
+// gp_dense_system_issue_step / _finish_step / _collect_step (for a caller that has SEEN the stream pass the step: no wait of its own) / _step / _set_one_launch /
+// _device_solution
+GP_DAMPED_SYSTEM_STEP_API(gp_dense_system, gp_dense_system_t)
 
 }  // extern "C"
-
-namespace gp {
-int dense_issue_step_with_poses(gp_dense_system_t* sys, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                                const LmPoseView& poses, bool* fused) {
-  return issue_step_impl(sys, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, nullptr, &poses, fused);
-}
-}  // namespace gp

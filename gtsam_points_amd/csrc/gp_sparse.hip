@@ -50,24 +50,38 @@ static std::vector<int> pack_int_arrays(std::initializer_list<const std::vector<
 }
 }  // namespace gp
 
-struct gp_sparse_system {
+struct gp_sparse_system : gp::DampedSystem {
+  gp_sparse_system() : gp::DampedSystem("gp_sparse_system") {}
   gp::SparseSymbolic sym;
-  int num_factors = 0, n = 0;
-  hipStream_t stream = nullptr;
   std::vector<gp::SparseDest> dests;
   std::vector<gp::Contribution> contribs;
   gp::DeviceArray d_dests, d_contribs, d_int, L, y, x, x_slots, c, status, prior, dinv, diag0;
-  gp::StepHandoff step;  // gp_sparse_system_step: x [n] | b [n] | c | status, written by the step's kernels, read by the host behind ONE synchronisation
   gp::SparseView view{};
   const int* d_perm = nullptr;
-  bool built = false;
   // the one-launch step of small graphs (sparse_small_step_kernel): eligible when factor + index lists fit one compute unit's LDS
   bool small_ok = false, one_launch = false;
   std::vector<double> prior_staged;  // the permuted prior diagonal of the step in flight (source of its H2D copy)
   size_t small_lds_bytes = 0;
   gp::DeviceArray d_small_arena, d_level_ptr;
   gp::SparseSmallView small{};
+  int issue_step(const gp_linearized6* records_dev, const gp::Damping& damping, const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) override;
+  // the one-launch step (sparse_small_step_kernel): 1 = gp_sparse_system_step uses it when the system qualifies (default), 0 = the multi-launch form; returns what the
+  // next step will run.  The two are bit-identical; the switch exists for the test that says so and for A/B timing.  So do 2 and 3, which select the one-launch step's
+  // other forms (gp::SmallForm): 2 = LockStep, 3 = LoneWaves.
+  int set_one_launch(int enable) override {
+    one_launch = enable != 0 && small_ok;
+    small.form = enable == 2 ? gp::SmallForm::LockStep : enable == 3 ? gp::SmallForm::LoneWaves : gp::SmallForm::Teams;
+    if (!one_launch) return 0;
+    return enable == 2 || enable == 3 ? enable : 1;
+  }
+  // x in slot order and the status word (!= 0: indeterminate, x is not to be used) -- for a consumer queued behind the step on the same stream (the device-side
+  // retract of gp_lm.hip)
+  void device_solution(const double** x_slots_dev, const int** status_dev) override {
+    if (x_slots_dev) *x_slots_dev = x_slots.as<double>();
+    if (status_dev) *status_dev = status.as<int>();
+  }
 };
+gp::DampedSystem* gp::as_damped_system(gp_sparse_system_t* s) { return s; }
 
 extern "C" {
 
@@ -157,17 +171,6 @@ int gp_debug_sparse_step_trace(gp_sparse_system_t* s, unsigned long long* dev_bu
   if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_debug_sparse_step_trace: null");
   s->small.trace = dev_buffer;
   return GP_OK;
-}
-
-// the one-launch step (sparse_small_step_kernel): 1 = gp_sparse_system_step uses it when the system qualifies (default), 0 = the multi-launch form; returns what the
-// next step will run.  The two are bit-identical; the switch exists for the test that says so and for A/B timing.  So do 2 and 3, which select the one-launch step's
-// other forms (gp::SmallForm): 2 = LockStep, 3 = LoneWaves.
-int gp_sparse_system_set_one_launch(gp_sparse_system_t* s, int enable) {
-  if (!s) return 0;
-  s->one_launch = enable != 0 && s->small_ok;
-  s->small.form = enable == 2 ? gp::SmallForm::LockStep : enable == 3 ? gp::SmallForm::LoneWaves : gp::SmallForm::Teams;
-  if (!s->one_launch) return 0;
-  return enable == 2 || enable == 3 ? enable : 1;
 }
 
 int gp_sparse_system_destroy(gp_sparse_system_t* s) {
@@ -304,81 +307,47 @@ int gp_sparse_system_solve(gp_sparse_system_t* s, double* x_host, double* x_dev_
 // the assembly (damping applied as the diagonal is written; b, c stored where the host reads them; status cleared), the levels, x (slot order) + status to the host.
 // Bit-identical to the three calls.  b_host / c_host are valid also when the system turns out indeterminate (the optimizer raises lambda and tries again).
 // the step's device work, queued on the system's stream: nothing waits here
-static int issue_step_impl(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                           const double* prior_diag_host, const gp::LmPoseView* epi) {
-  if (!s || (!records_dev && s->num_factors > 0) || !(lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_step: bad arguments");
+int gp_sparse_system::issue_step(const gp_linearized6* records_dev, const gp::Damping& damping, const double* prior_diag_host, const gp::LmPoseView* epi, bool* fused) {
+  if (fused) *fused = epi && one_launch;
+  if ((!records_dev && num_factors > 0) || !(damping.lambda >= 0.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_step: bad arguments");
   // (a step in flight also owns prior_staged, the source of its pending H2D copy)
-  GP_TRY(s->step.begin("gp_sparse_system", (size_t)s->n));
-  const gp::SparseSymbolic& S = s->sym;
-  const size_t n = (size_t)s->n;
-  double* h = s->step.host();
+  GP_TRY(step.begin(api, (size_t)this->n));
+  const gp::SparseSymbolic& S = sym;
+  const size_t n = (size_t)this->n;
+  double* h = step.host();
   gp::SparseStepExtras ex{};
-  ex.lambda = lambda, ex.min_diag = min_diagonal, ex.max_diag = max_diagonal, ex.diagonal = diagonal_damping;
+  ex.lambda = damping.lambda, ex.min_diag = damping.min_diag, ex.max_diag = damping.max_diag, ex.diagonal = damping.diagonal;
   if (prior_diag_host) {
-    GP_TRY(upload_prior(s, prior_diag_host, &s->prior_staged));
-    ex.prior_diag = s->prior.as<double>();
+    GP_TRY(upload_prior(this, prior_diag_host, &prior_staged));
+    ex.prior_diag = prior.as<double>();
   }
-  ex.perm = s->d_perm, ex.b_slots_host = h + n, ex.c_dev = s->c.as<double>(), ex.c_host = h + 2 * n, ex.status = s->status.as<int>();
-  ex.num_factors = s->num_factors, ex.num_dests = (int)s->dests.size();
-  ex.diag0 = s->diag0.as<double>();
-  hipLaunchKernelGGL(gp::sparse_assemble_kernel<true>, dim3((unsigned)s->dests.size() + 1), dim3(64), 0, s->stream, s->d_dests.as<gp::SparseDest>(),
-                     s->d_contribs.as<gp::Contribution>(), reinterpret_cast<const double*>(records_dev), s->L.as<double>(), s->y.as<double>(), ex);
-  if (s->one_launch) {
+  ex.perm = d_perm, ex.b_slots_host = h + n, ex.c_dev = c.as<double>(), ex.c_host = h + 2 * n, ex.status = status.as<int>();
+  ex.num_factors = num_factors, ex.num_dests = (int)dests.size();
+  ex.diag0 = diag0.as<double>();
+  hipLaunchKernelGGL(gp::sparse_assemble_kernel<true>, dim3((unsigned)dests.size() + 1), dim3(64), 0, stream, d_dests.as<gp::SparseDest>(),
+                     d_contribs.as<gp::Contribution>(), reinterpret_cast<const double*>(records_dev), L.as<double>(), y.as<double>(), ex);
+  if (one_launch) {
     // small graph: the assembly as it is (one workgroup per block of L across the chip: a gather of 8-byte values, which ONE compute unit's vector memory path takes
     // 40 us for), then factorisation and both substitutions in ONE launch with every operand in the LDS of one compute unit (sparse_small_step_kernel)
-    gp::SparseSmallView V = s->small;
+    gp::SparseSmallView V = small;
     V.x_slots_host = h;
     V.status_host = h + 2 * n + 1;
     V.has_epi = epi ? 1 : 0;
     if (epi) V.epi = *epi;
-    gp::launch_small_step(V, s->small_lds_bytes, s->stream, s->status.as<int>());
+    gp::launch_small_step(V, small_lds_bytes, stream, status.as<int>());
   } else {
-    launch_factor_and_substitutions(s);
-    hipLaunchKernelGGL(gp::sparse_step_end_kernel, dim3((s->n + 255) / 256), dim3(256), 0, s->stream, (const double*)s->x.as<double>(), s->d_perm, S.P, s->x_slots.as<double>(), h,
-                       (const int*)s->status.as<int>(), h + 2 * n + 1);
+    launch_factor_and_substitutions(this);
+    hipLaunchKernelGGL(gp::sparse_step_end_kernel, dim3((this->n + 255) / 256), dim3(256), 0, stream, (const double*)x.as<double>(), d_perm, S.P, x_slots.as<double>(), h,
+                       (const int*)status.as<int>(), h + 2 * n + 1);
   }
   GP_HIP(hipGetLastError());
-  s->built = false;
-  s->step.in_flight = true;
+  built = false;
+  step.in_flight = true;
   return GP_OK;
 }
 
-int gp_sparse_system_issue_step(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                                const double* prior_diag_host) {
-  return issue_step_impl(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host, nullptr);
-}
-
-// waits for the stream and hands over what the step's kernels left in the pinned buffer
-static int finish_step(gp_sparse_system_t* s, double* x_host, double* b_host, double* c_host, bool wait) {
-  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_finish_step: no step was issued");
-  return s->step.finish("gp_sparse_system", s->stream, (size_t)s->n, wait, x_host, b_host, c_host);
-}
-
-int gp_sparse_system_finish_step(gp_sparse_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, true); }
-// ... for a caller that has SEEN the stream pass the step (a completion word of work it queued behind the step on the same stream): no wait of its own
-int gp_sparse_system_collect_step(gp_sparse_system_t* s, double* x_host, double* b_host, double* c_host) { return finish_step(s, x_host, b_host, c_host, false); }
-
-int gp_sparse_system_step(gp_sparse_system_t* s, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                          const double* prior_diag_host, double* x_host, double* b_host, double* c_host) {
-  GP_TRY(gp_sparse_system_issue_step(s, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, prior_diag_host));
-  return gp_sparse_system_finish_step(s, x_host, b_host, c_host);
-}
-
-// where an issued step leaves its result ON THE DEVICE: x in slot order and the status word (!= 0: indeterminate, x is not to be used) -- for a consumer queued
-// behind the step on the same stream (the device-side retract of gp_lm.hip)
-int gp_sparse_system_device_solution(gp_sparse_system_t* s, const double** x_slots_dev, const int** status_dev) {
-  if (!s) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_sparse_system_device_solution: null system");
-  if (x_slots_dev) *x_slots_dev = s->x_slots.as<double>();
-  if (status_dev) *status_dev = s->status.as<int>();
-  return GP_OK;
-}
+// gp_sparse_system_issue_step / _finish_step (waits for the stream and hands over what the step's kernels left in the pinned buffer) / _collect_step (for a caller
+// that has SEEN the stream pass the step: no wait of its own) / _step / _set_one_launch / _device_solution
+GP_DAMPED_SYSTEM_STEP_API(gp_sparse_system, gp_sparse_system_t)
 
 }  // extern "C"
-
-namespace gp {
-int sparse_issue_step_with_poses(gp_sparse_system_t* sys, const gp_linearized6* records_dev, double lambda, int diagonal_damping, double min_diagonal, double max_diagonal,
-                                 const LmPoseView& poses, bool* fused) {
-  *fused = sys && sys->one_launch;
-  return issue_step_impl(sys, records_dev, lambda, diagonal_damping, min_diagonal, max_diagonal, nullptr, *fused ? &poses : nullptr);
-}
-}  // namespace gp

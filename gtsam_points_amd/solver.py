@@ -350,24 +350,14 @@ class LevenbergMarquardtGraphGPU:
             _capi.check(self._lib.gp_vgicp_batch_create(arr, F, stream, C.byref(self._batch)), "gp_vgicp_batch_create")
         else:
             self._batch = None
-        try:
-            if self.corr_factors:
-                _capi.check(self._lib.gp_lm_graph_create_with_factors(self._batch, self.pairs.ctypes.data, self._corr._h, self.corr_pairs.ctypes.data,
-                                                                     _pose_factor_array(self.pose_factors) if self.pose_factors else None, len(self.pose_factors),
-                                                                     self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
-                            "gp_lm_graph_create_with_factors")
-            elif self.pose_factors:
-                _capi.check(self._lib.gp_lm_graph_create_with_pose_factors(self._batch, self.pairs.ctypes.data, _pose_factor_array(self.pose_factors), len(self.pose_factors),
-                                                                          self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
-                            "gp_lm_graph_create_with_pose_factors")
-            else:
-                _capi.check(self._lib.gp_lm_graph_create(self._batch, self.pairs.ctypes.data, self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], C.byref(self._h)), "gp_lm_graph_create")
+        try:  # (one create for every mix: it takes a null correspondence batch and zero pose factors)
+            _capi.check(self._lib.gp_lm_graph_create_with_factors(self._batch, self.pairs.ctypes.data, self._corr._h if self._corr is not None else None,
+                                                                 self.corr_pairs.ctypes.data if self._corr is not None else None,
+                                                                 _pose_factor_array(self.pose_factors) if self.pose_factors else None, len(self.pose_factors),
+                                                                 self.num_poses, held.ctypes.data, SparseLinearSystemGPU.ORDERINGS[ordering], stream, C.byref(self._h)),
+                        "gp_lm_graph_create_with_factors")
         except Exception:
-            if self._batch:
-                self._lib.gp_vgicp_batch_destroy(self._batch)
-            self._batch = None
-            if self._corr is not None:
-                self._corr.close()
+            self.close()
             raise
         self.n = self._lib.gp_lm_graph_num_variables(self._h)
         self._x, self._b, self._c, self._e = np.zeros(self.n), np.zeros(self.n), np.zeros(1), np.zeros(1)
