@@ -256,12 +256,12 @@ struct PinnedArray {
   PinnedArray(const PinnedArray&) = delete;
   PinnedArray& operator=(const PinnedArray&) = delete;
   ~PinnedArray() { release(); }
-  int ensure(size_t n) {
+  int ensure(size_t n, unsigned flags = hipHostMallocDefault) {
     if (n <= bytes && ptr) return GP_OK;
     release();
     if (n == 0) n = 16;
     n += n / 5;
-    hipError_t e = hipHostMalloc(&ptr, n, hipHostMallocDefault);
+    hipError_t e = hipHostMalloc(&ptr, n, flags);
     if (e != hipSuccess) {
       ptr = nullptr;
       return hip_fail(e, "hipHostMalloc", __FILE__, __LINE__);

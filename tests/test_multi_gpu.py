@@ -70,6 +70,44 @@ def test_sharded_batch_equals_plain_batch(gpu, kitti07):
     assert np.array_equal(rr.linearize(deltas), ref) and np.array_equal(rr.compute_error(deltas, deltas2), ref_err)
 
 
+def test_plans_with_a_hole_and_with_mixed_shards_equal_plain_batch(gpu, kitti07):
+    """two shapes of plan the partition never deals, without a collective: a shard without factors between two that have some, and a contiguous shard beside two
+    interleaved ones (records stored straight into the host stack by the one, copied out row by row by the others) -- bit-equal to the plain batch"""
+    from gtsam_points_amd.distributed import MultiDeviceBatch
+
+    _, _, factors, deltas, deltas2 = _graph(gpu, kitti07)
+    ref, ref_err = _plain_batch(gpu, factors, deltas, deltas2)
+    hole = MultiDeviceBatch(factors, shard_of=[0] * 5 + [2] * 5, num_shards=3, use_rccl=0)
+    assert hole.num_shards == 3 and not hole.uses_rccl
+    assert [hole.shard_info(k)["num_factors"] for k in range(3)] == [5, 0, 5] and hole.shard_info(1)["num_points"] == 0
+    assert np.array_equal(hole.linearize(deltas), ref) and np.array_equal(hole.compute_error(deltas, deltas2), ref_err)
+    mixed = MultiDeviceBatch(factors, shard_of=[0, 0, 0, 1, 2, 1, 2, 1, 2, 1], num_shards=3, use_rccl=0)
+    assert [mixed.shard_info(k)["num_factors"] for k in range(3)] == [3, 4, 3]
+    assert np.array_equal(mixed.linearize(deltas), ref) and np.array_equal(mixed.compute_error(deltas, deltas2), ref_err)
+
+
+def test_refused_plans_leave_nothing_behind(gpu, kitti07):
+    """every refusal of gp_vgicp_multi_batch_create -- before anything is allocated, after the shards exist, and by the argument check -- says why, and a good batch
+    created straight after it linearises bit-equal to the plain batch"""
+    from gtsam_points_amd.distributed import MultiDeviceBatch
+
+    _, _, factors, deltas, deltas2 = _graph(gpu, kitti07)
+    ref, ref_err = _plain_batch(gpu, factors, deltas, deltas2)
+    halves = [0] * 5 + [1] * 5
+    refusals = [
+        (dict(shard_of=[0] * 9 + [2], num_shards=2, use_rccl=0), "gp_vgicp_multi_batch_create: shard index out of range"),
+        (dict(shard_of=halves, num_shards=2, use_rccl=1), "gp_vgicp_multi_batch_create: RCCL needs one shard per device"),
+        (dict(shard_of=halves, num_shards=0, use_rccl=0), "gp_vgicp_multi_batch_create: num_shards must be positive with an explicit assignment"),
+    ]
+    for kwargs, message in refusals:
+        with pytest.raises(gpu._capi.GPError) as e:
+            MultiDeviceBatch(factors, **kwargs)
+        assert str(e.value).endswith("(code 1): " + message), str(e.value)
+        good = MultiDeviceBatch(factors, shard_of=halves, num_shards=2, use_rccl=0)
+        assert np.array_equal(good.linearize(deltas), ref) and np.array_equal(good.compute_error(deltas, deltas2), ref_err)
+        del good
+
+
 def test_rccl_allreduce_path(gpu, kitti07):
     """the ncclAllReduce exchange over the zeroed [F x 122] stack: one shard per visible device (a single GPU is a valid 1-rank
     communicator).  With several devices the factor list is split with gp_shard_plan, clouds and maps are replicated onto the
