@@ -219,6 +219,23 @@ _SIGNATURES = {
     "gp_colored_gicp_factor_set_max_correspondence_distance": (C.c_int, [C.c_void_p, C.c_double]),
     "gp_colored_gicp_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
     "gp_colored_gicp_factor_num_correspondences": (C.c_int, [C.c_void_p]),
+    "gp_colored_gicp_factor_set_intensity_grid": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # IntensityKdTree: exact 1-NN in (x, y, z, intensity) (gp_intensity_search.hip)
+    "gp_intensity_grid_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_intensity_grid_destroy": (C.c_int, [C.c_void_p]),
+    "gp_intensity_grid_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gp_intensity_grid_point_grid": (C.c_void_p, [C.c_void_p]),
+    # IntegratedColorConsistencyFactor_ on a borrowed gp_point_grid or gp_intensity_grid (gp_color_consistency.hip)
+    "gp_color_consistency_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_double,
+                                                     C.c_void_p, C.POINTER(C.c_void_p)]),
+    "gp_color_consistency_factor_destroy": (C.c_int, [C.c_void_p]),
+    "gp_color_consistency_factor_set_intensity_grid": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "gp_color_consistency_factor_linearize": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(Linearized6)]),
+    "gp_color_consistency_factor_compute_error": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "gp_color_consistency_factor_set_photometric_term_weight": (C.c_int, [C.c_void_p, C.c_double]),
+    "gp_color_consistency_factor_set_max_correspondence_distance": (C.c_int, [C.c_void_p, C.c_double]),
+    "gp_color_consistency_factor_set_correspondence_update_tolerance": (C.c_int, [C.c_void_p, C.c_double, C.c_double]),
+    "gp_color_consistency_factor_num_correspondences": (C.c_int, [C.c_void_p]),
     # IntegratedCT_ICPFactor_ / IntegratedCT_GICPFactor_ on a borrowed gp_point_grid (gp_ct_factors.hip)
     "gp_ct_factor_create": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p,
                                       C.POINTER(C.c_void_p)]),

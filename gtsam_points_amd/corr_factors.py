@@ -19,7 +19,7 @@ import numpy as np
 
 from . import _capi
 from .factors import HessianFactor, LinearizedSystem6, pose_inverse
-from .features import KdTreeGPU, estimate_intensity_gradients_gpu
+from .features import IntensityKdTreeGPU, KdTreeGPU, estimate_intensity_gradients_gpu
 from .types import GaussianVoxelMapGPU, PointCloudGPU, _pose16
 
 
@@ -48,7 +48,19 @@ class _CorrFactorGPU:
         tree = tree if tree is not None else KdTreeGPU(target, stream=stream)
         if tree.frame.points_gpu is None or tree.frame.points_gpu.data_ptr() != target.points_gpu.data_ptr():
             raise _capi.GPError("error: target_tree was not built over the target frame's points")
+        if isinstance(tree, IntensityKdTreeGPU) and (target.intensities_gpu is None or tree._intensities_ptr != target.intensities_gpu.data_ptr()):
+            raise _capi.GPError("error: target_tree was not built over the target frame's points and intensities")
         return tree
+
+    def _photometric_tree(self, target, tree, stream):
+        """_shared_tree for the factors that may search in XYZI: a KdTreeGPU (the 3-D search -- what the reference does when handed a plain KdTree, which ignores
+        pt[3]) or an IntensityKdTreeGPU"""
+        if tree is not None and not isinstance(tree, (KdTreeGPU, IntensityKdTreeGPU)):
+            raise TypeError("target_tree must be a KdTreeGPU or an IntensityKdTreeGPU")
+        return self._shared_tree(target, tree, stream)
+
+    def _searches_xyzi(self):
+        return isinstance(getattr(self, "target_tree", None), IntensityKdTreeGPU)
 
     def __del__(self):
         if getattr(self, "_h", None):
@@ -179,8 +191,9 @@ class IntegratedColoredGICPFactorGPU(_RelativePoseFactorGPU):
     """Colored GICP matching-cost factor on the GPU (IntegratedColoredGICPFactor_, impl/integrated_colored_gicp_factor_impl.hpp): GICP's geometric term on the 1-NN
     correspondences within max_correspondence_distance (default 1 m, :28) weighted 1 - photometric_term_weight, plus the photometric residual
     I_B - I_A - (P g_B) . (mu_B - T p_A) in the target's tangent plane weighted photometric_term_weight (default 0.25, :29).
-    target_tree: a KdTreeGPU over `target` that many factors may share; None builds one.  target_gradients: an IntensityGradientsGPU of `target`; None estimates
-    it with k = 10.  The search is the 3-D one (the reference's optional 4-D IntensityKdTree is not provided)."""
+    target_tree: a KdTreeGPU over `target` that many factors may share (None builds one): the 3-D search; or an IntensityKdTreeGPU over it: the correspondences are
+    the nearest in (x, y, z, intensity) and max_correspondence_distance bounds the 4-D distance (:121-127).  target_gradients: an IntensityGradientsGPU of `target`;
+    None estimates it with k = 10."""
 
     _PREFIX = "gp_colored_gicp_factor"
 
@@ -192,7 +205,7 @@ class IntegratedColoredGICPFactorGPU(_RelativePoseFactorGPU):
         if source.points_gpu is None or source.covs_gpu is None or source.intensities_gpu is None:
             raise _capi.GPError("error: source frame doesn't have required attributes for colored_gicp")  # :42-45
         self.target, self.source = target, source
-        self.target_tree = self._shared_tree(target, target_tree, stream)
+        self.target_tree = self._photometric_tree(target, target_tree, stream)
         self.target_gradients = target_gradients if target_gradients is not None else estimate_intensity_gradients_gpu(target, 10, stream=stream)
         if self.target_gradients.size() != target.size():
             raise _capi.GPError("error: target_gradients does not have one gradient per target point")
@@ -207,6 +220,55 @@ class IntegratedColoredGICPFactorGPU(_RelativePoseFactorGPU):
             "gp_colored_gicp_factor_create",
         )
         self._adopt(h, stream)
+        if self._searches_xyzi():
+            self._call("set_intensity_grid", self.target_tree._xyzi)
+
+    def set_photometric_term_weight(self, weight):
+        self._call("set_photometric_term_weight", float(weight))
+
+    def set_max_correspondence_distance(self, dist):
+        self._call("set_max_correspondence_distance", float(dist))
+
+    def set_correspondence_update_tolerance(self, angle, trans):
+        """keep the stored correspondences while a linearisation pose stays within (angle [rad], trans [m]) of the pose they were searched at (:101-114)"""
+        self._call("set_correspondence_update_tolerance", float(angle), float(trans))
+
+
+class IntegratedColorConsistencyFactorGPU(_RelativePoseFactorGPU):
+    """Color consistency matching-cost factor on the GPU (IntegratedColorConsistencyFactor_, impl/integrated_color_consistency_factor_impl.hpp): the photometric
+    residual I_B - I_A - (P g_B) . (mu_B - T p_A) alone, weighted photometric_term_weight (default 1.0, :31), on the 1-NN correspondences within
+    max_correspondence_distance (default 1 m, :30).  No covariances are needed.  target_tree: a KdTreeGPU over `target` (None builds one) -- the 3-D search, what the
+    reference does when handed a plain KdTree -- or an IntensityKdTreeGPU: the nearest in (x, y, z, intensity), the cut-off on the 4-D distance.  target_gradients:
+    an IntensityGradientsGPU of `target`; None estimates it with k = 10.  Not a member of CorrespondenceFactorBatchGPU or the LM graph yet."""
+
+    _PREFIX = "gp_color_consistency_factor"
+
+    def __init__(self, target_key, source_key, target: PointCloudGPU, source: PointCloudGPU, target_tree=None, target_gradients=None, max_correspondence_distance=1.0,
+                 photometric_term_weight=1.0, stream=None, _fixed_target_pose=None):
+        self._init_keys(target_key, source_key, _fixed_target_pose)
+        # (the reference's texts say colored_gicp in this factor too, :37-45)
+        if target.points_gpu is None or target.normals_gpu is None or target.intensities_gpu is None:
+            raise _capi.GPError("error: target frame doesn't have required attributes for colored_gicp")
+        if source.points_gpu is None or source.intensities_gpu is None:
+            raise _capi.GPError("error: source frame doesn't have required attributes for colored_gicp")
+        self.target, self.source = target, source
+        self.target_tree = self._photometric_tree(target, target_tree, stream)
+        self.target_gradients = target_gradients if target_gradients is not None else estimate_intensity_gradients_gpu(target, 10, stream=stream)
+        if self.target_gradients.size() != target.size():
+            raise _capi.GPError("error: target_gradients does not have one gradient per target point")
+        GaussianVoxelMapGPU._sync_torch(target)
+        GaussianVoxelMapGPU._sync_torch(source)
+        h = C.c_void_p()
+        _capi.check(
+            self._lib.gp_color_consistency_factor_create(self.target_tree._h, target.ptr(target.points_gpu), target.ptr(target.normals_gpu), target.ptr(target.intensities_gpu),
+                                                         C.c_void_p(self.target_gradients.gradients_gpu.data_ptr()), target.size(), source.ptr(source.points_gpu),
+                                                         source.ptr(source.intensities_gpu), source.size(), float(max_correspondence_distance) ** 2,
+                                                         float(photometric_term_weight), stream, C.byref(h)),
+            "gp_color_consistency_factor_create",
+        )
+        self._adopt(h, stream)
+        if self._searches_xyzi():
+            self._call("set_intensity_grid", self.target_tree._xyzi)
 
     def set_photometric_term_weight(self, weight):
         self._call("set_photometric_term_weight", float(weight))
@@ -418,6 +480,13 @@ class CorrespondenceFactorBatchGPU:
     def __init__(self, factors, stream=None):
         self._lib = _capi.load()
         self.factors = list(factors)
+        # what the batch's one 3-D search launch and its term tables do not serve yet is refused, never searched in 3-D instead
+        for f in self.factors:
+            if isinstance(f, IntegratedColorConsistencyFactorGPU):
+                raise _capi.GPError("CorrespondenceFactorBatchGPU: an IntegratedColorConsistencyFactorGPU cannot join a batch or an LM graph yet")
+            if isinstance(f, IntegratedColoredGICPFactorGPU) and f._searches_xyzi():
+                raise _capi.GPError("CorrespondenceFactorBatchGPU: an IntegratedColoredGICPFactorGPU on an IntensityKdTreeGPU (XYZI search) cannot join a batch or an LM "
+                                    "graph yet: the batch searches in 3-D")
         gicp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedGICPFactorGPU)]
         icp = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedICPFactorGPU)]
         loam = [i for i, f in enumerate(self.factors) if isinstance(f, IntegratedLOAMFactorGPU)]

@@ -137,6 +137,10 @@ int gp_colored_gicp_factor_create(const gp_point_grid_t* grid, const float* targ
 
 int gp_colored_gicp_factor_destroy(gp_colored_gicp_factor_t* f) { return gp_corr_destroy(f); }  // (the grid is the caller's)
 
+int gp_colored_gicp_factor_set_intensity_grid(gp_colored_gicp_factor_t* f, const gp_intensity_grid_t* xyzi) {
+  return gp_corr_set_intensity_grid(f, xyzi, f ? f->term.intensities : nullptr, "gp_colored_gicp_factor_set_intensity_grid");
+}
+
 int gp_colored_gicp_factor_set_photometric_term_weight(gp_colored_gicp_factor_t* f, double weight) {
   if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_set_photometric_term_weight: null");
   if (!(weight >= 0.0 && weight <= 1.0)) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_colored_gicp_factor_set_photometric_term_weight: weight outside [0, 1]");

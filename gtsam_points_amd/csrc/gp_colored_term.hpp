@@ -139,13 +139,65 @@ struct ColoredGicpTerm {
   }
 };
 
+// The per-point body of IntegratedColorConsistencyFactor_::evaluate (integrated_color_consistency_factor_impl.hpp:176-222) in the project's signs: the colored term's
+// photometric part alone,
+//   q = T p_A, d = mu_B - q, u = (I - n_B n_B^T) g_B (:207-215), r_p = I_B - I_A - u . d (:195-198: I_B + g_B . (projected - mu_B) - I_A, projected - mu_B = -P d),
+//   w = photometric_term_weight (default 1.0, :31): error = w r_p^2 (:200), M = w u u^T (:217-219), the vector handed to accumulate_sums_mw is -w r_p u (:220-221).
+// That is ColoredGicpTerm at w_g = 0 without the Mahalanobis matrix: no covariance is read and nothing is inverted.  A matched point costs 60 B: 4 (index) + 12 + 4
+// (source point, intensity) + 12 + 12 + 4 + 12 (target point, normal, intensity, gradient).
+struct ColorConsistencyTerm {
+  const float* points;
+  const float* intensities;
+  const float* target_points;
+  const float* target_normals;
+  const float* target_intensities;
+  const float* target_gradients;
+  double photometric_term_weight;
+  static constexpr int kErrRegs = 2;
+  static constexpr int kNeighbours = 1;
+
+  template <int MODE>
+  __device__ __forceinline__ void accumulate(int i, size_t j, const Pose& Tl, const Pose& Te, double* acc) const {
+    const ColorConsistencyTerm& f = *this;
+    const double px = (double)f.points[3 * (size_t)i], py = (double)f.points[3 * (size_t)i + 1], pz = (double)f.points[3 * (size_t)i + 2];
+    const double qx = Te.r00 * px + Te.r01 * py + Te.r02 * pz + Te.tx;
+    const double qy = Te.r10 * px + Te.r11 * py + Te.r12 * pz + Te.ty;
+    const double qz = Te.r20 * px + Te.r21 * py + Te.r22 * pz + Te.tz;
+    const double dx = (double)f.target_points[3 * j] - qx, dy = (double)f.target_points[3 * j + 1] - qy, dz = (double)f.target_points[3 * j + 2] - qz;
+    const double nx = (double)f.target_normals[3 * j], ny = (double)f.target_normals[3 * j + 1], nz = (double)f.target_normals[3 * j + 2];
+    const double gx = (double)f.target_gradients[3 * j], gy = (double)f.target_gradients[3 * j + 1], gz = (double)f.target_gradients[3 * j + 2];
+    const double ng = nx * gx + ny * gy + nz * gz;
+    const double ux = gx - ng * nx, uy = gy - ng * ny, uz = gz - ng * nz;
+    const double rp = ((double)f.target_intensities[j] - (double)f.intensities[i]) - (ux * dx + uy * dy + uz * dz);
+    const double w = f.photometric_term_weight;
+    const double m[6] = {w * (ux * ux), w * (ux * uy), w * (ux * uz), w * (uy * uy), w * (uy * uz), w * (uz * uz)};
+    const double s = w * rp;
+    accumulate_sums_mw<MODE>(Tl, m, -s * ux, -s * uy, -s * uz, w * (rp * rp), px, py, pz, qx, qy, qz, acc);
+  }
+};
+
 }  // namespace gp
 
 // ---------------------------------------------------------------------------------------------------------------
-// host side: the factor handle
+// host side: the factor handles
 // ---------------------------------------------------------------------------------------------------------------
 
 struct gp_colored_gicp_factor : gp_corr_factor_core {  // (the grid is BORROWED, as the ICP factor's)
   gp::ColoredGicpTerm term{};
   int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_colored_factors.hip)
 };
+
+struct gp_color_consistency_factor : gp_corr_factor_core {  // (the grid is BORROWED)
+  gp::ColorConsistencyTerm term{};
+  int run_pass(const double* pose_lin, const double* pose_eval, void* out_host);  // (gp_color_consistency.hip)
+};
+
+// gp_*_factor_set_intensity_grid of the two photometric factors: from now on the correspondence pass is the XYZI search on `xyzi` (NULL: back to the 3-D grid).
+// Stored correspondences are forgotten: they belong to the other search.
+inline int gp_corr_set_intensity_grid(gp_corr_factor_core* f, const gp_intensity_grid* xyzi, const float* source_intensities, const char* who) {
+  if (!f) return gp::fail(GP_ERROR_INVALID_ARGUMENT, std::string(who) + ": null");
+  f->xyzi = xyzi;
+  f->intensities = source_intensities;
+  f->upd.corr_valid = f->upd.lin_valid = false;
+  return GP_OK;
+}

@@ -435,6 +435,10 @@ int gp_corr_batch_create_ex2(const gp_gicp_factor_t* const* gicp, int num_gicp, 
     if (l->plane) t.parts.push_back({l->plane.get(), B::LOAM_PLANE, m, 3, l});
   }));
   GP_TRY(t.add_members(colored, num_colored, "colored GICP", "a colored GICP", [&](const gp_colored_gicp_factor* f, int m) { t.parts.push_back({f, B::COLORED, m, 1, nullptr}); }));
+  // the batch's one search launch is the 3-D one: a member that searches in XYZI (gp_colored_gicp_factor_set_intensity_grid) is refused, never searched in 3-D instead
+  for (const BatchTables::Part& p : t.parts)
+    if (p.core->xyzi)
+      return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: a colored GICP factor on an intensity grid (XYZI search) cannot join a batch yet: the batch searches in 3-D");
   for (const BatchTables::Part& p : t.parts)
     if (p.core->stream != (hipStream_t)stream) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_corr_batch_create: every factor must have been created on the batch's stream");
 

@@ -278,6 +278,9 @@ struct gp_corr_factor_core {
   gp::MappedResults res;           // one record (or one error) and the completion word of the synchronous calls
   gp_corr_update upd;              // (a LOAM part leaves its own unused: gp_loam_factor keeps one for both parts)
   int num_inliers = 0;             // of the last linearise
+  // the photometric factors handed an XYZI structure (gp_intensity_search.hip; BORROWED): search() runs the 4-D walk with the source's intensities, `grid` is unused
+  const gp_intensity_grid* xyzi = nullptr;
+  const float* intensities = nullptr;  // [n] source
 
   int prepare(const gp_point_grid* grid_, const float* points_dev, int n_, double max_sq_dist_, hipStream_t stream_) {
     grid = grid_;
@@ -291,9 +294,12 @@ struct gp_corr_factor_core {
     return res.ensure(sizeof(gp_linearized6), 1);
   }
 
-  // the correspondence pass at pose_lin (n > 0)
+  // the correspondence pass at pose_lin (n > 0): the one place that picks the launch
   int search(const double* pose_lin) {
-    GP_TRY(gp::launch_nearest_correspondences(grid, points, n, pose_lin, max_sq_dist, corr.as<int>(), stream));
+    if (xyzi)
+      GP_TRY(gp::launch_nearest_correspondences_xyzi(xyzi, points, intensities, n, pose_lin, max_sq_dist, corr.as<int>(), stream));
+    else
+      GP_TRY(gp::launch_nearest_correspondences(grid, points, n, pose_lin, max_sq_dist, corr.as<int>(), stream));
     upd.note_search(pose_lin);
     return GP_OK;
   }

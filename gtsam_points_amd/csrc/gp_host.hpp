@@ -459,6 +459,13 @@ int launch_nearest_correspondences(const gp_point_grid* grid, const float* point
 // ... and the k = 2 or 3 nearest, for the LOAM factors: corr is int[k][n], corr[j * n + i] the j-th nearest of point i in ascending order of distance, every slot -1
 // when fewer than k lie within the cut-off
 int launch_nearest_k_correspondences(const gp_point_grid* grid, const float* points, int n, int k, const double pose_lin[16], double max_sq_dist, int* corr, hipStream_t stream);
+}  // namespace gp
+struct gp_intensity_grid;  // private to gp_intensity_search.hip
+namespace gp {
+// gp_intensity_search.hip, for the photometric factors handed an XYZI structure: corr[i] = index of the target point nearest to (pose_lin * points[i], intensities[i])
+// in (x, y, z, intensity) with squared 4-D distance < max_sq_dist, or -1; n > 0.  Asynchronous on `stream`.
+int launch_nearest_correspondences_xyzi(const gp_intensity_grid* grid, const float* points, const float* intensities, int n, const double pose_lin[16], double max_sq_dist,
+                                        int* corr, hipStream_t stream);
 
 // ... and the same search for a BATCH of factors in one launch (gp_corr_batch.hip): what the single launch carries in its kernel arguments -- the search structure,
 // the cloud, the cut-off, the pose -- is read from tables in device memory instead.  A tile is up to 1024 consecutive source points of ONE factor (tiles never

@@ -54,6 +54,52 @@ class KdTreeGPU:
         return idx.cpu().numpy(), d.cpu().numpy(), nf.cpu().numpy()
 
 
+class IntensityKdTreeGPU:
+    """IntensityKdTree (ann/intensity_kdtree.hpp) over a PointCloudGPU with intensities: exact 1-NN in (x, y, z, intensity).  The distance of a query (q, I_q) to
+    target point j is |q - x_j|^2 + (I_q - intensity_scale * I_j)^2 -- the scale on the STORED side only, as the reference writes it; at 1.0 the plain XYZI metric.
+    f64 on the f32 inputs; ties go to the lowest index.  k = 1 only, no search_eps; a point with a non-finite coordinate or intensity is never matched, a query
+    with one gets -1.  What the photometric factors take as target_tree to search in 4-D."""
+
+    def __init__(self, frame: PointCloudGPU, intensity_scale=1.0, cell_size=0.25, stream=None):
+        self._lib = _capi.load()
+        if frame.points_gpu is None or frame.intensities_gpu is None:
+            raise _capi.GPError("error: the frame has no points or no intensities for an IntensityKdTreeGPU")
+        self.frame = frame
+        self.intensity_scale = float(intensity_scale)
+        GaussianVoxelMapGPU._sync_torch(frame)
+        h = C.c_void_p()
+        _capi.check(self._lib.gp_intensity_grid_create(frame.ptr(frame.points_gpu), frame.ptr(frame.intensities_gpu), frame.size(), self.intensity_scale, float(cell_size),
+                                                       stream, C.byref(h)), "gp_intensity_grid_create")
+        self._xyzi = h
+        self._h = C.c_void_p(self._lib.gp_intensity_grid_point_grid(h))  # the 3-D structure inside: what a factor's create takes as its grid
+        self._intensities_ptr = frame.intensities_gpu.data_ptr()
+        self.stream = stream
+
+    def __del__(self):
+        if getattr(self, "_xyzi", None):
+            self._lib.gp_intensity_grid_destroy(self._xyzi)
+            self._xyzi = self._h = None
+
+    def knn_search(self, queries, k=1, max_sq_dist=np.finfo(np.float64).max):
+        """queries: (Q,4) numpy/torch rows (x, y, z, intensity), read as float64 -> (indices (Q,1) int32 with -1 where there is none, sq_dists (Q,1) float64: the
+        4-D squared distances, max_sq_dist where there is none; num_found (Q,))"""
+        import torch
+
+        if int(k) != 1:
+            raise _capi.GPError("IntensityKdTreeGPU.knn_search: k must be 1 (the XYZI search keeps one neighbour)")
+        dev = self.frame.device
+        q = torch.as_tensor(np.asarray(queries, dtype=np.float64) if not isinstance(queries, torch.Tensor) else queries).to(device=dev, dtype=torch.float64).reshape(-1, 4).contiguous()
+        m = int(q.shape[0])
+        idx = torch.empty((m, 1), dtype=torch.int32, device=dev)
+        d = torch.empty((m, 1), dtype=torch.float64, device=dev)
+        torch.cuda.current_stream(dev).synchronize()
+        _capi.check(self._lib.gp_intensity_grid_search(self._xyzi, C.c_void_p(q.data_ptr()), m, float(max_sq_dist), C.c_void_p(idx.data_ptr()), C.c_void_p(d.data_ptr()),
+                                                       self.stream), "gp_intensity_grid_search")
+        _capi.check(self._lib.gp_stream_synchronize(self.stream), "sync")
+        idx = idx.cpu().numpy()
+        return idx, d.cpu().numpy(), (idx[:, 0] >= 0).astype(np.int32)
+
+
 def estimate_covariances_gpu(frame: PointCloudGPU, k_neighbors=10, cell_size=0.0, stream=None, structure=0, counters=None):
     """estimate_covariances(points, n, k): fills frame.covs_gpu (float [N][9]); returns the number of points with < k neighbours.
     structure / counters: per call, see KdTreeGPU (not part of the reference API)."""
@@ -220,6 +266,7 @@ def estimate_intensity_gradients_gpu(frame: PointCloudGPU, k_neighbors=10, neigh
 # defined when it is imported from here -- so this module is imported before it (the package does)
 from .corr_factors import (  # noqa: E402,F401
     CorrespondenceFactorBatchGPU,
+    IntegratedColorConsistencyFactorGPU,
     IntegratedColoredGICPFactorGPU,
     IntegratedCTGICPFactorGPU,
     IntegratedCTICPFactorGPU,

@@ -523,7 +523,8 @@ int gp_estimate_intensity_gradients(const float* points_dev, const float* normal
                                     float* gradients_dev, int* num_short, gp_stream_t stream);
 
 /* IntegratedColoredGICPFactor_ (factors/integrated_colored_gicp_factor.hpp, impl/integrated_colored_gicp_factor_impl.hpp) on the 1-NN correspondences of T_lin p
- * with squared distance < max (:119-129; the 3-D search of the other factors -- the reference's optional 4-D IntensityKdTree is not provided).  With q = T p_A,
+ * with squared distance < max (:119-129; the 3-D search of the other factors, or -- gp_colored_gicp_factor_set_intensity_grid below -- the reference's 4-D
+ * IntensityKdTree search, in which the distance held against max is the 4-D one).  With q = T p_A,
  * d = mu_B - q, P = I - n_B n_B^T and u = P g_B (g_B the target's intensity gradient, :236-241):
  *   geometric    d with M_g = (C_B + R C_A R^T)^-1 taken at the LINEARISATION pose, as update_correspondences stores it (:134-138)
  *   photometric  r_p = I_B - I_A - u . d (:207-209)
@@ -548,6 +549,49 @@ int gp_colored_gicp_factor_set_photometric_term_weight(gp_colored_gicp_factor_t*
 int gp_colored_gicp_factor_set_max_correspondence_distance(gp_colored_gicp_factor_t* f, double dist);
 int gp_colored_gicp_factor_set_correspondence_update_tolerance(gp_colored_gicp_factor_t* f, double angle, double trans);
 int gp_colored_gicp_factor_num_correspondences(const gp_colored_gicp_factor_t* f);
+
+/* IntensityKdTree (ann/intensity_kdtree.hpp, src/gtsam_points/ann/intensity_kdtree.cpp): exact 1-NN in (x, y, z, intensity).  For a query (q, I_q) the answer is the
+ * target index j that minimises
+ *     d4^2(j) = |q - x_j|^2 + (I_q - s I_j)^2,   s = intensity_scale,
+ * the scale on the STORED side only, as the reference writes it (kdtree_get_pt multiplies by intensity_scale; the factors put the raw source intensity into pt[3]).
+ * f64 on the f32 inputs (s I_j one f64 product); a match is kept when d4^2 < max_sq_dist (strict; the reference's knn_search ignores max_sq_dist and its callers
+ * apply this test).  Ties: the LOWEST target index among the nearest.  Same bits on every run.
+ * The structure is a gp_point_grid over the points (cell_size <= 0 picks 0.25 m; the binned grid, or the hashed one for a bounding box too wide for it) plus a
+ * cell-sorted copy of the intensities; it OWNS those and BORROWS points_dev / intensities_dev, which must outlive it unchanged.
+ * Deviations: k = 1 only and no search_eps (the approximate search).  A target point with a non-finite coordinate or intensity is never matched and a query with
+ * one gets -1 (nanoflann's behaviour on NaN is unspecified).  As with gp_knn_search, an unbounded query (max_sq_dist = DBL_MAX) far from every point walks the
+ * structure until its bounding box is exhausted.
+ * gp_intensity_grid_search: queries_dev double[m][4] = (x, y, z, intensity) -> indices_dev int[m] (-1: none), sq_dists_dev double[m] (may be NULL; max_sq_dist where
+ * there is none).  Asynchronous on `stream`.  create is synchronous.  destroy synchronises the device. */
+typedef struct gp_intensity_grid gp_intensity_grid_t;
+int gp_intensity_grid_create(const float* points_dev, const float* intensities_dev, int num_points, double intensity_scale, double cell_size, gp_stream_t stream,
+                             gp_intensity_grid_t** out);
+int gp_intensity_grid_destroy(gp_intensity_grid_t* g);
+int gp_intensity_grid_search(const gp_intensity_grid_t* g, const double* queries_dev, int m, double max_sq_dist, int* indices_dev, double* sq_dists_dev, gp_stream_t stream);
+/* the 3-D structure inside (owned by `g`, valid while it lives): what a factor's create takes as `grid` before _set_intensity_grid hands it `g`; NULL for NULL */
+const gp_point_grid_t* gp_intensity_grid_point_grid(const gp_intensity_grid_t* g);
+/* from now on the factor's correspondence pass is the XYZI search on `xyzi` (BORROWED; built over the factor's target points and intensities) with the source's
+ * intensities as I_q, integrated_colored_gicp_factor_impl.hpp:121-127; NULL: back to the 3-D grid.  Stored correspondences are forgotten.  A factor in this state is
+ * refused by gp_corr_batch_create* (the batch searches in 3-D). */
+int gp_colored_gicp_factor_set_intensity_grid(gp_colored_gicp_factor_t* f, const gp_intensity_grid_t* xyzi);
+
+/* IntegratedColorConsistencyFactor_ (factors/integrated_color_consistency_factor.hpp, impl/integrated_color_consistency_factor_impl.hpp): the photometric term of
+ * the colored GICP factor alone, on the 1-NN correspondences of T_lin p (3-D on `grid`, or XYZI after _set_intensity_grid).  With q = T p_A, d = mu_B - q,
+ * u = (I - n_B n_B^T) g_B, r_p = I_B - I_A - u . d and w = photometric_term_weight (default 1.0 upstream, :31; any finite w >= 0):
+ *   error = sum w r_p^2 (:200; no 1/2), H = sum J^T (w u u^T) J (:217-219), b = sum J^T (-w r_p u) (:220-221), J_t = [-[q]x, I], J_s = [R [p]x, -R].
+ * No covariance is read.  `grid` is BORROWED.  Every entry point has the semantics of its gp_colored_gicp_factor_* namesake.  Not a member of gp_corr_batch_* yet. */
+typedef struct gp_color_consistency_factor gp_color_consistency_factor_t;
+int gp_color_consistency_factor_create(const gp_point_grid_t* grid, const float* target_points_dev, const float* target_normals_dev, const float* target_intensities_dev,
+                                       const float* target_gradients_dev, int num_target, const float* points_dev, const float* intensities_dev, int num_points,
+                                       double max_correspondence_distance_sq, double photometric_term_weight, gp_stream_t stream, gp_color_consistency_factor_t** out);
+int gp_color_consistency_factor_destroy(gp_color_consistency_factor_t* f); /* leaves the grids alone */
+int gp_color_consistency_factor_set_intensity_grid(gp_color_consistency_factor_t* f, const gp_intensity_grid_t* xyzi);
+int gp_color_consistency_factor_linearize(gp_color_consistency_factor_t* f, const double pose[16], gp_linearized6* out_host);
+int gp_color_consistency_factor_compute_error(gp_color_consistency_factor_t* f, const double pose_lin[16], const double pose_eval[16], double* out_host);
+int gp_color_consistency_factor_set_photometric_term_weight(gp_color_consistency_factor_t* f, double weight);
+int gp_color_consistency_factor_set_max_correspondence_distance(gp_color_consistency_factor_t* f, double dist);
+int gp_color_consistency_factor_set_correspondence_update_tolerance(gp_color_consistency_factor_t* f, double angle, double trans);
+int gp_color_consistency_factor_num_correspondences(const gp_color_consistency_factor_t* f);
 
 /* IntegratedCT_ICPFactor_ / IntegratedCT_GICPFactor_ (factors/integrated_ct_icp_factor.hpp, integrated_ct_gicp_factor.hpp and their impl/ files): a scan taken
  * while the sensor moved from pose0 (first key) to pose1 (second key), every source point transformed by the pose interpolated at its own time stamp.
