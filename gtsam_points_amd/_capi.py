@@ -85,6 +85,10 @@ _SIGNATURES = {
     "gp_voxelmap_create": (C.c_int, [C.c_double, C.c_int, C.c_int, C.c_double, C.c_void_p, C.POINTER(C.c_void_p)]),
     "gp_voxelmap_destroy": (C.c_int, [C.c_void_p]),
     "gp_voxelmap_insert": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gp_voxelmap_insert_incremental": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "gp_voxelmap_set_lru": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64]),
+    "gp_voxelmap_lru_get": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "gp_voxelmap_download_stamps": (C.c_int, [C.c_void_p, C.c_void_p]),
     "gp_voxelmap_info_get": (C.c_int, [C.c_void_p, C.POINTER(VoxelMapInfo)]),
     "gp_voxelmap_resolution": (C.c_double, [C.c_void_p]),
     "gp_voxelmap_views_get": (C.c_int, [C.c_void_p, C.POINTER(VoxelMapViews)]),

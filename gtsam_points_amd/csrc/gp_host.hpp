@@ -595,15 +595,18 @@ struct gp_voxelmap {
 
   // THE table of the map's arrays: each device array with the host copy that offload() keeps of it; array_bytes() is its size for the current `info`.
   // alloc_voxel_arrays, download, clone, offload and reload (gp_voxelmap.hip, gp_voxelmap_store.hip) walk it; a new per-voxel array is one more row here.  kGblocks stays last: the one array a map may lack (has_grid)
-  enum ArrayId { kBuckets, kRecords, kNumPoints, kMeans, kCovs, kIntensities, kCoords, kGblocks, kNumArrays };
+  // kSums / kStamps: what an INCREMENTAL map (gp_voxelmap_incremental.hip) keeps besides -- per voxel nine f64 sums (sum(p - centre), upper triangle of sum(cov)) and the
+  // value of lru_counter at the insert that last touched the voxel; empty (has_sums == false) for a map that never took an incremental insert
+  enum ArrayId { kBuckets, kRecords, kNumPoints, kMeans, kCovs, kIntensities, kCoords, kSums, kStamps, kGblocks, kNumArrays };
   struct Array {
     gp::DeviceArray dev;
     std::vector<char> host;
   };
   Array arrays[kNumArrays];
   size_t array_bytes(int id) const {
-    static constexpr size_t kEntry[kNumArrays] = {sizeof(gp_voxel_bucket), sizeof(gp::VoxelRecord), sizeof(int),     sizeof(float) * 3,
-                                                  sizeof(float) * 9,       sizeof(float),           sizeof(int) * 3, sizeof(gp::GridBlock)};
+    static constexpr size_t kEntry[kNumArrays] = {sizeof(gp_voxel_bucket), sizeof(gp::VoxelRecord), sizeof(int),     sizeof(float) * 3,  sizeof(float) * 9,
+                                                  sizeof(float),           sizeof(int) * 3,         sizeof(double) * 9, sizeof(int64_t), sizeof(gp::GridBlock)};
+    if ((id == kSums || id == kStamps) && !has_sums) return 0;
     const size_t n = id == kBuckets ? (size_t)info.num_buckets : id == kGblocks ? (has_grid ? (size_t)num_grid_blocks() : 0) : (size_t)info.num_voxels;
     return kEntry[id] * n;
   }
@@ -614,6 +617,8 @@ struct gp_voxelmap {
   gp::DeviceArray& voxel_covs = arrays[kCovs].dev;                // float[num_voxels][9]
   gp::DeviceArray& voxel_intensities = arrays[kIntensities].dev;  // float[num_voxels]
   gp::DeviceArray& voxel_coords = arrays[kCoords].dev;            // int[num_voxels][3] voxel coordinate of each voxel index
+  gp::DeviceArray& voxel_sums = arrays[kSums].dev;                // double[num_voxels][9]         (incremental maps only)
+  gp::DeviceArray& voxel_stamps = arrays[kStamps].dev;            // int64_t[num_voxels]           (incremental maps only)
   gp::DeviceArray& gblocks = arrays[kGblocks].dev;                // occupancy-block grid (gp::GridBlock[num_grid_blocks()]); empty when the box is too large
   // (not in the table: no host copy -- a reload builds it again)
   gp::DeviceArray plines;  // line table of the hashed VGICP kernel family (gp::VoxelMapView::plines): built on first use when the map has its block grid (round 4: its
@@ -627,6 +632,17 @@ struct gp_voxelmap {
   long long num_grid_blocks() const { return (long long)grid.dim[0] * grid.dim[1] * grid.dim[2]; }
   bool force_hashed_build = false;  // gp_voxelmap_set_tuning(GP_TUNE_MAP_BUILD): the next insert() uses the hashed build
   int bucket_load_percent = 33;     // GP_TUNE_BUCKET_LOAD: the binned build enters the reference's doubling sequence at the first size that holds the voxels at this load factor
+
+  // the sliding local map (IncrementalVoxelMap, ann/incremental_voxelmap.hpp:130-132): every gp_voxelmap_insert_incremental stamps the voxels it touches with
+  // lru_counter, then ++lru_counter, and every lru_clear_cycle-th call drops the voxels with stamp + lru_horizon < lru_counter
+  bool has_sums = false;  // the map was built by incremental inserts: kSums / kStamps are live
+  int64_t lru_counter = 0, lru_horizon = 10, lru_clear_cycle = 10;
+  void drop_incremental_state() {  // a one-shot build (insert, assign) replaces the map: it is no incremental map any more
+    has_sums = false;
+    lru_counter = 0;
+    voxel_sums.release();
+    voxel_stamps.release();
+  }
 
   bool offloaded = false;   // OffloadableGPU: the arrays live in arrays[].host
   uint64_t generation = 0;  // bumped whenever the device arrays are (re)allocated: factor tables built from view() go stale

@@ -330,6 +330,7 @@ int gp_voxelmap_insert(gp_voxelmap_t* m, const float* points_dev, const float* c
   // re-inserting into a map that already holds arrays releases them to the block cache ("any stream may take them"): kernels of other streams
   // that still read the old map must have finished.  A fresh map has nothing to wait for.
   if (m->buckets.ptr) GP_HIP(hipDeviceSynchronize());
+  m->drop_incremental_state();  // (an incremental map is replaced like any other, and counts its inserts from zero again)
   m->offloaded = false;
   m->generation++;
   if (n > 0 && !m->force_hashed_build) {

@@ -1,5 +1,6 @@
-// gp_voxelmap.hpp -- what the two host units of the voxel map share: gp_voxelmap.hip (handle, the two builds, the queries) and gp_voxelmap_store.hip (download, assign,
-// save / load, clone, offload / reload).  The map itself is gp_voxelmap in gp_host.hpp, with the one table of its arrays.
+// gp_voxelmap.hpp -- what the host units of the voxel map share: gp_voxelmap.hip (handle, the two builds, the queries), gp_voxelmap_store.hip (download, assign,
+// save / load, clone, offload / reload) and gp_voxelmap_incremental.hip (the incremental insert with LRU eviction).  The map itself is gp_voxelmap in gp_host.hpp, with
+// the one table of its arrays.
 #pragma once
 
 #include "gp_binning.hpp"

@@ -1,10 +1,13 @@
-// gp_voxelmap_kernels.hpp -- the kernels of the voxel-map build, included by gp_voxelmap.hip alone (which launches them):
+// gp_voxelmap_kernels.hpp -- the kernels of the voxel-map build, included by the two units that launch them: gp_voxelmap.hip (the one-shot builds) and
+// gp_voxelmap_incremental.hip (the incremental insert, which shares the grid and bucket kernels).  Every kernel is `inline`, so that both units may hold it:
 //   * shared by both builds: voxel_of / point_coord (which voxel a point belongs to) and intensity_max
 //   * the hashed build, reference-shaped -- the FALLBACK for a cloud whose box exceeds the block grid, for an empty cloud and for A/B (GP_TUNE_MAP_BUILD):
 //     claim_buckets_kernel, assign_voxels_kernel, accumulate_kernel (native f64 atomics relative to the voxel centre: not bit-reproducible), finalize_kernel
 //   * the line table of the hashed VGICP kernel family: line_claim_kernel
 //   * the occupancy-block grid of a hashed build: coords_bbox_kernel, grid_mark_kernel, grid_count_kernel, grid_renumber_kernel, buckets_renumber_kernel
 //   * the binned build, the DEFAULT: segmented_stats_kernel (an ordered segmented sum, no atomics: bit-identical from run to run) and insert_voxels_kernel
+//   * the incremental insert: segmented_sums_kernel (the same sum, not finalized), survivors_bbox_kernel, grid_mark_survivors_kernel, merge_source_kernel,
+//     merge_finalize_kernel
 //
 // Replaces the thrust::for_each functors of src/gtsam_points/types/gaussian_voxelmap_gpu.cu:25-172.  Differences by design:
 //   * voxel coordinates are floor(double(p) * (1.0/leaf)) -- the CPU map's rule (gaussian_voxelmap_cpu.cpp:59-61)
@@ -40,7 +43,7 @@ __device__ __forceinline__ float intensity_max(float cur, float x) { return cur 
 
 // voxel_bucket_assignment_kernel (gaussian_voxelmap_gpu.cu:37-75): claim a bucket per distinct voxel coordinate.
 // rep[b] = index of the first point that claimed bucket b, or -1.
-__global__ void __launch_bounds__(256) claim_buckets_kernel(const float* __restrict__ points, int n, int* __restrict__ rep, uint32_t num_buckets,
+inline __global__ void __launch_bounds__(256) claim_buckets_kernel(const float* __restrict__ points, int n, int* __restrict__ rep, uint32_t num_buckets,
                                                             uint32_t mask, int max_scan, double inv_leaf, int* __restrict__ invalid,
                                                             int* __restrict__ failures) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -63,7 +66,7 @@ __global__ void __launch_bounds__(256) claim_buckets_kernel(const float* __restr
 }
 
 // voxel_coord_select_kernel (:77-90) + voxel id allocation (:57-60)
-__global__ void __launch_bounds__(256) assign_voxels_kernel(const float* __restrict__ points, const int* __restrict__ rep, uint32_t num_buckets,
+inline __global__ void __launch_bounds__(256) assign_voxels_kernel(const float* __restrict__ points, const int* __restrict__ rep, uint32_t num_buckets,
                                                             double inv_leaf, gp_voxel_bucket* __restrict__ buckets, int* __restrict__ voxel_coords,
                                                             int* __restrict__ num_voxels) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,7 +86,7 @@ __global__ void __launch_bounds__(256) assign_voxels_kernel(const float* __restr
 }
 
 // accumulate_points_kernel (:92-152): sums[v] = { sum(p - centre) (3), sum upper(C) (6) } in double, count, max intensity
-__global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict__ points, const float* __restrict__ covs,
+inline __global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict__ points, const float* __restrict__ covs,
                                                          const float* __restrict__ intensities, int n, VoxelMapView map, double* __restrict__ sums,
                                                          int* __restrict__ counts, unsigned int* __restrict__ intensity_bits) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -116,7 +119,7 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict
 }
 
 // finalize_voxels_kernel (:154-172): divide by the count; emit the gather record and the reference-visible arrays
-__global__ void __launch_bounds__(256) finalize_kernel(int num_voxels, double leaf, const int* __restrict__ voxel_coords, const double* __restrict__ sums,
+inline __global__ void __launch_bounds__(256) finalize_kernel(int num_voxels, double leaf, const int* __restrict__ voxel_coords, const double* __restrict__ sums,
                                                        const int* __restrict__ counts, VoxelRecord* __restrict__ records,
                                                        float* __restrict__ voxel_means, float* __restrict__ voxel_covs) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -148,7 +151,7 @@ __global__ void __launch_bounds__(256) finalize_kernel(int num_voxels, double le
 }
 
 // line table: claim the first free key slot of the home line (front to back), else walk to the next line
-__global__ void __launch_bounds__(256) line_claim_kernel(int num_voxels, const int* __restrict__ voxel_coords, gp_voxel_bucket* __restrict__ lines, uint32_t lmask) {
+inline __global__ void __launch_bounds__(256) line_claim_kernel(int num_voxels, const int* __restrict__ voxel_coords, gp_voxel_bucket* __restrict__ lines, uint32_t lmask) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= num_voxels) return;
   const int cx = voxel_coords[3 * (size_t)v], cy = voxel_coords[3 * (size_t)v + 1], cz = voxel_coords[3 * (size_t)v + 2];
@@ -170,7 +173,7 @@ __global__ void __launch_bounds__(256) line_claim_kernel(int num_voxels, const i
 // ---- occupancy-block grid (gp_device.hpp: GridBlock; geometry helpers in gp_binning.hpp) ----
 
 // bounding box of the voxel coordinates in block units: bbox[0..2] = min, bbox[3..5] = max (wave reduce + one atomic per wave)
-__global__ void __launch_bounds__(256) coords_bbox_kernel(int num_voxels, const int* __restrict__ voxel_coords, int* __restrict__ bbox) {
+inline __global__ void __launch_bounds__(256) coords_bbox_kernel(int num_voxels, const int* __restrict__ voxel_coords, int* __restrict__ bbox) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   const int u = v < num_voxels ? v : num_voxels - 1;
   int lo[3], hi[3];
@@ -192,20 +195,20 @@ __global__ void __launch_bounds__(256) coords_bbox_kernel(int num_voxels, const 
   }
 }
 
-__global__ void __launch_bounds__(256) grid_mark_kernel(int num_voxels, const int* __restrict__ voxel_coords, GridGeom g, GridBlock* __restrict__ blocks) {
+inline __global__ void __launch_bounds__(256) grid_mark_kernel(int num_voxels, const int* __restrict__ voxel_coords, GridGeom g, GridBlock* __restrict__ blocks) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= num_voxels) return;
   const int cx = voxel_coords[3 * (size_t)v], cy = voxel_coords[3 * (size_t)v + 1], cz = voxel_coords[3 * (size_t)v + 2];
   atomicOr(&blocks[grid_block_index(g, cx, cy, cz)].bits, 1ull << grid_bit(cx, cy, cz));
 }
 
-__global__ void __launch_bounds__(256) grid_count_kernel(long long num_blocks, GridBlock* __restrict__ blocks) {
+inline __global__ void __launch_bounds__(256) grid_count_kernel(long long num_blocks, GridBlock* __restrict__ blocks) {
   const long long b = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b < num_blocks) blocks[b].base = __popcll(blocks[b].bits);
 }
 
 // new index of every voxel = base of its block + number of occupied bits below its own; coordinates move to the new order
-__global__ void __launch_bounds__(256) grid_renumber_kernel(int num_voxels, const int* __restrict__ coords_old, GridGeom g, const GridBlock* __restrict__ blocks,
+inline __global__ void __launch_bounds__(256) grid_renumber_kernel(int num_voxels, const int* __restrict__ coords_old, GridGeom g, const GridBlock* __restrict__ blocks,
                                                             int* __restrict__ perm, int* __restrict__ coords_new) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   if (v >= num_voxels) return;
@@ -218,7 +221,7 @@ __global__ void __launch_bounds__(256) grid_renumber_kernel(int num_voxels, cons
   coords_new[3 * (size_t)nv + 2] = cz;
 }
 
-__global__ void __launch_bounds__(256) buckets_renumber_kernel(uint32_t num_buckets, gp_voxel_bucket* __restrict__ buckets, const int* __restrict__ perm) {
+inline __global__ void __launch_bounds__(256) buckets_renumber_kernel(uint32_t num_buckets, gp_voxel_bucket* __restrict__ buckets, const int* __restrict__ perm) {
   const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= num_buckets) return;
   const int v = buckets[b].voxel_index;
@@ -235,12 +238,17 @@ __global__ void __launch_bounds__(256) buckets_renumber_kernel(uint32_t num_buck
 // sixteen lanes at the end: the statistics are bit-identical from run to run (no atomics) and do not depend on where the 512-row batches fall.
 // sums relative to the voxel centre in f64, like accumulate_kernel; outputs as finalize_kernel.
 constexpr int kStatsBatch = 512;
-__global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __restrict__ points, const float* __restrict__ covs, const float* __restrict__ intensities,
-                                                              int num_voxels, const int* __restrict__ cell_start, const int* __restrict__ order, double inv_leaf, double leaf,
-                                                              VoxelRecord* __restrict__ records, int* __restrict__ num_points, float* __restrict__ voxel_means,
-                                                              float* __restrict__ voxel_covs, float* __restrict__ voxel_intensities, int* __restrict__ voxel_coords,
-                                                              const gp::FillJob fill_buckets) {
-  gp::run_fill_job(fill_buckets);  // (the bucket table the insertion kernel behind this one claims its slots in: 0xff = empty)
+// what the sixteen lanes of a voxel hold after the sum; `writer` is true in the one lane that emits the voxel
+struct SegmentSums {
+  int v, n;                 // voxel (cell) ordinal, its points
+  int cx, cy, cz;           // its coordinate
+  double ox, oy, oz;        // its centre
+  double acc[9];            // sum(p - centre), upper triangle of sum(sym(C))
+  float imax;               // intensity_max from +0.0
+};
+// the sum itself, shared by segmented_stats_kernel (the one-shot build: finalized records) and segmented_sums_kernel (the incremental insert: the raw sums)
+__device__ __forceinline__ bool segmented_sums(const float* __restrict__ points, const float* __restrict__ covs, const float* __restrict__ intensities, int num_voxels,
+                                               const int* __restrict__ cell_start, const int* __restrict__ order, double inv_leaf, double leaf, SegmentSums& out) {
   constexpr int kGroup = 16;
   __shared__ float rows[kStatsBatch][12];  // x y z, then the covariance's nine entries
   __shared__ float inten[kStatsBatch];
@@ -310,9 +318,28 @@ __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __res
   }
 #pragma unroll
   for (int off = kGroup / 2; off > 0; off >>= 1) imax = intensity_max(imax, __shfl_xor(imax, off, kGroup));
-  if (!live) return;
-  if (lane != 0) return;
-  const int n = e - b;
+  out.v = v;
+  out.n = e - b;
+  out.cx = cx, out.cy = cy, out.cz = cz;
+  out.ox = ox, out.oy = oy, out.oz = oz;
+#pragma unroll
+  for (int k = 0; k < 9; k++) out.acc[k] = acc[k];
+  out.imax = imax;
+  return live && lane == 0;
+}
+
+inline __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __restrict__ points, const float* __restrict__ covs, const float* __restrict__ intensities,
+                                                              int num_voxels, const int* __restrict__ cell_start, const int* __restrict__ order, double inv_leaf, double leaf,
+                                                              VoxelRecord* __restrict__ records, int* __restrict__ num_points, float* __restrict__ voxel_means,
+                                                              float* __restrict__ voxel_covs, float* __restrict__ voxel_intensities, int* __restrict__ voxel_coords,
+                                                              const gp::FillJob fill_buckets) {
+  gp::run_fill_job(fill_buckets);  // (the bucket table the insertion kernel behind this one claims its slots in: 0xff = empty)
+  SegmentSums sum;
+  if (!segmented_sums(points, covs, intensities, num_voxels, cell_start, order, inv_leaf, leaf, sum)) return;
+  const int v = sum.v, n = sum.n, cx = sum.cx, cy = sum.cy, cz = sum.cz;
+  const double ox = sum.ox, oy = sum.oy, oz = sum.oz;
+  const double* acc = sum.acc;
+  const float imax = sum.imax;
   const double inv_n = 1.0 / (double)n;
   VoxelRecord rec;
   const double lx = acc[0] * inv_n, ly = acc[1] * inv_n, lz = acc[2] * inv_n;
@@ -341,7 +368,7 @@ __global__ void __launch_bounds__(256) segmented_stats_kernel(const float* __res
 
 // reference-visible bucket table from the list of DISTINCT voxels: claim the first free bucket of the probe chain
 // (reference hash + max_bucket_scan_count rule, so lookup_voxel finds it); failed[0] += points of a voxel whose chain is full
-__global__ void __launch_bounds__(256) insert_voxels_kernel(int num_voxels, const int* __restrict__ voxel_coords, const int* __restrict__ num_points,
+inline __global__ void __launch_bounds__(256) insert_voxels_kernel(int num_voxels, const int* __restrict__ voxel_coords, const int* __restrict__ num_points,
                                                             gp_voxel_bucket* __restrict__ buckets, uint32_t num_buckets, uint32_t mask, int max_scan,
                                                             int* __restrict__ failed) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
@@ -358,6 +385,174 @@ __global__ void __launch_bounds__(256) insert_voxels_kernel(int num_voxels, cons
     }
   }
   *failed = 1;  // (a flag, not a count: the caller doubles the table until nothing fails; host-mapped on the binned build's path)
+}
+
+// ---- incremental insert (gp_voxelmap_incremental.hip): a voxel-level merge of the map's voxels with the cells of the new frame ------------------------------
+// The frame is binned like a one-shot build's cloud; segmented_sums_kernel leaves each of its cells' count, f64 sums, intensity and coordinate.  The surviving old
+// voxels and the new cells mark their bits in a FRESH block grid over the union box; a voxel of the merged map is a set bit, numbered in (block, bit) order like
+// every map.  merge_source_kernel writes, per merged voxel, which old voxel and which new cell it is made of (-1: none); merge_finalize_kernel gathers the two, adds
+// old + new in f64 and emits everything the map keeps of a voxel.  No atomics on sums: two maps fed the same frames hold the same bits.
+
+// the eviction rule of IncrementalVoxelMap::insert (ann/impl/incremental_voxelmap_impl.hpp:49-55) for a voxel the new frame does NOT touch: `counter` is
+// lru_counter after its increment; evict = the call is a clearing one (counter % lru_clear_cycle == 0)
+__device__ __forceinline__ bool voxel_survives(long long stamp, int evict, long long horizon, long long counter) { return !evict || stamp + horizon >= counter; }
+
+__device__ __forceinline__ bool grid_contains(const GridGeom& g, int cx, int cy, int cz) {
+  const int bx = (cx >> 2) - g.lo[0], by = (cy >> 2) - g.lo[1], bz = (cz >> 2) - g.lo[2];
+  return bx >= 0 && bx < g.dim[0] && by >= 0 && by < g.dim[1] && bz >= 0 && bz < g.dim[2];
+}
+
+// the sums of the frame's cells, as segmented_stats_kernel forms them (same lanes, same order), not finalized
+inline __global__ void __launch_bounds__(256) segmented_sums_kernel(const float* __restrict__ points, const float* __restrict__ covs, const float* __restrict__ intensities,
+                                                                    int num_cells, const int* __restrict__ cell_start, const int* __restrict__ order, double inv_leaf,
+                                                                    double leaf, int* __restrict__ cell_counts, double* __restrict__ cell_sums,
+                                                                    float* __restrict__ cell_intensities, int* __restrict__ cell_coords) {
+  SegmentSums sum;
+  if (!segmented_sums(points, covs, intensities, num_cells, cell_start, order, inv_leaf, leaf, sum)) return;
+  const size_t c = (size_t)sum.v;
+  cell_counts[c] = sum.n;
+#pragma unroll
+  for (int k = 0; k < 9; k++) cell_sums[9 * c + k] = sum.acc[k];
+  cell_intensities[c] = sum.imax;
+  cell_coords[3 * c] = sum.cx;
+  cell_coords[3 * c + 1] = sum.cy;
+  cell_coords[3 * c + 2] = sum.cz;
+}
+
+// coords_bbox_kernel over the voxels that survive a clearing call (an evicted voxel contributes the empty box)
+inline __global__ void __launch_bounds__(256) survivors_bbox_kernel(int num_voxels, const int* __restrict__ voxel_coords, const long long* __restrict__ stamps,
+                                                                    long long horizon, long long counter, int* __restrict__ bbox) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool alive = v < num_voxels && voxel_survives(stamps[v], 1, horizon, counter);
+  int lo[3], hi[3];
+#pragma unroll
+  for (int a = 0; a < 3; a++) {
+    const int b = alive ? voxel_coords[3 * (size_t)v + a] >> 2 : 0;
+    lo[a] = alive ? b : 0x7fffffff;
+    hi[a] = alive ? b : (int)0x80000000;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1)
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
+      hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
+    }
+  if ((threadIdx.x & 63) == 0 && lo[0] <= hi[0]) {
+#pragma unroll
+    for (int a = 0; a < 3; a++) {
+      atomicMin(bbox + a, lo[a]);
+      atomicMax(bbox + 3 + a, hi[a]);
+    }
+  }
+}
+
+// grid_mark_kernel with the eviction rule: the old voxels that survive mark their bits in the new grid (stamps == null: the frame's cells, which all do).
+// The new box holds every survivor and every cell by construction; a coordinate outside it marks nothing
+inline __global__ void __launch_bounds__(256) grid_mark_survivors_kernel(int num, const int* __restrict__ coords, const long long* __restrict__ stamps, int evict,
+                                                                         long long horizon, long long counter, GridGeom g, GridBlock* __restrict__ blocks) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= num) return;
+  if (stamps && !voxel_survives(stamps[v], evict, horizon, counter)) return;
+  const int cx = coords[3 * (size_t)v], cy = coords[3 * (size_t)v + 1], cz = coords[3 * (size_t)v + 2];
+  if (!grid_contains(g, cx, cy, cz)) return;
+  atomicOr(&blocks[grid_block_index(g, cx, cy, cz)].bits, 1ull << grid_bit(cx, cy, cz));
+}
+
+// source[new index] = v for every old voxel (or new cell) v whose bit is set in the new grid.  For an old voxel that is: it survived by its stamp, or the frame
+// touches it (the cell set the bit) -- exactly the voxels the reference keeps, whose stamp of a touched voxel is the current counter.  An evicted voxel may lie
+// outside the new box
+inline __global__ void __launch_bounds__(256) merge_source_kernel(int num, const int* __restrict__ coords, GridGeom g, const GridBlock* __restrict__ blocks,
+                                                                  int* __restrict__ source) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= num) return;
+  const int cx = coords[3 * (size_t)v], cy = coords[3 * (size_t)v + 1], cz = coords[3 * (size_t)v + 2];
+  if (!grid_contains(g, cx, cy, cz)) return;
+  const GridBlock blk = blocks[grid_block_index(g, cx, cy, cz)];
+  const unsigned long long bit = 1ull << grid_bit(cx, cy, cz);
+  if (!(blk.bits & bit)) return;
+  source[blk.base + __popcll(blk.bits & (bit - 1ull))] = v;
+}
+
+// the old map's per-voxel arrays, and the frame's per-cell arrays, as merge_finalize_kernel gathers them
+struct MergeOld {
+  const int* coords;
+  const int* counts;
+  const double* sums;
+  const long long* stamps;
+  const float* intensities;
+};
+struct MergeNew {
+  const int* coords;
+  const int* counts;
+  const double* sums;
+  const float* intensities;
+};
+// one thread per voxel of the merged map: old + new in f64 (a voxel of one source alone keeps that source's sums to the bit), then the division and the outputs of
+// segmented_stats_kernel
+inline __global__ void __launch_bounds__(256) merge_finalize_kernel(int num_voxels, const int* __restrict__ source_old, const int* __restrict__ source_new, MergeOld old,
+                                                                    MergeNew cell, long long stamp_now, double leaf, double* __restrict__ sums,
+                                                                    long long* __restrict__ stamps, VoxelRecord* __restrict__ records, int* __restrict__ num_points,
+                                                                    float* __restrict__ voxel_means, float* __restrict__ voxel_covs,
+                                                                    float* __restrict__ voxel_intensities, int* __restrict__ voxel_coords,
+                                                                    const gp::FillJob fill_buckets) {
+  gp::run_fill_job(fill_buckets);  // (the bucket table insert_voxels_kernel claims its slots in behind this kernel: 0xff = empty)
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= num_voxels) return;
+  const int so = source_old[v], sn = source_new[v];  // at least one of the two is a source: the bit was set by one of them
+  double acc[9];
+  int n = 0, cx = 0, cy = 0, cz = 0;
+  float imax = 0.0f;
+  long long stamp = stamp_now;
+  if (so >= 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) acc[k] = old.sums[9 * (size_t)so + k];
+    n = old.counts[so];
+    imax = old.intensities[so];
+    stamp = old.stamps[so];
+    cx = old.coords[3 * (size_t)so], cy = old.coords[3 * (size_t)so + 1], cz = old.coords[3 * (size_t)so + 2];
+  }
+  if (sn >= 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      const double x = cell.sums[9 * (size_t)sn + k];
+      acc[k] = so >= 0 ? acc[k] + x : x;
+    }
+    n += cell.counts[sn];
+    imax = intensity_max(imax, cell.intensities[sn]);
+    stamp = stamp_now;
+    cx = cell.coords[3 * (size_t)sn], cy = cell.coords[3 * (size_t)sn + 1], cz = cell.coords[3 * (size_t)sn + 2];
+  }
+  if (so < 0 && sn < 0) return;  // (cannot happen; nothing is written from undefined sums)
+#pragma unroll
+  for (int k = 0; k < 9; k++) sums[9 * (size_t)v + k] = acc[k];
+  stamps[v] = stamp;
+  const double inv_n = 1.0 / (double)n;
+  VoxelRecord rec;
+  const double lx = acc[0] * inv_n, ly = acc[1] * inv_n, lz = acc[2] * inv_n;
+  rec.mean_local[0] = (float)lx;
+  rec.mean_local[1] = (float)ly;
+  rec.mean_local[2] = (float)lz;
+  rec.num_points = n;
+#pragma unroll
+  for (int k = 0; k < 6; k++) rec.cov[k] = acc[3 + k] / (double)n;
+  records[v] = rec;
+  num_points[v] = n;
+  const double ox = ((double)cx + 0.5) * leaf, oy = ((double)cy + 0.5) * leaf, oz = ((double)cz + 0.5) * leaf;
+  voxel_means[3 * (size_t)v] = (float)(ox + lx);
+  voxel_means[3 * (size_t)v + 1] = (float)(oy + ly);
+  voxel_means[3 * (size_t)v + 2] = (float)(oz + lz);
+  float* c = voxel_covs + 9 * (size_t)v;
+  c[0] = (float)rec.cov[0];
+  c[1] = c[3] = (float)rec.cov[1];
+  c[2] = c[6] = (float)rec.cov[2];
+  c[4] = (float)rec.cov[3];
+  c[5] = c[7] = (float)rec.cov[4];
+  c[8] = (float)rec.cov[5];
+  voxel_intensities[v] = imax;
+  voxel_coords[3 * (size_t)v] = cx;
+  voxel_coords[3 * (size_t)v + 1] = cy;
+  voxel_coords[3 * (size_t)v + 2] = cz;
 }
 
 }  // namespace gp

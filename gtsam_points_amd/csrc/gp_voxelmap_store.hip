@@ -170,6 +170,10 @@ int gp_voxelmap_assign(gp_voxelmap_t* m, int num_voxels, const int* coords, cons
     gp::sym6_to_full(covs6 + 6 * v, h_covs.data() + 9 * v);
     if (intensities) h_int[v] = intensities[v];
   }
+  if (m->has_sums) {  // (an incremental map is replaced like any other: gp_voxelmap_insert)
+    GP_HIP(hipDeviceSynchronize());
+    m->drop_incremental_state();
+  }
   m->info.num_voxels = num_voxels;
   m->info.num_buckets = (int)nb;
   m->offloaded = false;
@@ -306,6 +310,10 @@ int gp_voxelmap_clone_to_device(const gp_voxelmap_t* map, int device, gp_stream_
   m->plmask = map->plmask;
   m->has_grid = map->has_grid;
   m->grid = map->grid;
+  m->has_sums = map->has_sums;
+  m->lru_counter = map->lru_counter;
+  m->lru_horizon = map->lru_horizon;
+  m->lru_clear_cycle = map->lru_clear_cycle;
   int rc = GP_OK;
   auto copy = [&](gp::DeviceArray& dst, const gp::DeviceArray& src, size_t bytes) {
     if (rc != GP_OK) return;
@@ -336,7 +344,9 @@ size_t gp_voxelmap_memory_usage_gpu(const gp_voxelmap_t* map) {
   if (!map) return 0;
   // reference formula (gaussian_voxelmap_gpu.cu:469-472) + the gather records, coordinates and line table this implementation adds (not a sum over the table of
   // arrays: like the reference's, it leaves the intensities out)
-  return (size_t)map->info.num_voxels * (sizeof(int) + sizeof(float) * 3 + sizeof(float) * 9 + sizeof(gp::VoxelRecord) + sizeof(int) * 3) +
+  // (an incremental map's sums and stamps: their rows of the table)
+  return map->array_bytes(gp_voxelmap::kSums) + map->array_bytes(gp_voxelmap::kStamps) +
+         (size_t)map->info.num_voxels * (sizeof(int) + sizeof(float) * 3 + sizeof(float) * 9 + sizeof(gp::VoxelRecord) + sizeof(int) * 3) +
          (size_t)map->info.num_buckets * sizeof(gp_voxel_bucket) + (map->private_built ? ((size_t)map->plmask + 1) * 4 * sizeof(gp_voxel_bucket) : 0) +
          (map->has_grid ? (size_t)map->num_grid_blocks() * sizeof(gp::GridBlock) : 0);
 }

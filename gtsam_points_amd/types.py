@@ -382,6 +382,62 @@ class GaussianVoxelMapGPU(OffloadableGPU):
         return out.cpu().numpy()
 
 
+class IncrementalGaussianVoxelMapGPU(GaussianVoxelMapGPU):
+    """The sliding local map: a GaussianVoxelMapGPU whose insert() ADDS the frame to the voxels already there and evicts the least recently used ones --
+    GaussianVoxelMapCPU's insert (gaussian_voxelmap_cpu.cpp:23-47, ann/impl/incremental_voxelmap_impl.hpp:31-68), which the reference's GPU map lacks.
+    Every insert stamps the voxels it touches with lru_counter and increments it; every lru_clear_cycle-th insert drops the voxels with
+    stamp + lru_horizon < lru_counter.  Everything else -- lookup, overlap_gpu, the VGICP factor, the batches, the LM graph -- is the base class's."""
+
+    def __init__(self, resolution, lru_horizon=10, lru_clear_cycle=10, init_num_buckets=8192 * 2, max_bucket_scan_count=10, stream=None, _handle=None):
+        GaussianVoxelMapGPU.__init__(self, resolution, init_num_buckets, max_bucket_scan_count, 0.0, stream=stream, _handle=_handle)
+        if _handle is None:
+            _capi.check(self._lib.gp_voxelmap_set_lru(self._h, int(lru_horizon), int(lru_clear_cycle)), "gp_voxelmap_set_lru")
+
+    def insert(self, frame: PointCloudGPU):
+        n = frame.size()
+        if n > 0 and (frame.points_gpu is None or frame.covs_gpu is None):
+            raise _capi.GPError("error: GPU points/covs not allocated!!")
+        if n > 0:
+            self._sync_torch(frame)
+        _capi.check(
+            self._lib.gp_voxelmap_insert_incremental(self._h, frame.ptr(frame.points_gpu), frame.ptr(frame.covs_gpu), frame.ptr(frame.intensities_gpu), n),
+            "gp_voxelmap_insert_incremental",
+        )
+
+    def replace(self, frame: PointCloudGPU):
+        """the base class's one-shot insert: the map becomes the frame's alone and counts its inserts from zero again"""
+        GaussianVoxelMapGPU.insert(self, frame)
+
+    def _lru(self):
+        c, h, k = C.c_int64(), C.c_int64(), C.c_int64()
+        _capi.check(self._lib.gp_voxelmap_lru_get(self._h, C.byref(c), C.byref(h), C.byref(k)), "gp_voxelmap_lru_get")
+        return c.value, h.value, k.value
+
+    @property
+    def lru_counter(self):
+        return self._lru()[0]
+
+    @property
+    def lru_horizon(self):
+        return self._lru()[1]
+
+    @property
+    def lru_clear_cycle(self):
+        return self._lru()[2]
+
+    def set_lru_horizon(self, horizon):
+        _capi.check(self._lib.gp_voxelmap_set_lru(self._h, int(horizon), self._lru()[2]), "gp_voxelmap_set_lru")
+
+    def set_lru_clear_cycle(self, cycle):
+        _capi.check(self._lib.gp_voxelmap_set_lru(self._h, self._lru()[1], int(cycle)), "gp_voxelmap_set_lru")
+
+    def download_stamps(self):
+        """int64 (V,): the value of lru_counter at the insert that last touched each voxel, in the voxels' order"""
+        out = np.zeros(self.voxelmap_info.num_voxels, dtype=np.int64)
+        _capi.check(self._lib.gp_voxelmap_download_stamps(self._h, out.ctypes.data), "gp_voxelmap_download_stamps")
+        return out
+
+
 def _poses_flat(poses):
     return np.ascontiguousarray(np.stack([np.asarray(T, dtype=np.float64).T.reshape(16) for T in poses]))
 

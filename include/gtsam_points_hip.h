@@ -142,6 +142,21 @@ int gp_voxelmap_destroy(gp_voxelmap_t* map);
  * intensities_dev may be NULL (voxel intensities = 0, :232-240).  Returns when everything it issued on the map's stream has finished (a polled completion
  * flag behind the last kernel; a stream synchronisation when that takes longer than 0.5 ms).  The hashed kernel family's private line table is built on first use. */
 int gp_voxelmap_insert(gp_voxelmap_t* map, const float* points_dev, const float* covs_dev, const float* intensities_dev, int num_points);
+/* The INCREMENTAL insert with LRU eviction -- GaussianVoxelMapCPU::insert (gaussian_voxelmap_cpu.cpp:23-47), i.e. IncrementalVoxelMap<GaussianVoxel>::insert
+ * (ann/impl/incremental_voxelmap_impl.hpp:31-68); the reference's GPU map has none.  The frame's points are ADDED to the voxels the map holds (count, f64 sums,
+ * max intensity), the voxels it touches are stamped with the map's counter, the counter is incremented, and on every lru_clear_cycle-th call the voxels with
+ * stamp + lru_horizon < counter are dropped (with lru_horizon = 0 the ones just touched too); means and covariances are the sums over the counts.  An empty frame
+ * (num_points == 0: the arrays may be NULL) still counts and may evict.  Non-finite and out-of-range points are skipped as by gp_voxelmap_insert.
+ * The map starts empty (or as an incremental map): one that holds voxels built by gp_voxelmap_insert / _assign / _load is refused (GP_ERROR_INVALID_ARGUMENT), and so
+ * is a frame with which the map's box would exceed the block grid (2^24 blocks of 4x4x4 voxels) -- the map, its counter and its generation are unchanged then.
+ * gp_voxelmap_insert on an incremental map replaces it as on any other and resets the counter.  Deterministic: two maps fed the same frames hold the same bits.
+ * Factors built on the map notice the new contents through its generation, like after gp_voxelmap_insert. */
+int gp_voxelmap_insert_incremental(gp_voxelmap_t* map, const float* points_dev, const float* covs_dev, const float* intensities_dev, int num_points);
+/* lru_horizon >= 0 and lru_clear_cycle >= 1 (defaults 10 / 10, ann/incremental_voxelmap.hpp); the counter, the horizon and the cycle (any pointer may be NULL) */
+int gp_voxelmap_set_lru(gp_voxelmap_t* map, int64_t lru_horizon, int64_t lru_clear_cycle);
+int gp_voxelmap_lru_get(const gp_voxelmap_t* map, int64_t* lru_counter, int64_t* lru_horizon, int64_t* lru_clear_cycle);
+/* int64 out_host[num_voxels]: the counter value of the insert that last touched each voxel.  Refused for a map with voxels that took no incremental insert. */
+int gp_voxelmap_download_stamps(const gp_voxelmap_t* map, int64_t* out_host);
 int gp_voxelmap_info_get(const gp_voxelmap_t* map, gp_voxelmap_info* info);
 double gp_voxelmap_resolution(const gp_voxelmap_t* map);                       /* voxel_resolution() */
 int gp_voxelmap_views_get(const gp_voxelmap_t* map, gp_voxelmap_views* views);
