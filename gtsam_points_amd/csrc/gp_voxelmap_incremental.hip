@@ -6,14 +6,15 @@
 //      intensity = max(intensity, I), stamp = lru_counter; a voxel the frame does not touch keeps everything
 //   2. ++lru_counter; when lru_counter % lru_clear_cycle == 0 every voxel with stamp + lru_horizon < lru_counter goes (with lru_horizon = 0 the ones just touched too)
 //   3. mean = sum / count, cov = sum(cov) / count
-// as a VOXEL-LEVEL MERGE, O(old voxels + new points + blocks), with no per-point atomics (kernels: gp_voxelmap_kernels.hpp, "incremental insert"):
+// as a VOXEL-LEVEL MERGE, O(old voxels + new points + blocks), with no per-point atomics.  The unit holds the three kernels that only it launches (below); the bounding
+// box, the block grid and the bucket placement are gp_voxelmap.hip's, through the helpers of gp_voxelmap.hpp:
 //   bin_points + segmented_sums_kernel   the frame's distinct cells with their counts, f64 sums and intensities -- the binned build's lanes and summation order
 //   the union box                        of the surviving old voxels (the old grid's box; on a clearing call the box of the survivors, so that the grid follows the
 //                                        sliding map instead of growing along the whole trajectory) and of the frame's cells.  A box beyond kMaxGridBlocks is REFUSED
 //                                        (GP_ERROR_INVALID_ARGUMENT, map and counter untouched): a hashed fallback like the one-shot build's is not built here
-//   a fresh block grid                   bits from the survivors and the cells, counts, exclusive scan: the merged map's numbering is (block, bit) order
+//   a fresh block grid (build_block_grid) bits from the survivors and the cells, counts, exclusive scan: the merged map's numbering is (block, bit) order
 //   merge_source / merge_finalize        per merged voxel at most one old voxel and one cell: old + new in f64, then everything the map keeps of a voxel
-//   insert_voxels_kernel                 the reference-visible bucket table, along the binned build's doubling sequence
+//   place_voxels                         the reference-visible bucket table, along the binned build's doubling sequence
 // The sums are kept per voxel in f64 (gp_voxelmap::kSums) beside the stamps (kStamps); the f32 mean_local of the gather record is rounded from them once per insert,
 // so the rounding does not compound.  The new arrays are swapped in only when all of this has succeeded.
 // A map that holds voxels but no sums (built by insert, assign or load) is refused, not adopted.
@@ -21,10 +22,93 @@
 #include "gp_voxelmap.hpp"
 #include "gp_voxelmap_kernels.hpp"
 
-namespace {
+namespace gp {
 
-constexpr int kBlock = 256;
-inline int grid_for(size_t n) { return (int)((n + kBlock - 1) / kBlock); }
+// The frame is binned like a one-shot build's cloud; segmented_sums_kernel leaves each of its cells' count, f64 sums, intensity and coordinate.  The surviving old
+// voxels and the new cells mark their bits in a FRESH block grid over the union box; a voxel of the merged map is a set bit, numbered in (block, bit) order like
+// every map.  merge_source_kernel writes, per merged voxel, which old voxel and which new cell it is made of (-1: none); merge_finalize_kernel gathers the two, adds
+// old + new in f64 and emits everything the map keeps of a voxel.  No atomics on sums: two maps fed the same frames hold the same bits.
+
+// a source of the merge as merge_finalize_kernel gathers it: the old map's per-voxel arrays, or the frame's per-cell arrays (stamps == null)
+struct MergeSource {
+  const int* coords;
+  const int* counts;
+  const double* sums;
+  const float* intensities;
+  const long long* stamps;
+};
+
+// the sums of the frame's cells, as segmented_stats_kernel forms them (same lanes, same order), not finalized
+__global__ void __launch_bounds__(256) segmented_sums_kernel(const float* __restrict__ points, const float* __restrict__ covs, const float* __restrict__ intensities,
+                                                             int num_cells, const int* __restrict__ cell_start, const int* __restrict__ order, double inv_leaf, double leaf,
+                                                             int* __restrict__ cell_counts, double* __restrict__ cell_sums, float* __restrict__ cell_intensities,
+                                                             int* __restrict__ cell_coords) {
+  SegmentSums sum;
+  if (!segmented_sums(points, covs, intensities, num_cells, cell_start, order, inv_leaf, leaf, sum)) return;
+  const size_t c = (size_t)sum.v;
+  cell_counts[c] = sum.n;
+#pragma unroll
+  for (int k = 0; k < 9; k++) cell_sums[9 * c + k] = sum.acc[k];
+  cell_intensities[c] = sum.imax;
+  cell_coords[3 * c] = sum.cx;
+  cell_coords[3 * c + 1] = sum.cy;
+  cell_coords[3 * c + 2] = sum.cz;
+}
+
+// source[new index] = v for every old voxel (or new cell) v whose bit is set in the new grid.  For an old voxel that is: it survived by its stamp, or the frame
+// touches it (the cell set the bit) -- exactly the voxels the reference keeps, whose stamp of a touched voxel is the current counter.  An evicted voxel may lie
+// outside the new box
+__global__ void __launch_bounds__(256) merge_source_kernel(int num, const int* __restrict__ coords, GridGeom g, const GridBlock* __restrict__ blocks,
+                                                           int* __restrict__ source) {
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= num) return;
+  const int cx = coords[3 * (size_t)v], cy = coords[3 * (size_t)v + 1], cz = coords[3 * (size_t)v + 2];
+  if (!grid_contains(g, cx, cy, cz)) return;
+  const int nv = grid_ordinal(g, blocks, cx, cy, cz);
+  if (nv >= 0) source[nv] = v;
+}
+
+// one thread per voxel of the merged map: old + new in f64 (a voxel of one source alone keeps that source's sums to the bit), then the one-shot build's emit
+__global__ void __launch_bounds__(256) merge_finalize_kernel(int num_voxels, const int* __restrict__ source_old, const int* __restrict__ source_new, MergeSource old,
+                                                             MergeSource cell, long long stamp_now, double leaf, double* __restrict__ sums,
+                                                             long long* __restrict__ stamps, VoxelOutputs out, const gp::FillJob fill_buckets) {
+  gp::run_fill_job(fill_buckets);  // (the bucket table insert_voxels_kernel claims its slots in behind this kernel: 0xff = empty)
+  const int v = blockIdx.x * blockDim.x + threadIdx.x;
+  if (v >= num_voxels) return;
+  const int so = source_old[v], sn = source_new[v];  // at least one of the two is a source: the bit was set by one of them
+  double acc[9];
+  int n = 0, cx = 0, cy = 0, cz = 0;
+  float imax = 0.0f;
+  long long stamp = stamp_now;
+  if (so >= 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) acc[k] = old.sums[9 * (size_t)so + k];
+    n = old.counts[so];
+    imax = old.intensities[so];
+    stamp = old.stamps[so];
+    cx = old.coords[3 * (size_t)so], cy = old.coords[3 * (size_t)so + 1], cz = old.coords[3 * (size_t)so + 2];
+  }
+  if (sn >= 0) {
+#pragma unroll
+    for (int k = 0; k < 9; k++) {
+      const double x = cell.sums[9 * (size_t)sn + k];
+      acc[k] = so >= 0 ? acc[k] + x : x;
+    }
+    n += cell.counts[sn];
+    imax = intensity_max(imax, cell.intensities[sn]);
+    stamp = stamp_now;
+    cx = cell.coords[3 * (size_t)sn], cy = cell.coords[3 * (size_t)sn + 1], cz = cell.coords[3 * (size_t)sn + 2];
+  }
+  if (so < 0 && sn < 0) return;  // (cannot happen; nothing is written from undefined sums)
+#pragma unroll
+  for (int k = 0; k < 9; k++) sums[9 * (size_t)v + k] = acc[k];
+  stamps[v] = stamp;
+  emit_voxel(out, v, n, acc, imax, cx, cy, cz, voxel_centre(cx, leaf), voxel_centre(cy, leaf), voxel_centre(cz, leaf));
+}
+
+}  // namespace gp
+
+namespace {
 
 // the device is idle on `s` before the scratch of a failed insert goes back to the pool (declared behind the arrays it guards)
 struct DrainOnFailure {
@@ -68,7 +152,7 @@ int gp_voxelmap_insert_incremental(gp_voxelmap_t* m, const float* points_dev, co
 
   gp::PointBins bins;
   gp::DeviceArray cell_counts, cell_sums, cell_intensities, cell_coords, box_dev, scratch, source_old, source_new, blocks;
-  gp::DeviceArray fresh[gp_voxelmap::kGblocks];  // the merged map's rows of the table (kGblocks: `blocks`)
+  gp_voxelmap::Array fresh[gp_voxelmap::kGblocks];  // the merged map's rows of the table (kGblocks: `blocks`)
   DrainOnFailure drain{s};
 
   // ---- the frame's cells ----
@@ -86,14 +170,10 @@ int gp_voxelmap_insert_incremental(gp_voxelmap_t* m, const float* points_dev, co
   int box[6];
   gp::empty_bbox(box);
   if (old_live && !evict) join_box(box, m->grid);  // (a map with voxels and sums was built here: it has its grid)
+  const gp::VoxelSet old_voxels{old_live ? V_old : 0, m->voxel_coords.as<int>(), m->voxel_stamps.as<long long>(), evict, horizon, counter};
   if (old_live && evict) {
     GP_TRY(box_dev.alloc_async(sizeof(box), s));
-    GP_HIP(hipMemcpyAsync(box_dev.ptr, box, sizeof(box), hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL(gp::survivors_bbox_kernel, dim3(grid_for(V_old)), dim3(kBlock), 0, s, V_old, (const int*)m->voxel_coords.as<int>(),
-                       (const long long*)m->voxel_stamps.as<long long>(), horizon, counter, box_dev.as<int>());
-    GP_HIP(hipGetLastError());
-    GP_HIP(hipMemcpyAsync(box, box_dev.ptr, sizeof(box), hipMemcpyDeviceToHost, s));
-    GP_HIP(hipStreamSynchronize(s));
+    GP_TRY(gp::voxels_bbox(old_voxels, box_dev.as<int>(), box, s));
   }
   if (C > 0) join_box(box, bins.geom);
   const bool any = box[0] <= box[3];
@@ -101,8 +181,6 @@ int gp_voxelmap_insert_incremental(gp_voxelmap_t* m, const float* points_dev, co
   long long nb = 0;
   if (any && !gp::grid_geometry(box, &g, &nb)) return refuse_box();
 
-  gp::HostWords hw;
-  GP_TRY(gp::HostWords::get(&hw));
   int V = 0;
   if (any) {
     // ---- the frame's sums per cell ----
@@ -116,25 +194,14 @@ int gp_voxelmap_insert_incremental(gp_voxelmap_t* m, const float* points_dev, co
                          cell_coords.as<int>());
       GP_HIP(hipGetLastError());
     }
-    // ---- a fresh block grid over the union box: bits, counts, scan ----
+    // ---- a fresh block grid over the union box: bits of the survivors and of the cells, counts, scan ----
     GP_TRY(blocks.alloc_pooled(sizeof(gp::GridBlock) * (size_t)nb, s));
-    GP_HIP(hipMemsetAsync(blocks.ptr, 0, sizeof(gp::GridBlock) * (size_t)nb, s));
-    if (old_live) {
-      hipLaunchKernelGGL(gp::grid_mark_survivors_kernel, dim3(grid_for(V_old)), dim3(kBlock), 0, s, V_old, (const int*)m->voxel_coords.as<int>(),
-                         (const long long*)m->voxel_stamps.as<long long>(), evict, horizon, counter, g, blocks.as<gp::GridBlock>());
-      GP_HIP(hipGetLastError());
-    }
-    if (C > 0) {
-      hipLaunchKernelGGL(gp::grid_mark_survivors_kernel, dim3(grid_for(C)), dim3(kBlock), 0, s, C, (const int*)cell_coords.as<int>(), (const long long*)nullptr, 0, horizon,
-                         counter, g, blocks.as<gp::GridBlock>());
-      GP_HIP(hipGetLastError());
-    }
-    hipLaunchKernelGGL(gp::grid_count_kernel, dim3(grid_for((size_t)nb)), dim3(kBlock), 0, s, nb, blocks.as<gp::GridBlock>());
-    GP_HIP(hipGetLastError());
     GP_TRY(scratch.alloc_async(sizeof(int) * gp::scan_scratch_ints(nb), s));
-    int* base0 = &blocks.as<gp::GridBlock>()[0].base;
-    GP_TRY(gp::exclusive_scan_strided(base0, 4, base0, 4, nb, scratch.as<int>(), s));
+    const gp::VoxelSet sets[2] = {old_voxels, {C, cell_coords.as<int>(), nullptr, 0, 0, 0}};
+    GP_TRY(gp::build_block_grid(g, nb, blocks.as<gp::GridBlock>(), scratch.as<int>(), sets, 2, s));
     // (the scan leaves its grand total, the merged map's voxel count, behind its block sums: gp_scan.hpp)
+    gp::HostWords hw;
+    GP_TRY(gp::HostWords::get(&hw));
     GP_TRY(hw.finish(s, scratch.as<int>() + (nb + gp::kScanThreads - 1) / gp::kScanThreads, 13));
     V = reinterpret_cast<volatile int*>(hw.host)[13];
     if (V <= 0 || V > V_old + C) return gp::fail(GP_ERROR_HIP, "gp_voxelmap_insert_incremental: the merged grid holds an impossible number of voxels");
@@ -142,71 +209,51 @@ int gp_voxelmap_insert_incremental(gp_voxelmap_t* m, const float* points_dev, co
 
   // ---- the merged map's arrays ----
   const size_t Vz = (size_t)V;
-  GP_TRY(fresh[gp_voxelmap::kRecords].alloc_pooled(sizeof(gp::VoxelRecord) * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kNumPoints].alloc_pooled(sizeof(int) * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kMeans].alloc_pooled(sizeof(float) * 3 * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kCovs].alloc_pooled(sizeof(float) * 9 * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kIntensities].alloc_pooled(sizeof(float) * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kCoords].alloc_pooled(sizeof(int) * 3 * std::max<size_t>(Vz, 1), s));
-  GP_TRY(fresh[gp_voxelmap::kSums].alloc_pooled(sizeof(double) * 9 * Vz, s));
-  GP_TRY(fresh[gp_voxelmap::kStamps].alloc_pooled(sizeof(long long) * Vz, s));
-  // the bucket table enters the doubling sequence where the binned build does (gp_voxelmap.hip, insert_binned)
-  int64_t num_buckets = m->init_num_buckets;
-  while (num_buckets * (int64_t)m->bucket_load_percent < 100 * (int64_t)V) num_buckets *= 2;
+  GP_TRY(fresh[gp_voxelmap::kRecords].dev.alloc_pooled(sizeof(gp::VoxelRecord) * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kNumPoints].dev.alloc_pooled(sizeof(int) * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kMeans].dev.alloc_pooled(sizeof(float) * 3 * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kCovs].dev.alloc_pooled(sizeof(float) * 9 * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kIntensities].dev.alloc_pooled(sizeof(float) * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kCoords].dev.alloc_pooled(sizeof(int) * 3 * std::max<size_t>(Vz, 1), s));
+  GP_TRY(fresh[gp_voxelmap::kSums].dev.alloc_pooled(sizeof(double) * 9 * Vz, s));
+  GP_TRY(fresh[gp_voxelmap::kStamps].dev.alloc_pooled(sizeof(long long) * Vz, s));
+  // the bucket table enters the doubling sequence where the binned build does; its first table is filled with "empty" by merge_finalize_kernel on its way
+  int64_t num_buckets = gp::entry_bucket_count(m->init_num_buckets, m->bucket_load_percent, V);
   if (num_buckets > gp::kMaxBuckets) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_insert_incremental: bucket table would exceed 2^30 entries");
-  gp::DeviceArray& buckets = fresh[gp_voxelmap::kBuckets];
+  gp::DeviceArray& buckets = fresh[gp_voxelmap::kBuckets].dev;
   GP_TRY(buckets.alloc_pooled(sizeof(gp_voxel_bucket) * (size_t)num_buckets, s));
+  const gp::VoxelOutputs out = gp::voxel_outputs(fresh);
   if (V > 0) {
     GP_TRY(source_old.alloc_async(sizeof(int) * Vz, s));
     GP_TRY(source_new.alloc_async(sizeof(int) * Vz, s));
     GP_HIP(hipMemsetAsync(source_old.ptr, 0xff, sizeof(int) * Vz, s));
     GP_HIP(hipMemsetAsync(source_new.ptr, 0xff, sizeof(int) * Vz, s));
+    const gp::MergeSource old{m->voxel_coords.as<int>(), m->num_points.as<int>(), m->voxel_sums.as<double>(), m->voxel_intensities.as<float>(), m->voxel_stamps.as<long long>()};
+    const gp::MergeSource cell{cell_coords.as<int>(), cell_counts.as<int>(), cell_sums.as<double>(), cell_intensities.as<float>(), nullptr};
     if (old_live) {
-      hipLaunchKernelGGL(gp::merge_source_kernel, dim3(grid_for(V_old)), dim3(kBlock), 0, s, V_old, (const int*)m->voxel_coords.as<int>(), g,
-                         (const gp::GridBlock*)blocks.as<gp::GridBlock>(), source_old.as<int>());
+      hipLaunchKernelGGL(gp::merge_source_kernel, dim3(gp::blocks_of(V_old)), dim3(256), 0, s, V_old, old.coords, g, (const gp::GridBlock*)blocks.as<gp::GridBlock>(),
+                         source_old.as<int>());
       GP_HIP(hipGetLastError());
     }
     if (C > 0) {
-      hipLaunchKernelGGL(gp::merge_source_kernel, dim3(grid_for(C)), dim3(kBlock), 0, s, C, (const int*)cell_coords.as<int>(), g,
-                         (const gp::GridBlock*)blocks.as<gp::GridBlock>(), source_new.as<int>());
+      hipLaunchKernelGGL(gp::merge_source_kernel, dim3(gp::blocks_of(C)), dim3(256), 0, s, C, cell.coords, g, (const gp::GridBlock*)blocks.as<gp::GridBlock>(),
+                         source_new.as<int>());
       GP_HIP(hipGetLastError());
     }
-    const gp::MergeOld old{m->voxel_coords.as<int>(), m->num_points.as<int>(), m->voxel_sums.as<double>(), m->voxel_stamps.as<long long>(), m->voxel_intensities.as<float>()};
-    const gp::MergeNew cell{cell_coords.as<int>(), cell_counts.as<int>(), cell_sums.as<double>(), cell_intensities.as<float>()};
-    hipLaunchKernelGGL(gp::merge_finalize_kernel, dim3(grid_for(Vz)), dim3(kBlock), 0, s, V, (const int*)source_old.as<int>(), (const int*)source_new.as<int>(), old, cell,
-                       stamp_now, m->resolution, fresh[gp_voxelmap::kSums].as<double>(), fresh[gp_voxelmap::kStamps].as<long long>(),
-                       fresh[gp_voxelmap::kRecords].as<gp::VoxelRecord>(), fresh[gp_voxelmap::kNumPoints].as<int>(), fresh[gp_voxelmap::kMeans].as<float>(),
-                       fresh[gp_voxelmap::kCovs].as<float>(), fresh[gp_voxelmap::kIntensities].as<float>(), fresh[gp_voxelmap::kCoords].as<int>(),
+    hipLaunchKernelGGL(gp::merge_finalize_kernel, dim3(gp::blocks_of(Vz)), dim3(256), 0, s, V, (const int*)source_old.as<int>(), (const int*)source_new.as<int>(), old, cell,
+                       stamp_now, m->resolution, fresh[gp_voxelmap::kSums].dev.as<double>(), fresh[gp_voxelmap::kStamps].dev.as<long long>(), out,
                        gp::fill_job(buckets.ptr, sizeof(gp_voxel_bucket) * (size_t)num_buckets, 0xffffffffu));
     GP_HIP(hipGetLastError());
-  } else {
-    GP_HIP(hipMemsetAsync(buckets.ptr, 0xff, sizeof(gp_voxel_bucket) * (size_t)num_buckets, s));
   }
-  // the table is doubled until every voxel is placed, as in the binned build: no voxel is ever dropped
-  for (bool first = true;; num_buckets *= 2, first = false) {
-    if (!first) {  // (a table that turned out too small: the rare path)
-      if (num_buckets > gp::kMaxBuckets) return gp::fail(GP_ERROR_INVALID_ARGUMENT, "gp_voxelmap_insert_incremental: bucket table would exceed 2^30 entries");
-      GP_HIP(hipStreamSynchronize(s));  // (the table let go of here is the one the failed attempt wrote)
-      GP_TRY(buckets.alloc_pooled(sizeof(gp_voxel_bucket) * (size_t)num_buckets, s));
-      GP_HIP(hipMemsetAsync(buckets.ptr, 0xff, sizeof(gp_voxel_bucket) * (size_t)num_buckets, s));
-    }
-    reinterpret_cast<volatile int*>(hw.host)[12] = 0;
-    if (V > 0) {
-      hipLaunchKernelGGL(gp::insert_voxels_kernel, dim3(grid_for(Vz)), dim3(kBlock), 0, s, V, (const int*)fresh[gp_voxelmap::kCoords].as<int>(),
-                         (const int*)fresh[gp_voxelmap::kNumPoints].as<int>(), buckets.as<gp_voxel_bucket>(), (uint32_t)num_buckets, gp::pow2_mask(num_buckets),
-                         m->info.max_bucket_scan_count, hw.dev + 12);
-      GP_HIP(hipGetLastError());
-    }
-    GP_TRY(hw.finish(s));
-    if (reinterpret_cast<volatile int*>(hw.host)[12] == 0) break;
-  }
+  // `buckets` and the count stay local until everything has succeeded: the map is untouched otherwise
+  GP_TRY(gp::place_voxels("gp_voxelmap_insert_incremental", out.coords, out.num_points, V, buckets, &num_buckets, m->info.max_bucket_scan_count, V > 0, s));
   GP_HIP(hipStreamSynchronize(s));  // (the flag says the results are there; the old arrays and the scratch go back to the pool behind the kernels themselves)
   drain.armed = false;
 
   // ---- success: the merged map replaces the old one ----
   // the old arrays go back to the block cache ("any stream may take them"): kernels of other streams that still read the old map must have finished, as for a re-insert
   if (m->buckets.ptr) GP_HIP(hipDeviceSynchronize());
-  for (int id = 0; id < gp_voxelmap::kGblocks; id++) m->arrays[id].dev.swap(fresh[id]);
+  for (int id = 0; id < gp_voxelmap::kGblocks; id++) m->arrays[id].dev.swap(fresh[id].dev);
   m->gblocks.swap(blocks);
   m->grid = g;
   m->has_grid = V > 0;

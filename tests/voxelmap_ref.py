@@ -35,6 +35,42 @@ FACE_RESOLUTIONS = (0.5, 0.1, 0.3, 1e-3, 100.0)
 FAR_DISTANCES = (0.0, 1e2, 1e3, 1e4, 1e5)
 
 
+def coord_hash(coord):
+    """vector3i_hash of cuda/kernels/vector3_hash.cuh:14-39 (csrc/gp_device.hpp coord_hash): boost-style hash_combine of the three sign-extended coordinates in uint64"""
+    M, mask = 0xC6A4A7935BD1E995, (1 << 64) - 1
+    h = 0
+    for c in coord:
+        k = ((int(c) & mask) * M) & mask
+        k ^= k >> 47
+        k = (k * M) & mask
+        h = (((h ^ k) * M) & mask) + 0xE6546B64 & mask
+    return h
+
+
+def entry_bucket_count(init_num_buckets, num_voxels, load_percent=33):
+    """csrc/gp_voxelmap.hip entry_bucket_count: where the binned build and the incremental insert enter the doubling sequence of the bucket table"""
+    n = init_num_buckets
+    while n * load_percent < 100 * num_voxels:
+        n *= 2
+    return n
+
+
+def buckets_can_place(coords, num_buckets, max_scan):
+    """insert_voxels_kernel's claim in any order: with max_scan == 1 every voxel has ONE bucket, so the table holds them iff their home buckets are distinct; for longer
+    chains a greedy first-fit in list order (the device's order is not fixed, so only max_scan == 1 is order-free: the callers use that)"""
+    taken = set()
+    for c in coords:
+        h = coord_hash(c)
+        for i in range(max_scan):
+            b = ((h + i) & ((1 << 64) - 1)) % num_buckets
+            if b not in taken:
+                taken.add(b)
+                break
+        else:
+            return False
+    return True
+
+
 def fast_floor(x):
     """fast_floor.hpp:13-14 on an f64 array -> int64"""
     x = np.asarray(x, dtype=np.float64)
