@@ -57,13 +57,6 @@ __device__ __forceinline__ void ba_point(const BaView& v, const double* __restri
   for (int r = 0; r < 3; r++) q[r] = P[r] * x + P[4 + r] * y + P[8 + r] * z + P[12 + r];
 }
 
-// the sum over the wave, the same bits in every lane (a butterfly: both partners add the same two operands)
-__device__ __forceinline__ double ba_wave_sum(double v) {
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-  return v;
-}
-
 // one Jacobi rotation of the symmetric 3x3 in the (p, q) plane; r is the third index
 __device__ __forceinline__ void ba_jacobi_rotate(double& app, double& aqq, double& apq, double& arp, double& arq, double* __restrict__ vp, double* __restrict__ vq) {
   if (apq == 0.0) return;
@@ -135,7 +128,7 @@ __global__ void __launch_bounds__(64) ba_feature_kernel(BaView v, const double* 
     ba_point(v, poses, i, q);
     s0 += q[0] - c0[0], s1 += q[1] - c0[1], s2 += q[2] - c0[2];
   }
-  const double mean[3] = {c0[0] + ba_wave_sum(s0) / N, c0[1] + ba_wave_sum(s1) / N, c0[2] + ba_wave_sum(s2) / N};
+  const double mean[3] = {c0[0] + wave_sum(s0) / N, c0[1] + wave_sum(s1) / N, c0[2] + wave_sum(s2) / N};
   // the centred second moments
   double m00 = 0.0, m01 = 0.0, m02 = 0.0, m11 = 0.0, m12 = 0.0, m22 = 0.0;
   for (int i = begin + lane; i < end; i += 64) {
@@ -144,7 +137,7 @@ __global__ void __launch_bounds__(64) ba_feature_kernel(BaView v, const double* 
     m00 += d0 * d0, m01 += d0 * d1, m02 += d0 * d2, m11 += d1 * d1, m12 += d1 * d2, m22 += d2 * d2;
   }
   double l[3], u0[3], u1[3], u2[3];
-  ba_eig3(ba_wave_sum(m00) / N, ba_wave_sum(m01) / N, ba_wave_sum(m02) / N, ba_wave_sum(m11) / N, ba_wave_sum(m12) / N, ba_wave_sum(m22) / N, l, u0, u1, u2);
+  ba_eig3(wave_sum(m00) / N, wave_sum(m01) / N, wave_sum(m02) / N, wave_sum(m11) / N, wave_sum(m12) / N, wave_sum(m22) / N, l, u0, u1, u2);
   const bool edge = v.kinds[f] == GP_BA_EDGE;
   const double scale = edge ? 1.0 : v.scales[f];  // (EdgeEVMFactor ignores error_scale)
   const double fval = edge ? l[0] + l[1] : scale * l[0];

@@ -12,27 +12,17 @@ namespace {
 
 constexpr unsigned kNoCell = 0x7fffffffu;  // cell_of[] of a skipped (non-finite) point
 
-__device__ __forceinline__ bool point_cell(const float* __restrict__ points, size_t i, double inv_cell, int& cx, int& cy, int& cz) {
-  const float x = points[3 * i], y = points[3 * i + 1], z = points[3 * i + 2];
-  const double ux = (double)x * inv_cell, uy = (double)y * inv_cell, uz = (double)z * inv_cell;
-  // finite and inside the range a 32-bit cell coordinate can hold (with room for the >> 2 block arithmetic)
-  const bool ok = fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9;  // false for NaN / inf
-  cx = ok ? fast_floor(ux) : 0;
-  cy = ok ? fast_floor(uy) : 0;
-  cz = ok ? fast_floor(uz) : 0;
-  return ok;
-}
-
 // bounding box (block units) of the finite points.  ONE kernel, reduced by the HOST: a workgroup reduces its tiles of 4096 points (the sixteen loads of a thread in
 // flight together; at most HostSlots::kSlots workgroups, which stride over the tiles) and leaves {min xyz, max xyz, -, seq} in its 32-byte slot of host-mapped memory,
 // the sequence number stored behind the box; the host combines the slots as they arrive.  A workgroup without a finite point leaves the neutral box.
+// (The cell rule, the box, its reduce and the record: gp_cells.hpp.)
 // (Tried before: the boxes folded into six device words with atomicMax and the last workgroup by ticket writing the result -- 488 atomics on one address are served one
 // after the other, 16 us; then per-workgroup boxes + a one-workgroup reduce kernel, 10 us of which ~6 are the second kernel's boundary.)
 constexpr int kBboxTile = 4096;
 __global__ void __launch_bounds__(256) bins_bbox_kernel(const float* __restrict__ points, int n, double inv_cell, int* __restrict__ slots /* host-mapped */, int seq,
                                                         const FillJob zero_states) {
   run_fill_job(zero_states);  // (the state words of the kernels behind: gp_host.hpp, FillJob)
-  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  CellBox box;
   const size_t tiles = ((size_t)n + kBboxTile - 1) / kBboxTile;
   for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
     const size_t base = tile * kBboxTile;
@@ -45,45 +35,16 @@ __global__ void __launch_bounds__(256) bins_bbox_kernel(const float* __restrict_
     }
 #pragma unroll
     for (int r = 0; r < kBboxTile / 256; r++) {
-      const double ux = (double)p[r][0] * inv_cell, uy = (double)p[r][1] * inv_cell, uz = (double)p[r][2] * inv_cell;
-      const bool ok = fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9;  // (point_cell's rule)
-      const int c[3] = {fast_floor(ux) >> 2, fast_floor(uy) >> 2, fast_floor(uz) >> 2};
+      int c[3];
+      const bool ok = cell_of((double)p[r][0], (double)p[r][1], (double)p[r][2], inv_cell, c[0], c[1], c[2]);
 #pragma unroll
-      for (int a = 0; a < 3; a++) {
-        lo[a] = ok ? min(lo[a], c[a]) : lo[a];
-        hi[a] = ok ? max(hi[a], c[a]) : hi[a];
-      }
+      for (int a = 0; a < 3; a++) c[a] >>= 2;
+      if (ok) box.add(c);
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
-    }
   __shared__ int wave_box[4][6];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      wave_box[threadIdx.x >> 6][a] = lo[a];
-      wave_box[threadIdx.x >> 6][3 + a] = hi[a];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int v[6];
-#pragma unroll
-    for (int a = 0; a < 6; a++) {
-      v[a] = wave_box[0][a];
-#pragma unroll
-      for (int w = 1; w < 4; w++) v[a] = a < 3 ? min(v[a], wave_box[w][a]) : max(v[a], wave_box[w][a]);
-    }
-    int4* slot = reinterpret_cast<int4*>(slots + 8 * (size_t)blockIdx.x);
-    slot[0] = make_int4(v[0], v[1], v[2], v[3]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first half is in host memory before the half that carries the sequence number
-    slot[1] = make_int4(v[4], v[5], 0, seq);
-  }
+  box.block_reduce(wave_box);
+  if (threadIdx.x == 0) box.publish(slots, 0, seq);
 }
 
 // sort key of a point: (block index, bit inside the block) -- the order the cells are numbered in.  < 2^24 * 64 = 2^30.  The kernel also counts the keys' digits for
@@ -111,9 +72,8 @@ __global__ void __launch_bounds__(256) bins_key_kernel(const float* __restrict__
 #pragma unroll
     for (int r = 0; r < 8; r++) {
       const size_t i = base + (size_t)(half * 8 + r) * 256 + threadIdx.x;
-      const double ux = (double)p[r][0] * inv_cell, uy = (double)p[r][1] * inv_cell, uz = (double)p[r][2] * inv_cell;
-      const bool ok = fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9;  // (point_cell's rule)
-      const int cx = fast_floor(ux), cy = fast_floor(uy), cz = fast_floor(uz);
+      int cx, cy, cz;
+      const bool ok = cell_of((double)p[r][0], (double)p[r][1], (double)p[r][2], inv_cell, cx, cy, cz);
       const unsigned key = ok ? (unsigned)(grid_block_index(g, cx, cy, cz) * 64 + grid_bit(cx, cy, cz)) : invalid_key;
       if (i < (size_t)n) {
         keys[i] = key;
@@ -181,17 +141,15 @@ __device__ __forceinline__ void load_cell_keys(const unsigned* __restrict__ sort
 }
 
 __global__ void __launch_bounds__(256) bins_count_kernel(const unsigned* __restrict__ sorted_keys, int n, unsigned invalid_key, unsigned long long* __restrict__ state, int num_groups) {
-  __shared__ unsigned long long wave_sum[4];
+  __shared__ unsigned long long wave_total[4];
   const int tile = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   CellKeys c;
   load_cell_keys(sorted_keys, n, (long long)tile * kCellsTile + (long long)threadIdx.x * kCellsPerThread, invalid_key, c);
-  unsigned long long sum = (unsigned long long)__popc(c.cflag) | ((unsigned long long)__popc(c.bflag) << 31);
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) sum += __shfl_xor(sum, off, 64);
-  if (lane == 0) wave_sum[wave] = sum;
+  const unsigned long long sum = wave_sum((unsigned long long)__popc(c.cflag) | ((unsigned long long)__popc(c.bflag) << 31));
+  if (lane == 0) wave_total[wave] = sum;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const unsigned long long total = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+    const unsigned long long total = wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
     state[num_groups + tile] = total;
     if (total) atomicAdd(state + tile / kCellsGroup, total);  // (integer sum of <= 32 tiles: the order does not matter)
   }
@@ -201,7 +159,7 @@ __global__ void __launch_bounds__(256) bins_cells_kernel(const unsigned* __restr
                                                          GridBlock* __restrict__ blocks, int* __restrict__ cell_start, unsigned* __restrict__ cell_of, int* __restrict__ cell_block,
                                                          int* __restrict__ occ_blocks, int* __restrict__ host_counts /* host-mapped */, int seq,
                                                          const unsigned* __restrict__ sort_state, unsigned sort_pass_words, int sort_passes) {
-  __shared__ unsigned long long wave_sum[4];
+  __shared__ unsigned long long wave_total[4];
   __shared__ unsigned long long tile_prefix;
   const int tile = blockIdx.x;
   // A sort pass that gave up a wait (gp_sort.hpp, draw_tile) voids this build: its output has holes -- whatever the pooled buffer held -- and NOTHING may be indexed with
@@ -227,9 +185,7 @@ __global__ void __launch_bounds__(256) bins_cells_kernel(const unsigned* __restr
       const int e = e0 + lane;
       unsigned long long w = 0;
       if (e < entries) w = e < group ? state[e] : state[num_groups + (size_t)group * kCellsGroup + (e - group)];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) w += __shfl_xor(w, off, 64);
-      prefix += w;
+      prefix += wave_sum(w);
     }
   }
   CellKeys ck;
@@ -244,14 +200,14 @@ __global__ void __launch_bounds__(256) bins_cells_kernel(const unsigned* __restr
     const unsigned long long t = __shfl_up(incl, off, 64);
     if (lane >= off) incl += t;
   }
-  if (lane == 63) wave_sum[wave] = incl;
+  if (lane == 63) wave_total[wave] = incl;
   if (threadIdx.x == 0) tile_prefix = prefix;
   __syncthreads();
   GP_SORT_STAMP(tile, 1);  // keys loaded, flags counted, prefix known
   unsigned long long wave_excl = 0;
 #pragma unroll
   for (int w = 0; w < 4; w++)
-    if (w < wave) wave_excl += wave_sum[w];
+    if (w < wave) wave_excl += wave_total[w];
   GP_SORT_STAMP(tile, 2);
   if (!any) return;
   const unsigned long long excl = tile_prefix + wave_excl + incl - mine;
@@ -366,13 +322,8 @@ int bin_points_once(const float* points_dev, int n, double inv_cell, hipStream_t
   GP_TRY(bins->cell_block.alloc_pooled(sizeof(int) * (size_t)n, s));
   GP_TRY(bins->occ_blocks.alloc_pooled(sizeof(int) * (size_t)n, s));  // at most one block per cell
   // the host combines the workgroups' boxes as they arrive (bounded spin, then the stream -- which also surfaces a failed kernel)
-  int h_bbox[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  GP_TRY(slots.collect(box_wgs, seq_box, s, "bin_points", [&](const volatile int* box) {
-    for (int a = 0; a < 3; a++) {
-      h_bbox[a] = std::min(h_bbox[a], (int)box[a]);
-      h_bbox[3 + a] = std::max(h_bbox[3 + a], (int)box[3 + a]);
-    }
-  }));
+  int h_bbox[6];
+  GP_TRY(collect_boxes(slots, box_wgs, seq_box, s, "bin_points", h_bbox, nullptr));
   if (h_bbox[0] > h_bbox[3]) {  // no finite point at all
     GP_TRY(bins->cell_start.alloc_pooled(sizeof(int), s));
     GP_HIP(hipMemsetAsync(bins->cell_start.ptr, 0, sizeof(int), s));

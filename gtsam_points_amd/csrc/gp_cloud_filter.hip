@@ -17,12 +17,7 @@ __device__ __forceinline__ void stat_reduce(double sum, double sq, int count, do
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   __shared__ double lds[4][2];
   __shared__ int lds_count[4];
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-    sum += __shfl_xor(sum, off, 64);
-    sq += __shfl_xor(sq, off, 64);
-    count += __shfl_xor(count, off, 64);
-  }
+  sum = wave_sum(sum), sq = wave_sum(sq), count = wave_sum(count);
   if (lane == 0) lds[wave][0] = sum, lds[wave][1] = sq, lds_count[wave] = count;
   __syncthreads();
   if (threadIdx.x < 2) out_sums[threadIdx.x] = (lds[0][threadIdx.x] + lds[1][threadIdx.x]) + (lds[2][threadIdx.x] + lds[3][threadIdx.x]);

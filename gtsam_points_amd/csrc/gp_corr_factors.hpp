@@ -218,9 +218,7 @@ __device__ __forceinline__ void store_tile_sums_row(double* acc, double* __restr
   } else {
 #pragma unroll
     for (int k = 0; k < NACC; k++) {
-      double v = acc[k];
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+      const double v = wave_sum(acc[k]);
       if (lane == 0) lds[wave][k] = v;
     }
   }

@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "../../include/gtsam_points_hip.h"
+#include "gp_cells.hpp"
 
 namespace gp {
 
@@ -130,8 +131,7 @@ __host__ __device__ __forceinline__ uint32_t coord_hash32(int x, int y, int z) {
   return h;
 }
 
-// fast_floor in DOUBLE, util/fast_floor.hpp:12-15 (the CPU map's rule; the reference GPU map floors
-// float(x)/float(res), vector3_hash.cuh:41-50, which flips ~5e-5 of points across voxel faces)
+// (fast_floor, util/fast_floor.hpp:12-15, is gp_cells.hpp's, with the cell rule it serves)
 // LiDAR clouds carry NaN / inf returns.  A non-finite coordinate has no voxel (the reference floors it into an undefined integer that no
 // table holds); on the device the float -> int conversion of a NaN is 0, i.e. voxel (0, 0, 0), which may well exist: every lookup of a
 // transformed point is guarded with one of these, so that such a point contributes nothing (no correspondence, not an inlier, no overlap)
@@ -144,9 +144,13 @@ __host__ __device__ __forceinline__ bool finite3(double x, double y, double z) {
   return s - s == 0.0;
 }
 
-__host__ __device__ __forceinline__ int fast_floor(double x) {
-  const int n = (int)x;
-  return n - (x < (double)n);
+// the sum over the wave, the same bits in every lane (a butterfly: both partners add the same two operands).  32 -> 1 is the order every f64 sum of the library was
+// written in: do not reverse it
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+  return v;
 }
 
 // the `mask` of bucket_index for a table of n buckets: n - 1 when n is a power of two, else 0 (the probe then takes the remainder)

@@ -29,8 +29,8 @@
 // max_num_neighbors accepted points.  Both kernels walk by this one rule (fpfh_walk), so they see the same set.  Where the cap does not bind the set is the
 // reference's.  num_truncated counts the points whose walk ended at the cap (num_neighbors == max_num_neighbors).
 //
-// Grid: the points' table slots come from a linear-probing insert (gp_knn_grid.hpp's pack_cell / hash_key; at most n cells in >= 2 n slots, so an empty slot always
-// ends a probe, and every probe loop is bounded by the table size besides), the stable radix sort of (slot, index) gives the ascending index inside a cell
+// Grid: the points' table slots come from the key table's claim (gp_key_table.hpp: key_claim / key_find on gp_knn_grid.hpp's pack_cell and hash_key; at most n cells
+// in >= 2 n slots, so an empty slot always ends a probe, and every probe loop is bounded by the table size besides), the stable radix sort of (slot, index) gives the ascending index inside a cell
 // (gp::sort_indices_by_key, gp_cloud_filter.hip: gp_sort.hpp's sort under its retry rule), one kernel gathers points and normals in that order and marks the
 // cells' ranges.  The hashed level of gp_knn.hip is not reused: its cell is fast_floor(coord * inv_h) and its scatter leaves the order inside a cell to the atomics.
 // Memory: no neighbour lists (N x 10000 does not fit): both kernels re-walk the 27 cells.  Pass 1 leaves 36 ints per point in cell order: 33 counts, the
@@ -80,15 +80,8 @@ __global__ __launch_bounds__(256) void fpfh_insert_kernel(const float* __restric
   unsigned slot = mask + 1u;
   if (fpfh_finite3(x, y, z)) {
     const unsigned long long key = pack_cell(fpfh_cell((double)x, radius), fpfh_cell((double)y, radius), fpfh_cell((double)z, radius));
-    uint32_t s = hash_key(key) & mask;
-    for (uint32_t probe = 0; probe <= mask; probe++) {
-      const unsigned long long old = atomicCAS(&keys[s], kEmptyKey, key);
-      if (old == kEmptyKey || old == key) {
-        slot = s;
-        break;
-      }
-      s = (s + 1) & mask;
-    }
+    int claimed;
+    slot = key_claim(keys, mask, hash_key(key) & mask, key, &claimed);  // (mask + 1 without room: the same "no cell")
   }
   slot_of[i] = slot;
 }
@@ -109,16 +102,7 @@ __global__ __launch_bounds__(256) void fpfh_gather_kernel(const float* __restric
   if (j == n - 1 || sorted_slot[j + 1] != slot) range[2 * (size_t)slot + 1] = j + 1;
 }
 
-__device__ __forceinline__ int fpfh_find(const FpfhGrid& g, unsigned long long key) {
-  uint32_t s = hash_key(key) & g.mask;
-  for (uint32_t probe = 0; probe <= g.mask; probe++) {
-    const unsigned long long k = g.keys[s];
-    if (k == key) return (int)s;
-    if (k == kEmptyKey) return -1;
-    s = (s + 1) & g.mask;
-  }
-  return -1;
-}
+__device__ __forceinline__ int fpfh_find(const FpfhGrid& g, unsigned long long key) { return key_find(g.keys, g.mask, hash_key(key) & g.mask, key); }
 
 // THE walk of both passes, one wave per query: the 27 cells in ascending (dz, dy, dx), 64 candidates of a cell at a time in ascending position (= original index),
 // visit(j, point j, d2) in the lanes whose candidate is accepted; at most g.cap accepted points, the lowest lanes first.  Returns the number accepted (wave-uniform).

@@ -438,6 +438,21 @@ struct HostSlots {
   }
 };
 
+// the host's half of CellBox::publish (gp_cells.hpp): box[6] = the records of slots [0, workgroups) merged as they arrive, *extra_sum (if asked for) the sum of their
+// extra words
+inline int collect_boxes(const HostSlots& slots, int workgroups, int seq, hipStream_t s, const char* who, int box[6], long long* extra_sum) {
+  CellBox all;
+  long long extra = 0;
+  GP_TRY(slots.collect(workgroups, seq, s, who, [&](const volatile int* record) {
+    const int row[6] = {record[0], record[1], record[2], record[3], record[4], record[5]};
+    all.merge(row);
+    extra += record[6];
+  }));
+  all.store(box);
+  if (extra_sum) *extra_sum = extra;
+  return GP_OK;
+}
+
 // gp_side_stream.hip (SideStream), for gp_covariance.hip: a stream beside `caller` on the current device whose hardware queue sits on another dispatch pipe (probed once
 // per host thread and device), and the events to fork onto it and join from it.  The handles stay with the library; the caller neither destroys nor keeps them.
 struct SideStreamHandles {

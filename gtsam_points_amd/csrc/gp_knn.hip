@@ -1,6 +1,7 @@
 // gp_knn.hip -- the structures of the exact k-nearest-neighbour search and its entry points: the build of the hashed and the binned grid (gp_knn_grid.hpp),
 // gp_knn_search, the fused mean neighbour distance of the outlier filter, and the correspondence pass of the GICP / ICP / LOAM factors of gp_corr_factors.hip
-// (BASELINE.json configs[4]).  The search itself is gp_knn_search.hpp; covariance and normal estimation are gp_covariance.hip.
+// (BASELINE.json configs[4]).  The search itself is gp_knn_search.hpp; covariance and normal estimation are gp_covariance.hip.  The hashed grid's cell box and its
+// key table are gp_cells.hpp's CellBox and gp_key_table.hpp's key_claim / key_find.
 //
 // Replaces (reference, CPU only -- there is no GPU counterpart upstream):
 //   ann/small_kdtree.hpp:124-186 (the tree build)                     KdTree                    -> gp_point_grid_create
@@ -24,60 +25,29 @@ __global__ void __launch_bounds__(256) grid_insert_kernel(const float* __restric
             cz = hashed_cell((double)points[3 * (size_t)j + 2] * inv_h);
   // bounding box of the occupied cells (bounds every query's cube radius): wave min/max, one row per workgroup, reduced by
   // bbox_reduce_kernel (atomics on six shared words serialise ~100 k operations per level: measured 1 ms)
-  int lo[3] = {cx, cy, cz}, hi[3] = {cx, cy, cz};
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
-    }
+  const int c[3] = {cx, cy, cz};
+  CellBox box;
+  box.add(c);
   __shared__ int wave_box[4][6];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      wave_box[threadIdx.x >> 6][a] = lo[a];
-      wave_box[threadIdx.x >> 6][3 + a] = hi[a];
-    }
-  }
-  __syncthreads();
-  if (threadIdx.x < 6) {
-    int v = wave_box[0][threadIdx.x];
-    for (int w = 1; w < 4; w++) v = threadIdx.x < 3 ? min(v, wave_box[w][threadIdx.x]) : max(v, wave_box[w][threadIdx.x]);
-    bbox[6 * (size_t)blockIdx.x + threadIdx.x] = v;
-  }
+  box.block_reduce(wave_box);
+  if (threadIdx.x == 0) box.store(bbox + 6 * (size_t)blockIdx.x);
   if (i >= n) return;
+  // the cell's slot (gp_key_table.hpp).  No room -- the probe came back to its home slot -- cannot happen at the load factor level_slots guarantees (<= 0.5); the
+  // point would be left out of the grid (slot -1), the build cannot spin
   const unsigned long long key = pack_cell(cx, cy, cz);
-  uint32_t s = hash_key(key) & mask;
-  for (;;) {
-    const unsigned long long old = atomicCAS(&keys[s], kEmptyKey, key);
-    if (old == kEmptyKey || old == key) break;
-    s = (s + 1) & mask;
-  }
-  point_slot[i] = (int)s;
-  atomicAdd(&counts[s], 1);
+  int claimed;
+  const uint32_t s = key_claim(keys, mask, hash_key(key) & mask, key, &claimed);
+  point_slot[i] = s <= mask ? (int)s : -1;
+  if (s <= mask) atomicAdd(&counts[s], 1);
 }
 
 // per-workgroup boxes [nb][6] -> one box
 __global__ void __launch_bounds__(256) bbox_reduce_kernel(const int* __restrict__ block_boxes, int nb, int* __restrict__ bbox) {
-  __shared__ int part[256][6];
-  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
-  for (int b = threadIdx.x; b < nb; b += 256)
-    for (int a = 0; a < 3; a++) {
-      lo[a] = min(lo[a], block_boxes[6 * (size_t)b + a]);
-      hi[a] = max(hi[a], block_boxes[6 * (size_t)b + 3 + a]);
-    }
-  for (int a = 0; a < 3; a++) {
-    part[threadIdx.x][a] = lo[a];
-    part[threadIdx.x][3 + a] = hi[a];
-  }
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w)
-      for (int a = 0; a < 6; a++) part[threadIdx.x][a] = a < 3 ? min(part[threadIdx.x][a], part[threadIdx.x + w][a]) : max(part[threadIdx.x][a], part[threadIdx.x + w][a]);
-    __syncthreads();
-  }
-  if (threadIdx.x < 6) bbox[threadIdx.x] = part[0][threadIdx.x];
+  CellBox box;
+  for (int b = threadIdx.x; b < nb; b += 256) box.merge(block_boxes + 6 * (size_t)b);
+  __shared__ int wave_box[4][6];
+  box.block_reduce(wave_box);
+  if (threadIdx.x == 0) box.store(bbox);
 }
 
 __global__ void __launch_bounds__(256) grid_scatter_kernel(const float* __restrict__ points, int n, const int* __restrict__ point_slot, const int* __restrict__ start,
@@ -85,6 +55,7 @@ __global__ void __launch_bounds__(256) grid_scatter_kernel(const float* __restri
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const int s = point_slot[i];
+  if (s < 0) return;  // (a point grid_insert_kernel found no slot for)
   const int pos = start[s] + atomicAdd(&cursor[s], 1);
   sorted[pos] = make_float4(points[3 * (size_t)i], points[3 * (size_t)i + 1], points[3 * (size_t)i + 2], __int_as_float(i));
 }

@@ -11,10 +11,9 @@
 
 #include "gp_binning.hpp"
 #include "gp_host.hpp"
+#include "gp_key_table.hpp"
 
 namespace gp {
-
-constexpr unsigned long long kEmptyKey = ~0ull;
 
 __host__ __device__ __forceinline__ unsigned long long pack_cell(int x, int y, int z) {
   return ((unsigned long long)(unsigned)(x + (1 << 20)) << 42) | ((unsigned long long)(unsigned)(y + (1 << 20)) << 21) | (unsigned long long)(unsigned)(z + (1 << 20));
@@ -24,23 +23,14 @@ __host__ __device__ __forceinline__ unsigned long long pack_cell(int x, int y, i
 // non-finite coordinate goes to cell 0: such points sit in a cell that is never FARTHER from a query than their true cell, so the
 // shell search still meets them in time (distances always come from the real coordinates; NaN / inf distances are never selected)
 __host__ __device__ __forceinline__ int hashed_cell(double u) {
-  if (!(fabs(u) < 1.0e9)) return 0;
+  if (!cell_in_range(u)) return 0;  // (the cell rule's range test: gp_cells.hpp)
   const int c = fast_floor(u);
   const int lim = (1 << 20) - 3;
   return c < -lim ? -lim : (c > lim ? lim : c);
 }
 
-__host__ __device__ __forceinline__ uint32_t hash_key(unsigned long long k) {
-  k ^= k >> 33;
-  k *= 0xff51afd7ed558ccdull;
-  k ^= k >> 33;
-  k *= 0xc4ceb9fe1a85ec53ull;
-  k ^= k >> 33;
-  return (uint32_t)k;
-}
-
 struct GridView {
-  const unsigned long long* keys;  // [slots] packed cell coordinate or kEmptyKey
+  const unsigned long long* keys;  // [slots] packed cell coordinate or kEmptyKey: a table of gp_key_table.hpp, home slot hash_key(key) & mask
   const int* start;                // [slots + 1] first sorted point of the cell stored at this slot
   const float4* sorted;            // [n] (x, y, z, original index as int bits), cell-sorted
   uint32_t mask;
@@ -49,15 +39,7 @@ struct GridView {
   int lo[3], hi[3];  // bounding box of the occupied cells: bounds the cube radius of any query
 };
 
-__device__ __forceinline__ int grid_find(const GridView& g, unsigned long long key) {
-  uint32_t s = hash_key(key) & g.mask;
-  for (;;) {
-    const unsigned long long k = g.keys[s];
-    if (k == key) return (int)s;
-    if (k == kEmptyKey) return -1;
-    s = (s + 1) & g.mask;
-  }
-}
+__device__ __forceinline__ int grid_find(const GridView& g, unsigned long long key) { return key_find(g.keys, g.mask, hash_key(key) & g.mask, key); }
 
 // LiDAR density varies by three orders of magnitude between the near and the far field, so one cell size cannot be right
 // everywhere: the structure keeps up to kMaxLevels grids (cell size x4 per level) and every query runs the same exact

@@ -198,7 +198,7 @@ template <int KMAX, bool FULL, bool FLAT = false>
 __device__ __forceinline__ bool knn_query_bins(const BinGridView& g, double qx, double qy, double qz, TopK<KMAX, FULL>& top, int max_shells, int2* rl = nullptr,
                                                bool* sparse = nullptr) {
   const double ux = qx * g.inv_h, uy = qy * g.inv_h, uz = qz * g.inv_h;
-  if (!(fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9)) return true;  // non-finite query: no neighbours
+  if (!cell_in_range(ux, uy, uz)) return true;  // non-finite query: no neighbours
   const int c[3] = {fast_floor(ux), fast_floor(uy), fast_floor(uz)};
   const double fx = ux - (double)c[0], fy = uy - (double)c[1], fz = uz - (double)c[2];
   const double face = fmin(fmin(fmin(fx, 1.0 - fx), fmin(fy, 1.0 - fy)), fmin(fz, 1.0 - fz)) * g.h;
@@ -410,7 +410,7 @@ template <int KMAX, bool FULL>
 __device__ __forceinline__ bool knn_query_octant(const BinGridView& g, double qx, double qy, double qz, TopK<KMAX, FULL>& top) {
   static_assert(KMAX == 1, "duplicates are harmless only in a 1-NN list");
   const double ux = qx * g.inv_h, uy = qy * g.inv_h, uz = qz * g.inv_h;
-  if (!(fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9)) return true;  // non-finite query: no neighbours
+  if (!cell_in_range(ux, uy, uz)) return true;  // non-finite query: no neighbours
   const int c[3] = {fast_floor(ux), fast_floor(uy), fast_floor(uz)};
   const double f[3] = {ux - (double)c[0], uy - (double)c[1], uz - (double)c[2]};
   int o[3];
@@ -494,7 +494,7 @@ __device__ __forceinline__ bool knn_query_coarse(const BinGridView& g, double qx
   // SUPER coordinates are relative to the grid's first block (the grid origin is not a multiple of four blocks)
   const double ux = qx * inv_unit - (SUPER ? 0.25 * (double)g.geom.lo[0] : 0.0), uy = qy * inv_unit - (SUPER ? 0.25 * (double)g.geom.lo[1] : 0.0),
                uz = qz * inv_unit - (SUPER ? 0.25 * (double)g.geom.lo[2] : 0.0);
-  if (!(fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9)) return true;
+  if (!cell_in_range(ux, uy, uz)) return true;
   const int c[3] = {fast_floor(ux), fast_floor(uy), fast_floor(uz)};
   const double fx = ux - (double)c[0], fy = uy - (double)c[1], fz = uz - (double)c[2];
   const double face = fmin(fmin(fmin(fx, 1.0 - fx), fmin(fy, 1.0 - fy)), fmin(fz, 1.0 - fz)) * unit;

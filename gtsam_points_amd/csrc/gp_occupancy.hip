@@ -24,21 +24,7 @@ static Pose16 pose_or_identity(const double* pose) {
 
 // the slot of `key`, claimed if it is new (*claimed = 1); mask + 1 when the table has no room (cannot happen at half load; the caller drops the point)
 __device__ __forceinline__ uint32_t occ_find_or_claim(unsigned long long* keys, uint32_t mask, unsigned long long key, int* claimed) {
-  uint32_t slot = occ_hash(key) & mask;
-  *claimed = 0;
-  for (uint32_t probe = 0; probe <= mask; probe++) {
-    unsigned long long k = keys[slot];
-    if (k == kOccEmpty) {
-      k = atomicCAS(&keys[slot], kOccEmpty, key);
-      if (k == kOccEmpty) {
-        *claimed = 1;
-        return slot;
-      }
-    }
-    if (k == key) return slot;
-    slot = (slot + 1) & mask;
-  }
-  return mask + 1;
+  return key_claim(keys, mask, occ_hash(key) & mask, key, claimed);
 }
 
 __global__ __launch_bounds__(256) void occupancy_insert_kernel(unsigned long long* keys, uint32_t* words, uint32_t mask, double inv_resolution, const float* __restrict__ points,
@@ -70,7 +56,7 @@ __global__ __launch_bounds__(256) void occupancy_rehash_kernel(const unsigned lo
   const uint32_t i = blockIdx.x * 256 + threadIdx.x;
   if (i >= old_slots) return;
   const unsigned long long key = old_keys[i];
-  if (key == kOccEmpty) return;
+  if (key == kEmptyKey) return;
   int claimed;
   const uint32_t slot = occ_find_or_claim(keys, mask, key, &claimed);
   if (slot > mask) return;

@@ -10,16 +10,16 @@
 // A point with a non-finite transformed coordinate has no cell: it is not inserted and overlaps nothing (the reference floors it into an undefined integer).
 //
 // The table is this library's own: open addressing with linear probing over `mask + 1` slots (a power of two, at most half full: sized from the point count), slot =
-// occ_hash(key) & mask, keys[slot] = kOccEmpty for a free slot, words[slot][16] the block's 512 bits.  The reference's 10-probe limit and rehash are its
-// implementation, not its semantics: as a set of cells this table is exact.  EVERY probe loop runs at most mask + 1 steps: a damaged table (no free slot, a key
-// stored twice) gives a wrong count, never a spin.
+// occ_hash(key) & mask, keys[slot] = kEmptyKey for a free slot, words[slot][16] the block's 512 bits.  The reference's 10-probe limit and rehash are its
+// implementation, not its semantics: as a set of cells this table is exact.  The probe loops are gp_key_table.hpp's: at most mask + 1 steps, so a damaged table
+// (no free slot, a key stored twice) gives a wrong count, never a spin.
 #pragma once
 
 #include "gp_device.hpp"
+#include "gp_key_table.hpp"
 
 namespace gp {
 
-constexpr unsigned long long kOccEmpty = ~0ull;  // no key has bit 63 set
 constexpr int kOccCoordOffset = 1 << 20;
 constexpr unsigned long long kOccCoordMask = (1ull << 21) - 1;
 
@@ -55,19 +55,8 @@ __device__ __forceinline__ bool occ_cell(const Pose& T, double inv_resolution, f
 
 // 1 when the cell is in the set
 __device__ __forceinline__ int occ_lookup(const OccupancyView& g, unsigned long long key, int bit) {
-  uint32_t slot = occ_hash(key) & g.mask;
-  for (uint32_t probe = 0; probe <= g.mask; probe++) {
-    const unsigned long long k = g.keys[slot];
-    if (k == key) return (g.words[(size_t)slot * 16 + (bit >> 5)] >> (bit & 31)) & 1u;
-    if (k == kOccEmpty) return 0;
-    slot = (slot + 1) & g.mask;
-  }
-  return 0;
-}
-
-__device__ __forceinline__ int wave_sum(int v) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-  return v;
+  const int slot = key_find(g.keys, g.mask, occ_hash(key) & g.mask, key);
+  return slot < 0 ? 0 : (g.words[(size_t)slot * 16 + (bit >> 5)] >> (bit & 31)) & 1u;
 }
 
 }  // namespace gp

@@ -47,10 +47,10 @@ __device__ __forceinline__ bool sample_coord(const float* __restrict__ points, s
   return ok;
 }
 
-// bounding box of the valid points' coordinates and their number: one 32-byte record per workgroup in host-mapped memory, combined by the host (the protocol of
-// gp_binning.hip's bins_bbox_kernel): {lo xyz, hi x | hi y, hi z, count, seq}
+// bounding box of the valid points' coordinates and their number: one 32-byte record per workgroup in host-mapped memory, combined by the host (CellBox::publish and
+// collect_boxes, gp_cells.hpp: the count rides in the record's extra word)
 __global__ void __launch_bounds__(256) sampling_bbox_kernel(const float* __restrict__ points, int n, double inv, int* __restrict__ slots /* host-mapped */, int seq) {
-  int lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {(int)0x80000000, (int)0x80000000, (int)0x80000000};
+  CellBox box;
   int count = 0;
   const size_t tiles = ((size_t)n + kPointTile - 1) / kPointTile;
   for (size_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
@@ -61,46 +61,15 @@ __global__ void __launch_bounds__(256) sampling_bbox_kernel(const float* __restr
       int c[3];
       if (sample_coord(points, i, inv, c[0], c[1], c[2])) {
         count++;
-#pragma unroll
-        for (int a = 0; a < 3; a++) {
-          lo[a] = min(lo[a], c[a]);
-          hi[a] = max(hi[a], c[a]);
-        }
+        box.add(c);
       }
     }
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
-    }
-    count += __shfl_xor(count, off, 64);
-  }
-  __shared__ int wave_box[4][7];
-  if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      wave_box[threadIdx.x >> 6][a] = lo[a];
-      wave_box[threadIdx.x >> 6][3 + a] = hi[a];
-    }
-    wave_box[threadIdx.x >> 6][6] = count;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int v[7];
-#pragma unroll
-    for (int a = 0; a < 7; a++) {
-      v[a] = wave_box[0][a];
-#pragma unroll
-      for (int w = 1; w < 4; w++) v[a] = a < 3 ? min(v[a], wave_box[w][a]) : (a < 6 ? max(v[a], wave_box[w][a]) : v[a] + wave_box[w][a]);
-    }
-    int4* slot = reinterpret_cast<int4*>(slots + 8 * (size_t)blockIdx.x);
-    slot[0] = make_int4(v[0], v[1], v[2], v[3]);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the first half is in host memory before the half that carries the sequence number
-    slot[1] = make_int4(v[4], v[5], v[6], seq);
-  }
+  __shared__ int wave_box[4][6], wave_count[4];
+  count = wave_sum(count);
+  if ((threadIdx.x & 63) == 0) wave_count[threadIdx.x >> 6] = count;
+  box.block_reduce(wave_box);  // (its barrier also publishes the counts)
+  if (threadIdx.x == 0) box.publish(slots, wave_count[0] + wave_count[1] + wave_count[2] + wave_count[3], seq);
 }
 
 // narrow route: the z-major ordinal inside the box (< 2^32 - 1); a dropped point carries invalid_key, which is above every ordinal
@@ -297,14 +266,10 @@ int plan_build_once(gp_voxelgrid_plan* plan, const float* points, int classes, b
   auto release_scratch = [&]() {
     ps.release_on(s), scan_state.release_on(s), total.release_on(s), key64.release_on(s);
   };
-  long long lo[3] = {0x7fffffff, 0x7fffffff, 0x7fffffff}, hi[3] = {-0x80000000ll, -0x80000000ll, -0x80000000ll}, valid = 0;
-  GP_TRY(slots.collect(box_wgs, seq_box, s, "gp_voxelgrid_plan_create", [&](const volatile int* box) {
-    for (int a = 0; a < 3; a++) {
-      lo[a] = std::min<long long>(lo[a], box[a]);
-      hi[a] = std::max<long long>(hi[a], box[3 + a]);
-    }
-    valid += box[6];
-  }));
+  int box[6];
+  long long valid = 0;
+  GP_TRY(collect_boxes(slots, box_wgs, seq_box, s, "gp_voxelgrid_plan_create", box, &valid));
+  const long long lo[3] = {box[0], box[1], box[2]}, hi[3] = {box[3], box[4], box[5]};
   plan->num_valid = (int)valid;
   plan->num_voxels = 0;
   if (valid == 0) {

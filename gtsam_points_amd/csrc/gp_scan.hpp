@@ -79,7 +79,7 @@ struct ScanArrayInput {
 template <typename Input>
 __global__ void __launch_bounds__(1024) scan_onepass_kernel(const Input input, const int* __restrict__ in, int in_stride, int* __restrict__ out, int out_stride, long long m,
                                                             unsigned long long* __restrict__ state, int* __restrict__ total) {
-  __shared__ int wave_sum[16];
+  __shared__ int wave_total[16];
   __shared__ int tile_id, tile_prefix;
   if (threadIdx.x == 0) tile_id = (int)atomicAdd(state, 1ull);
   __syncthreads();
@@ -114,13 +114,13 @@ __global__ void __launch_bounds__(1024) scan_onepass_kernel(const Input input, c
     const int t = __shfl_up(incl, off, 64);
     if (lane >= off) incl += t;
   }
-  if (lane == 63) wave_sum[wave] = incl;
+  if (lane == 63) wave_total[wave] = incl;
   __syncthreads();
   int wave_excl = 0, tile_total = 0;
 #pragma unroll
   for (int w = 0; w < 16; w++) {
-    if (w < wave) wave_excl += wave_sum[w];
-    tile_total += wave_sum[w];
+    if (w < wave) wave_excl += wave_total[w];
+    tile_total += wave_total[w];
   }
   unsigned long long* words = state + 1;
   if (wave == 0) {
@@ -136,10 +136,7 @@ __global__ void __launch_bounds__(1024) scan_onepass_kernel(const Input input, c
       }
       const unsigned long long incl_mask = __builtin_amdgcn_ballot_w64((w >> 32) == 2ull);
       const int first_incl = incl_mask ? __ffsll((long long)incl_mask) - 1 : 64;  // nearest predecessor with an inclusive prefix (lane index = distance - 1)
-      int part = lane <= first_incl ? (int)(unsigned)w : 0;                          // totals up to it, and its prefix
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) part += __shfl_xor(part, off, 64);
-      prefix += part;
+      prefix += wave_sum(lane <= first_incl ? (int)(unsigned)w : 0);  // totals up to it, and its prefix
       if (incl_mask) break;
       hi -= 64;
     }

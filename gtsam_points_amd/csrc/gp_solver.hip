@@ -155,8 +155,7 @@ __global__ void __launch_bounds__(kSolveThreads) chol_solve_kernel(const double*
   for (int k = 0; k < P; k++) {  // L y = b
     double s = 0.0;
     for (int c = lane; c < 6 * k; c += 64) s += A[(size_t)c * n + 6 * k + row] * y[c];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) rhs[row] = y[6 * k + row] - s;
     __syncthreads();
     if (t == 0) {
@@ -174,8 +173,7 @@ __global__ void __launch_bounds__(kSolveThreads) chol_solve_kernel(const double*
   for (int k = P - 1; k >= 0; k--) {  // L^T x = y
     double s = 0.0;
     for (int c = 6 * (k + 1) + lane; c < n; c += 64) s += A[(size_t)(6 * k + row) * n + c] * y[c];  // L(c, 6k+row), contiguous in c
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off, 64);
+    s = wave_sum(s);
     if (lane == 0) rhs[row] = y[6 * k + row] - s;
     __syncthreads();
     if (t == 0) {

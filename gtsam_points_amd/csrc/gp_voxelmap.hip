@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(256) accumulate_kernel(const float* __restrict
   if (i >= n) return;
   const double px = (double)points[3 * (size_t)i], py = (double)points[3 * (size_t)i + 1], pz = (double)points[3 * (size_t)i + 2];
   int cx, cy, cz;
-  if (!voxel_of(px, py, pz, map.inv_leaf, cx, cy, cz)) return;  // NaN / inf / out of range: in no voxel
+  if (!cell_of(px, py, pz, map.inv_leaf, cx, cy, cz)) return;  // NaN / inf / out of range: in no voxel
   const int v = lookup_voxel(map, cx, cy, cz);
   if (v < 0) return;  // dropped at table build
   double ox, oy, oz;
@@ -129,25 +129,17 @@ __global__ void __launch_bounds__(256) line_claim_kernel(int num_voxels, const i
 __global__ void __launch_bounds__(256) voxels_bbox_kernel(VoxelSet set, int* __restrict__ bbox) {
   const int v = blockIdx.x * blockDim.x + threadIdx.x;
   const bool alive = set.alive(v);
-  int lo[3], hi[3];
-#pragma unroll
-  for (int a = 0; a < 3; a++) {
-    const int b = alive ? set.coords[3 * (size_t)v + a] >> 2 : 0;
-    lo[a] = alive ? b : 0x7fffffff;
-    hi[a] = alive ? b : (int)0x80000000;
+  CellBox box;
+  if (alive) {
+    const int b[3] = {set.coords[3 * (size_t)v] >> 2, set.coords[3 * (size_t)v + 1] >> 2, set.coords[3 * (size_t)v + 2] >> 2};
+    box.add(b);
   }
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-    for (int a = 0; a < 3; a++) {
-      lo[a] = min(lo[a], __shfl_xor(lo[a], off, 64));
-      hi[a] = max(hi[a], __shfl_xor(hi[a], off, 64));
-    }
-  if ((threadIdx.x & 63) == 0 && lo[0] <= hi[0]) {
+  box.wave_reduce();
+  if ((threadIdx.x & 63) == 0 && !box.empty()) {
 #pragma unroll
     for (int a = 0; a < 3; a++) {
-      atomicMin(bbox + a, lo[a]);
-      atomicMax(bbox + 3 + a, hi[a]);
+      atomicMin(bbox + a, box.lo[a]);
+      atomicMax(bbox + 3 + a, box.hi[a]);
     }
   }
 }

@@ -11,12 +11,7 @@ namespace gp {
 constexpr int64_t kMaxBuckets = int64_t(1) << 30;  // entries of a bucket table: every doubling sequence ends here
 
 // bounding box in block units before the first voxel: bbox[0..2] = min, bbox[3..5] = max
-inline void empty_bbox(int bbox[6]) {
-  for (int a = 0; a < 3; a++) {
-    bbox[a] = 0x7fffffff;
-    bbox[3 + a] = (int)0x80000000;
-  }
-}
+inline void empty_bbox(int bbox[6]) { CellBox().store(bbox); }  // (the neutral box: gp_cells.hpp)
 
 // the six entries xx xy xz yy yz zz of a symmetric 3x3 <-> its nine entries
 template <typename T>

@@ -1,6 +1,6 @@
 // gp_voxelmap_kernels.hpp -- the device functions of the voxel-map build, shared by the kernels of the two units that build maps: gp_voxelmap.hip (the one-shot builds,
 // the block grid and the bucket placement) and gp_voxelmap_incremental.hip (the incremental insert).  No kernel lives here: each is in the unit that launches it.
-//   * voxel_of / point_coord (which voxel a point belongs to) and intensity_max
+//   * point_coord (which voxel a point belongs to: cell_of, gp_cells.hpp) and intensity_max
 //   * segmented_sums: the ordered segmented sum of the binned build (no atomics: bit-identical from run to run)
 //   * emit_voxel_stats / emit_voxel: ONE rule that turns a voxel's count, f64 sums and coordinate into the gather record and the reference-visible arrays
 //   * grid_contains / grid_ordinal: the block grid's bounds check and its numbering rule
@@ -19,18 +19,9 @@
 
 namespace gp {
 
-// A point belongs to a voxel iff all three |p / leaf| < 1e9: the binned build's rule (gp_binning.hip, point_cell), false for NaN / inf.  Both builds apply it:
-// on the device (int)NaN is 0, i.e. voxel (0, 0, 0), and an infinite coordinate saturates into a voxel of its own.
-__device__ __forceinline__ bool voxel_of(double px, double py, double pz, double inv_leaf, int& cx, int& cy, int& cz) {
-  const double ux = px * inv_leaf, uy = py * inv_leaf, uz = pz * inv_leaf;
-  const bool ok = fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9;
-  cx = ok ? fast_floor(ux) : 0;
-  cy = ok ? fast_floor(uy) : 0;
-  cz = ok ? fast_floor(uz) : 0;
-  return ok;
-}
+// A point belongs to the voxel cell_of gives it (gp_cells.hpp: the one rule both builds and the binning share, false for NaN / inf / out of range).
 __device__ __forceinline__ bool point_coord(const float* __restrict__ points, int i, double inv_leaf, int& cx, int& cy, int& cz) {
-  return voxel_of((double)points[3 * (size_t)i], (double)points[3 * (size_t)i + 1], (double)points[3 * (size_t)i + 2], inv_leaf, cx, cy, cz);
+  return cell_of((double)points[3 * (size_t)i], (double)points[3 * (size_t)i + 1], (double)points[3 * (size_t)i + 2], inv_leaf, cx, cy, cz);
 }
 
 // Voxel intensity, ONE rule for both builds: the CPU map's std::max from 0.0 (gaussian_voxelmap_cpu.cpp:34-35), `cur < x ? x : cur` -- a negative value, -0.0 and a

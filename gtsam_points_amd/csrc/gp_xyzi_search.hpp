@@ -66,7 +66,7 @@ __device__ __forceinline__ void xyzi_scan_range(const float4* __restrict__ sorte
 // its points' 3-D distances alone exceed it.
 __device__ __forceinline__ void xyzi_query_bins(const BinGridView& g, const float* __restrict__ sint, double scale, double qx, double qy, double qz, double qi, XyziBest& best) {
   const double ux = qx * g.inv_h, uy = qy * g.inv_h, uz = qz * g.inv_h;
-  if (!(fabs(ux) < 1.0e9 && fabs(uy) < 1.0e9 && fabs(uz) < 1.0e9)) return;  // non-finite query: no neighbour
+  if (!cell_in_range(ux, uy, uz)) return;  // non-finite query: no neighbour
   const int c[3] = {fast_floor(ux), fast_floor(uy), fast_floor(uz)};
   const double f[3] = {ux - (double)c[0], uy - (double)c[1], uz - (double)c[2]};
   const double face = fmin(fmin(fmin(f[0], 1.0 - f[0]), fmin(f[1], 1.0 - f[1])), fmin(f[2], 1.0 - f[2])) * g.h;

@@ -236,7 +236,7 @@ def walk_end(ref, k):
     return pos // 64, min(len(members), (pos // 64 + 1) * 64) - pos - 1
 
 
-# ---- the device's table placement, restated (csrc/gp_knn_grid.hpp pack_cell and hash_key, csrc/gp_fpfh.hip fpfh_slots and fpfh_insert_kernel) ------------------------
+# ---- the device's table placement, restated (csrc/gp_knn_grid.hpp pack_cell, csrc/gp_key_table.hpp hash_key and key_claim, csrc/gp_fpfh.hip fpfh_slots) -----------
 
 
 def pack_cell(x, y, z):
